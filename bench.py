@@ -1,7 +1,12 @@
 #!/usr/bin/env python3
 """bench.py -- train voxels/sec of the 3D U-Net hot path on N MI355X (BASELINE.json metric).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times K steps and prints the headline line (`value`, `ms_per_step`, `loss`, `dice`, ...);
+``--dump-outputs DIR`` also writes what the last timed step handed its caller as .npy files.  Everything else the line can
+carry -- the in-library kernel timing and roofline blocks, the exact-fp32 figure, the CPU baseline with `parity_vs_cpu`, the
+bf16 `workloads` legs and the HIP-graph replays -- is measured only with ``--full``.
 
 N > 1 without a launcher (WORLD_SIZE unset): bench.py starts the N ranks itself (one child process per GPU,
 torchrun's environment contract, RCCL over xGMI) BEFORE any GPU call and only waits for them; under
@@ -11,7 +16,7 @@ A "step" is one full iteration of the reference's train loop (train.py:187-221) 
 resident in HBM: zero_grad, 2-channel gt, forward, argmax, BCE-with-logits, backward, (gradient all-reduce),
 Adam step, Dice counters.  Workload = BASELINE.json configs[1]: UNet3D(1,2,32), x = fp32 [2,1,128,128,128] per GPU.
 
-Prints ONE JSON line on rank 0 with `roofline` (dominant kernel family = the implicit-GEMM conv kernel, timed live
+Prints ONE JSON line on rank 0; with --full it carries `roofline` (dominant kernel family = the implicit-GEMM conv kernel, timed live
 with HIP events on the launch stream) and `cpu_baseline` (the CPU oracle == the reference's PyTorch-CPU arithmetic,
 timed in a child process on this box's host cores, started before the first GPU call and released after the last GPU leg).
 """
@@ -60,6 +65,7 @@ LEGS = [
 
 
 LABEL_THRESHOLD = 0.02
+PARAM_SAMPLE = 1 << 20       # --dump-outputs: parameters sampled after the last timed step's Adam update (4 MiB)
 PARITY_GRADS = ["encoder1.enc1conv1.weight", "encoder1.enc1norm1.weight", "bottleneck.bottleneckconv1.weight", "upconv1.weight", "conv.weight", "conv.bias"]
 PARITY_TOL = 1e-4            # north_star: logits / loss / Dice within 1e-4 of the reference's PyTorch-CPU path (fp32)
 PARITY_MARGIN = 2e-4         # a voxel whose reference logit margin is below twice the tolerance is not decisive for the argmax
@@ -472,11 +478,32 @@ def parity_vs_cpu(first, parity_file, input_sums):
     return out
 
 
+def dump_outputs(dirname, out, model):
+    """--dump-outputs: what the timed path handed its caller in the LAST timed step, one float32 / float64 .npy file each -- the
+    logits, the argmax mask, the loss, the Dice counters -- and a fixed seeded sample of the parameters its Adam update left in
+    the model (52 MiB at the headline shape).  The inputs are seeded, so two builds compare output for output."""
+    import numpy as np
+    import torch
+    os.makedirs(dirname, exist_ok=True)
+    for k in ("pred", "mask", "loss", "counts"):
+        if k in out:
+            dt = torch.float64 if k in ("loss", "counts") else torch.float32
+            np.save(os.path.join(dirname, f"{k}.npy"), out[k].detach().to(dt).cpu().numpy())
+    flat = torch.cat([p.detach().reshape(-1).float() for p in model.parameters()])
+    idx = torch.randint(0, flat.numel(), (min(PARAM_SAMPLE, flat.numel()),), generator=torch.Generator().manual_seed(0)).sort().values
+    np.save(os.path.join(dirname, "params_sample.npy"), flat[idx.to(flat.device)].cpu().numpy())
+
+
 def parse_args():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beyond the headline: in-library kernel timing and rooflines, the exact-fp32 figure, the CPU "
+                         "baseline and `parity_vs_cpu`, the bf16 `workloads` legs and the HIP-graph replays (the --no-* options below thin it out)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last one computed (logits, mask, loss, Dice counters, a parameter sample) as DIR/<name>.npy")
     ap.add_argument("--workload", default="unet3d_f32_2x128", choices=sorted(WORKLOADS))
     ap.add_argument("--conv-math", default=os.environ.get("MI355SEG_CONV_MATH") or "f16x3", choices=["fp32", "bf16x6", "f16x3"],
                     help="arithmetic of the k3 MFMA convolutions on fp32 tensors: f16x3 (default; fp32-accurate two-piece split on the fp16 matrix "
@@ -493,11 +520,16 @@ def parse_args():
     ap.add_argument("--no-prof", action="store_true", help="skip the in-library HIP-event kernel timing")
     ap.add_argument("--prof-all", action="store_true", help="HIP-event timing of every kernel family (adds ~1 %% to the step)")
     ap.add_argument("--hip-graph", action="store_true", help="experiment: replay the train step as captured HIP graphs (implies --no-prof)")
-    ap.add_argument("--dump-launches", default=None, help="write per-launch (family, ms, GFLOP, TFLOP/s) of the LAST timed step to this file")
+    ap.add_argument("--dump-launches", default=None, help="with --full: write per-launch (family, ms, GFLOP, TFLOP/s) of the LAST timed step to this file")
     ap.add_argument("--rehearse-cpu", action="store_true",
                     help="plumbing rehearsal without a GPU (tests only): the launch / rendezvous / reducer / barrier / JSON path on a "
                          "toy torch.nn model over gloo; the line is marked rehearsal and is NOT a measurement")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.dump_launches and not args.full:
+        ap.error("--dump-launches needs --full (the in-library kernel timing)")
+    if not args.full:               # a plain run: set-up, warm-up, the timed steps, the headline line
+        args.no_cpu_baseline = args.no_workloads = args.no_exact_leg = args.no_prof = True
+    return args
 
 
 def pmc_traffic():
@@ -611,7 +643,7 @@ def main():
     x_cpu, gt_cpu = synthetic_batch((B, cin, Dd, Hh, Ww), 1234 + rank)
     x, gt = x_cpu.to(dev), gt_cpu.to(dev)
     label_foreground_frac = float(gt_cpu.mean())
-    input_sums = batch_checksums(x_cpu, gt_cpu)
+    input_sums = batch_checksums(x_cpu, gt_cpu) if parity_file is not None else None
     del x_cpu, gt_cpu
     reducer = D.setup_replica(model)                # world > 1: rank 0's parameters / buffers everywhere + bucketed gradient reducer
     rank_devices = [str(dev)]
@@ -637,7 +669,7 @@ def main():
         opt.step()
         m = pred.argmax(1, keepdim=True)
         c = torch.stack([gt.long().sum(), m.sum(), ((gt.long() & m) != 0).sum(), ((gt.long() | m) != 0).sum()])
-        return {"loss": loss.detach(), "counts": c}
+        return {"pred": pred.detach(), "loss": loss.detach(), "counts": c}
 
     def step():
         if args.rehearse_cpu:
@@ -706,6 +738,8 @@ def main():
             dist.destroy_process_group()
         return 0
 
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, out, model)
     from mi355seg.utils.metric import metric_from_counts
     jac, dice = metric_from_counts(counts.cpu().tolist())
     vox_per_step = world * B * Dd * Hh * Ww
@@ -784,9 +818,10 @@ def main():
                                "achieved_counts": "algorithmic fp32 FLOPs (2 x voxels x 27 x Cin x Cout per launch), not MFMA issue slots",
                                "algorithmic_gflop_per_launch": fl / n / 1e9, "hbm_algorithmic_gbs": by / (tms * 1e-3) / 1e9}
     peak_step = MATH_PEAK[args.conv_math]
-    t_mfma = flop_per_vox * B * Dd * Hh * Ww / (peak_step * 1e12) * 1e3
-    t_hbm = bytes_per_vox * B * Dd * Hh * Ww / (PEAK_HBM_TBS * 1e12) * 1e3
-    res["step_roofline"] = {"conv_t_mfma_ms": t_mfma, "conv_t_hbm_ms": t_hbm, "frac_of_mfma_bound": t_mfma / ms, "frac_of_hbm_bound": t_hbm / ms}
+    if args.full:
+        t_mfma = flop_per_vox * B * Dd * Hh * Ww / (peak_step * 1e12) * 1e3
+        t_hbm = bytes_per_vox * B * Dd * Hh * Ww / (PEAK_HBM_TBS * 1e12) * 1e3
+        res["step_roofline"] = {"conv_t_mfma_ms": t_mfma, "conv_t_hbm_ms": t_hbm, "frac_of_mfma_bound": t_mfma / ms, "frac_of_hbm_bound": t_hbm / ms}
 
     if args.conv_math != "fp32" and not args.no_exact_leg and graphed is None and world == 1:
         # the same step with the exact-fp32 MFMA convolutions, reported beside the headline (outside the timed region)

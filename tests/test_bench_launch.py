@@ -8,6 +8,8 @@ import os
 import subprocess
 import sys
 
+import numpy as np
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
@@ -40,6 +42,22 @@ def test_bench_self_launches_two_ranks():
 def test_bench_single_rank_does_not_launch():
     r = _run(["--gpus", "1"])
     assert r["n_gpus"] == 1 and r["rccl_ranks"] == 1 and r["dist_backend"] is None and "comm" not in r
+
+
+def test_bench_dump_outputs_repeat_exactly(tmp_path):
+    """--dump-outputs: the last timed step's outputs as float32 / float64 .npy files, identical from run to run (seeded inputs)."""
+    dirs = [tmp_path / "a", tmp_path / "b"]
+    for d in dirs:
+        r = _run(["--gpus", "1", "--dump-outputs", str(d)])
+        assert r["steps"] == 3 and r["ms_per_step"] > 0
+    names = sorted(os.listdir(dirs[0]))
+    assert names == sorted(os.listdir(dirs[1])) and {"pred.npy", "loss.npy", "counts.npy", "params_sample.npy"} <= set(names)
+    total = 0
+    for n in names:
+        a, b = np.load(dirs[0] / n), np.load(dirs[1] / n)
+        assert a.dtype in (np.float32, np.float64) and np.array_equal(a, b), n
+        total += a.nbytes
+    assert np.load(dirs[0] / "pred.npy").shape == (2, 2, 8, 8, 8) and total <= 64e6
 
 
 def test_bench_under_an_external_launcher_is_one_of_the_ranks():

@@ -4,6 +4,7 @@ implementations (meta tensors: no kernel runs).  GPU part: the registered autogr
 wrappers the models use, and ``torch.library.opcheck`` accepts the registrations."""
 import pytest
 import torch
+from conftest import load_golden
 
 
 def test_custom_ops_are_registered_with_schemas_and_fake_impls():
@@ -96,7 +97,7 @@ def test_whole_unet3d_train_forward_backward_through_torch_ops_matches_the_refer
     from oracle.fill import fill_module_, make_input, make_labels
     from oracle.step import two_channel_gt
     ops, RELU = torch.ops.mi355seg, mi355seg.functional.ACT_RELU
-    g = np.load(os.path.join(golden_dir, "unet3d_f8_32.npz"))
+    g = load_golden("unet3d_f8_32")
     m = fill_module_(UNet3D(1, 2, 8)).cuda().train()        # parameter container only: its forward() is not called
 
     def block(h, blk):

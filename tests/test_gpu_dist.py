@@ -182,15 +182,15 @@ def test_two_rank_graphed_step_matches_the_eager_data_parallel_step():
                 assert torch.equal(v, out[1][mode][1][k]), (mode, k)
 
 
-def _bench(extra, timeout=900):
+def _bench(extra, timeout=900, full=True):
     import json
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env["MI355SEG_DIST_BACKEND"] = "gloo"
-    p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--workload", "unet3d_f32_1x64", "--no-workloads", "--no-cpu-baseline",
-                        "--steps", "8", "--warmup", "2"] + extra, capture_output=True, text=True, env=env, timeout=timeout)
+    p = subprocess.run([sys.executable, os.path.join(root, "bench.py")] + (["--full"] if full else []) + ["--workload", "unet3d_f32_1x64", "--no-workloads",
+                        "--no-cpu-baseline", "--steps", "8", "--warmup", "2"] + extra, capture_output=True, text=True, env=env, timeout=timeout)
     assert p.returncode == 0, p.stderr[-3000:]
     lines = [l for l in p.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, p.stdout[-2000:]
@@ -217,3 +217,21 @@ def test_bench_two_ranks_whole_hip_path_on_one_gpu():
     # two ranks time-share one GPU and stage 90 MB of gradients through the host (gloo): the aggregate is at best the one-rank rate and
     # must stay within 2x of "twice as many voxels in twice the time plus the gloo round trip" -- an order-of-magnitude plumbing check
     assert two["value"] > 0.1 * one["value"] and two["value"] < 2.0 * 2.0 * one["value"], (one["value"], two["value"])
+
+
+def test_bench_plain_run_is_the_headline_and_dumps_the_last_step(tmp_path):
+    """Without --full the line is the headline alone (no kernel timing, roofline or legs), and --dump-outputs writes what the last
+    timed step handed its caller: logits, mask, loss, Dice counters and a parameter sample, float32 / float64, within 64 MB."""
+    import numpy as np
+    r = _bench(["--gpus", "1", "--dump-outputs", str(tmp_path)], full=False)
+    assert r["steps"] == 8 and r["warmup"] == 2 and r["ms_per_step"] > 0 and r["value"] > 0 and r["higher_is_better"] is True
+    assert r["unit"] == "voxels/s" and r["dtype"] and r["metric"]
+    assert not {"roofline", "kernel_families", "step_roofline", "exact_fp32_ms_per_step", "cpu_baseline", "workloads"} & set(r)
+    pred, mask = np.load(tmp_path / "pred.npy"), np.load(tmp_path / "mask.npy")
+    loss, counts = np.load(tmp_path / "loss.npy"), np.load(tmp_path / "counts.npy")
+    assert pred.shape == (1, 2, 64, 64, 64) and pred.dtype == np.float32 and np.isfinite(pred).all()
+    assert mask.shape == (1, 1, 64, 64, 64) and set(np.unique(mask).tolist()) <= {0.0, 1.0}
+    assert (mask == pred.argmax(1)[:, None]).mean() > 0.999
+    assert loss.dtype == np.float64 and abs(float(loss) - r["loss"]) < 1e-6 and counts.dtype == np.float64 and counts.shape == (4,)
+    sample = np.load(tmp_path / "params_sample.npy")
+    assert sample.dtype == np.float32 and sample.size == 1 << 20 and np.isfinite(sample).all()

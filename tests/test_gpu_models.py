@@ -9,6 +9,7 @@ import torch
 
 from oracle.fill import fill_module_, make_class_labels, make_input, make_labels
 from oracle.step import two_channel_gt
+from conftest import load_golden
 
 pytestmark = pytest.mark.gpu
 TOL = 1e-4
@@ -46,7 +47,7 @@ def _masks(g):
 
 def test_vnet_train_step_vs_reference_fixture(seg, golden_dir):
     from mi355seg.models.three_d.vnet3d import VNet
-    g = np.load(os.path.join(golden_dir, "vnet_32.npz"))
+    g = load_golden("vnet_32")
     m = fill_module_(VNet(in_channels=1, classes=2)).cuda().train()
     masks = _masks(g)
     assert len(masks) == 4
@@ -186,7 +187,7 @@ def test_resunet_well_conditioned_fixture_plain_tolerance(seg, golden_dir):
     from mi355seg.models.three_d.residual_unet3d import UNet
     from oracle.fill import RESUNET96_HEAD_SCALE, fill_module_hash_, make_input_rough
     from oracle.nets import ResUNet
-    g = np.load(os.path.join(golden_dir, "resunet_f4_96.npz"))
+    g = load_golden("resunet_f4_96")
     K = 1 << 18
     x = make_input_rough((1, 4, 96, 96, 96), seed=2.0).cuda()
     labels = make_class_labels((1, 96, 96, 96), 4)

@@ -12,6 +12,8 @@ from oracle.fill import fill_module_, make_input, make_labels
 from oracle.metric import metric as oracle_metric
 from oracle.step import two_channel_gt
 
+from conftest import load_golden
+
 pytestmark = pytest.mark.gpu
 TOL = 1e-4
 
@@ -44,7 +46,7 @@ def seg():
 def test_unet3d_train_step_vs_reference_fixture(seg, golden_dir):
     from mi355seg.models.three_d.unet3d import UNet3D
     from mi355seg.engine import train_step
-    g = np.load(os.path.join(golden_dir, "unet3d_f8_32.npz"))
+    g = load_golden("unet3d_f8_32")
     m = fill_module_(UNet3D(in_channels=1, out_channels=2, init_features=8)).cuda().train()
     opt = torch.optim.Adam(m.parameters(), lr=1e-3)
     x = make_input((2, 1, 32, 32, 32)).cuda()

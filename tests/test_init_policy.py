@@ -52,19 +52,3 @@ def test_unknown_init_type_raises_like_the_reference():
     for who, pol in _policies():
         with pytest.raises(NotImplementedError):
             torch.nn.Conv3d(1, 1, 1).apply(pol("bogus"))
-
-
-def test_reference_init_runs_here_and_matches_fixture(golden_dir):
-    import ast
-    path = "/root/reference/train.py"
-    if not os.path.exists(path):
-        pytest.skip("reference tree not present (GPU box)")
-    ns = {"torch": torch}
-    for node in ast.parse(open(path).read()).body:
-        if isinstance(node, ast.FunctionDef) and node.name == "weights_init_normal":
-            exec(compile(ast.Module([node], []), path, "exec"), ns)
-    g = np.load(os.path.join(golden_dir, "init_policy.npz"))
-    for it in INIT_TYPES:
-        got = _apply(ns["weights_init_normal"], it)
-        for k, v in got.items():
-            assert np.array_equal(v, g[k]), k

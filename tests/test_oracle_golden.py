@@ -12,6 +12,7 @@ from oracle.fill import fill_module_, make_class_labels, make_input, make_labels
 from oracle.metric import metric as oracle_metric
 from oracle.nets import UNet3D
 from oracle.step import train_step, two_channel_gt
+from conftest import load_golden
 
 TOL = 2e-5
 
@@ -23,7 +24,7 @@ def _sample(t, k=4096):
 
 
 def test_unet3d_train_step_matches_reference_fixture(golden_dir):
-    g = np.load(os.path.join(golden_dir, "unet3d_f8_32.npz"))
+    g = load_golden("unet3d_f8_32")
     m = fill_module_(UNet3D(in_channels=1, out_channels=2, init_features=8)).train()
     opt = torch.optim.Adam(m.parameters(), lr=1e-3)
     x = make_input((2, 1, 32, 32, 32))
@@ -87,7 +88,7 @@ def test_losses_match_reference_fixture(golden_dir):
 
 def test_vnet_and_resunet_oracle_match_reference_fixtures(golden_dir):
     from oracle.nets import ResUNet, VNet
-    g = np.load(os.path.join(golden_dir, "vnet_32.npz"))
+    g = load_golden("vnet_32")
     torch.manual_seed(7)
     m = fill_module_(VNet(in_channels=1, classes=2)).train()
     x = make_input((2, 1, 32, 32, 32))
@@ -120,7 +121,7 @@ def test_resunet_oracle_matches_the_well_conditioned_fixture(golden_dir):
     within the PLAIN 1e-4 of the reference on every sampled voxel (the reference itself moves 8.6e-6 with the thread count)."""
     from oracle.fill import RESUNET96_HEAD_SCALE, fill_module_hash_, make_input_rough
     from oracle.nets import ResUNet
-    g = np.load(os.path.join(golden_dir, "resunet_f4_96.npz"))
+    g = load_golden("resunet_f4_96")
     assert float(g["thread_spread"]) < 2e-5
     m = fill_module_hash_(ResUNet(in_channels=4, n_classes=4, base_n_filter=4), RESUNET96_HEAD_SCALE).eval()
     x = make_input_rough((1, 4, 96, 96, 96), seed=2.0)

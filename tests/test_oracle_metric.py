@@ -84,22 +84,3 @@ def test_metric_from_counts_matches_reference_ratios(golden_dir):
     g, names = _metric_fixture(golden_dir)
     for n in names:
         assert list(metric_from_counts(g[n + "/counts"].tolist())) == g[n + "/jaccard_dice"].tolist(), n
-
-
-def test_reference_metric_runs_here_and_matches_fixture(golden_dir):
-    """Where /root/reference exists: run the lifted reference function again and compare with the committed fixture."""
-    import copy
-    import os
-    import ast
-    import pytest
-    path = "/root/reference/utils/metric.py"
-    if not os.path.exists(path):
-        pytest.skip("reference tree not present (GPU box)")
-    ns = {"np": np, "copy": copy}
-    for node in ast.parse(open(path).read()).body:
-        if isinstance(node, ast.FunctionDef) and node.name == "metric":
-            exec(compile(ast.Module([node], []), path, "exec"), ns)
-    g, names = _metric_fixture(golden_dir)
-    for n in names:
-        j, d = ns["metric"](torch.from_numpy(g[n + "/gt"]), torch.from_numpy(g[n + "/pred"]))
-        assert [j, d] == g[n + "/jaccard_dice"].tolist(), n

@@ -1,13 +1,13 @@
 #!/usr/bin/env python3
 """Reduce one rocprofv3 --pmc pass (SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_VALU_MFMA_BUSY_CYCLES GRBM_GUI_ACTIVE) of
-`bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-prof --no-exact-leg` into a per-kernel CSV:
+`bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --no-prof --no-exact-leg` into a per-kernel CSV:
 launches, total ms, effective clock (GRBM_GUI_ACTIVE / 8 XCDs / wall: MI355X_MICROARCH.md "DVFS give-back"), MFMA busy as a
 fraction of the chip's 1024 SIMDs, LDS bank-conflict cycles over active LDS cycles.
 
   cd /tmp && export TMPDIR=/tmp
   rocprofv3 --pmc SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_VALU_MFMA_BUSY_CYCLES GRBM_GUI_ACTIVE --kernel-trace --output-format csv \
-            -d $R/gpurun_out/pmc_sq -o s -- python3 $R/bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-prof --no-exact-leg
-  python tools/pmc_sq_summary.py gpurun_out/pmc_sq profiles/r02_pmc_sq_summary.csv"""
+            -d $OUT/pmc_sq -o s -- python3 $R/bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --no-prof --no-exact-leg
+  python tools/pmc_sq_summary.py $OUT/pmc_sq profiles/r02_pmc_sq_summary.csv   ($OUT: the profiler output folder)"""
 import collections
 import csv
 import glob

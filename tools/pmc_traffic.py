@@ -1,14 +1,14 @@
 #!/usr/bin/env python3
 """Reduce two rocprofv3 --pmc passes (FETCH_SIZE, WRITE_SIZE; they do not fit one pass on gfx950) of
-`bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-prof` into profiles/pmc_traffic.json: L2-to-fabric bytes per
+`bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --no-prof` into profiles/pmc_traffic.json: L2-to-fabric bytes per
 launch of the dominant kernel family (bf16x6 k3 forward + input gradient: conv_x3s_kernel and conv_igemm_kernel<MATH_X3, 3, ...>), FETCH_SIZE doubled as MI355X_MICROARCH.md prescribes.
 
 Collect on the GPU box (program directly after `--`, counters in their own runs):
   cd /tmp && export TMPDIR=/tmp
-  rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $R/gpurun_out/pmc_f -o f -- python3 $R/bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-prof
-  rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d $R/gpurun_out/pmc_w -o w -- python3 $R/bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-prof
+  rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $OUT/pmc_f -o f -- python3 $R/bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --no-prof
+  rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d $OUT/pmc_w -o w -- python3 $R/bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --no-prof
 then (here, in the git checkout, with NO source change since the snapshot that was profiled):
-  python tools/pmc_traffic.py gpurun_out/pmc_f gpurun_out/pmc_w profiles/pmc_traffic.json [conv_math] [kernel-name substring]
+  python tools/pmc_traffic.py $OUT/pmc_f $OUT/pmc_w profiles/pmc_traffic.json [conv_math] [kernel-name substring]   ($OUT: the profiler output folder)
 
 The result is stamped with the git HEAD, the conv math of the run and a hash of the kernel sources; bench.py only pastes it
 into `roofline.traffic` when the stamp is an ancestor of the code being run (or, on a box without .git, when the kernel
@@ -59,7 +59,7 @@ def main():
     write = w * 1024.0 / nw
     res = {
         "git_head": head, "conv_math": conv_math, "kernel_sources": KERNEL_SOURCES, "kernel_sources_sha16": h.hexdigest()[:16],
-        "source": "rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE (separate passes), python bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-prof",
+        "source": "rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE (separate passes), python bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --no-prof",
         "correction": "FETCH_SIZE doubled (gfx950 reports 1/2 of a wide coalesced read stream, MI355X_MICROARCH.md HBM section); WRITE_SIZE as read; unit KB*1024; "
                       "L2-to-fabric requests: Infinity-Cache hits are included, so this is an upper bound on HBM bytes",
         "kernel": "kernel names containing one of '" + match + "' (all k3 fwd + dgrad launches)",

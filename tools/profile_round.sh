@@ -17,7 +17,7 @@ LEG[resunet]="$R/tools/bench_model.py res_unet 1 4 160 192 160 --classes 4 --dty
 LEG[unetr]="$R/tools/bench_model.py unetr 1 1 96 96 96 --dtype bf16 --steps 3 --no-prof"
 case "$1" in
 stats)
-  rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats_cfg2 -- python3 $R/bench.py --steps 10 --warmup 3 --no-cpu-baseline --no-exact-leg --no-workloads > $O/stats_cfg2.log 2>&1
+  rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats_cfg2 -- python3 $R/bench.py --full --steps 10 --warmup 3 --no-cpu-baseline --no-exact-leg --no-workloads > $O/stats_cfg2.log 2>&1
   for n in vnet resunet unetr; do
     rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats_$n -- python3 ${LEG[$n]} > $O/stats_$n.log 2>&1
   done ;;
