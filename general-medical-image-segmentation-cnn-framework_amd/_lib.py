@@ -18,6 +18,7 @@ LIB_PATH = os.environ.get("MI355SEG_LIB_PATH") or os.path.join(_PKG, "libmi355se
 _CTYPE = {
     "int": ctypes.c_int,
     "float": ctypes.c_float,
+    "double": ctypes.c_double,
     "long long": ctypes.c_longlong,
     "size_t": ctypes.c_size_t,
 }

@@ -12,7 +12,7 @@ channel slices of concat buffers (a custom op's outputs may not alias its inputs
 Reference calls replaced: nn.Conv3d (unet3d.py:80-98), nn.ConvTranspose3d k2 s2 (unet3d.py:29-43), nn.MaxPool3d(2,2)
 (unet3d.py:19-25), nn.Upsample(2, nearest) (residual_unet3d.py:19), nn.BCEWithLogitsLoss + argmax + metric
 (train.py:204-221)."""
-from typing import Optional, Tuple
+from typing import List, Optional, Tuple
 
 import torch
 from torch import Tensor
@@ -284,6 +284,28 @@ def dice_counts(gt: Tensor, pred: Tensor) -> Tensor:
 @dice_counts.register_fake
 def _(gt, pred):
     return torch.empty(4, dtype=torch.int64, device=gt.device)
+
+
+@torch.library.custom_op("mi355seg::confusion_counts", mutates_args=())
+def confusion_counts(gt: Tensor, pred: Tensor) -> Tensor:
+    """utils/metric.py:34-55 on the device: int64[8] = the four counters of dice_counts, then tp, fp, fn, tn."""
+    return F.confusion_counts(gt, pred)
+
+
+@confusion_counts.register_fake
+def _(gt, pred):
+    return torch.empty(8, dtype=torch.int64, device=gt.device)
+
+
+@torch.library.custom_op("mi355seg::hd95", mutates_args=())
+def hd95(gt: Tensor, pred: Tensor, spacing: List[float], percentile: float = 95.0) -> Tensor:
+    """utils/metric.py:32 on the device: the percentile Hausdorff distance of two int64 label volumes, 0-dim fp64."""
+    return F.hd95(gt, pred, spacing, percentile)
+
+
+@hd95.register_fake
+def _(gt, pred, spacing, percentile=95.0):
+    return torch.empty((), dtype=torch.float64, device=gt.device)
 
 
 # ------------------------------------------------------------------------------------------------ layout (module boundary)
@@ -575,5 +597,5 @@ torch.library.register_autograd("mi355seg::cat_channels", lambda ctx, g: (g[...,
 
 OPS = ["conv3d", "conv3d_dgrad", "conv3d_wgrad", "conv_transpose3d_k2s2", "conv_transpose3d_k2s2_backward", "max_pool3d_2x",
        "max_pool3d_2x_backward", "upsample_nearest_2x", "upsample_nearest_2x_backward", "bce_argmax_dice", "bce_with_logits_backward",
-       "dice_counts", "to_channels_last", "to_channels_first", "norm_stats", "norm_apply_act", "norm_act_backward", "conv_bn_act",
+       "dice_counts", "confusion_counts", "hd95", "to_channels_last", "to_channels_first", "norm_stats", "norm_apply_act", "norm_act_backward", "conv_bn_act",
        "conv_bn_act_backward", "activation", "activation_backward", "cat_channels"]

@@ -1551,6 +1551,121 @@ def dice_counts(gt, pred):
     return out
 
 
+def _label_volume(t, what):
+    """int64 GPU label volume -> contiguous [D, H, W] (leading singleton dimensions, the reference's [C=1, D, H, W] and
+    [1, 1, D, H, W], are dropped)."""
+    if not t.is_cuda or t.dtype != torch.int64:
+        raise Mi355SegError(f"{what}: expected int64 tensors on the GPU")
+    if t.dim() < 3 or t.numel() != t.shape[-3] * t.shape[-2] * t.shape[-1] or t.numel() == 0:
+        raise Mi355SegError(f"{what}: expected one label volume [D, H, W] (leading dimensions of size 1 allowed), got {tuple(t.shape)}")
+    return t.reshape(t.shape[-3:]).contiguous()
+
+
+def _spacing3(spacing, what):
+    sp = tuple(float(v) for v in (spacing if hasattr(spacing, "__len__") else (spacing,) * 3))
+    if len(sp) != 3 or not all(v > 0 and v < float("inf") for v in sp):
+        raise Mi355SegError(f"{what}: spacing must be three positive numbers (sz, sy, sx), got {spacing!r}")
+    return sp
+
+
+def confusion_counts(gt, pred):
+    """utils/metric.py:34-55 on two int64 device tensors -> int64[8]: the four counters of ``dice_counts`` followed by
+    tp, fp, fn, tn (value sums of the reference's tp_array, fp_array, fn_array, tn_array)."""
+    if not gt.is_cuda or gt.dtype != torch.int64 or pred.dtype != torch.int64 or gt.numel() != pred.numel():
+        raise Mi355SegError("confusion_counts: expected two int64 tensors of one size on the GPU")
+    gt, pred = gt.contiguous(), pred.contiguous()
+    L = lib()
+    ws = workspace(L.query("mi355seg_confusion_counts_ws_bytes", gt.numel()), gt.device)
+    out = torch.empty(8, dtype=torch.int64, device=gt.device)
+    L.call("mi355seg_confusion_counts_i64", _p(gt), _p(pred), gt.numel(), _p(out), _p(ws), ws.numel(), _stream())
+    return out
+
+
+def mask_edges(gt, pred):
+    """Surface voxels of two label volumes (foreground != 0) -> (edges uint8 [2, D, H, W], info int64[8]).  A foreground voxel is an
+    edge voxel when one of its six face neighbours is background, outside the array counting as background.  info = (edge voxels of
+    gt, of pred, box lo z, y, x, box hi z, y, x) with the box around both edge sets, hi exclusive."""
+    gt, pred = _label_volume(gt, "mask_edges"), _label_volume(pred, "mask_edges")
+    if gt.shape != pred.shape:
+        raise Mi355SegError(f"mask_edges: shapes differ, {tuple(gt.shape)} and {tuple(pred.shape)}")
+    D, H, W = gt.shape
+    edges = torch.empty((2, D, H, W), dtype=torch.uint8, device=gt.device)
+    info = torch.empty(8, dtype=torch.int64, device=gt.device)
+    lib().call("mi355seg_mask_edges_i64", _p(gt), _p(pred), D, H, W, _p(edges), _p(info), _stream())
+    return edges, info
+
+
+def _full_box(shape):
+    return (0, 0, 0) + tuple(int(v) for v in shape)
+
+
+def edt3d(sites, spacing, box=None):
+    """Exact SQUARED Euclidean distance to the nearest non-zero voxel of each of the two site maps: uint8 [2, D, H, W] on the GPU ->
+    fp64 [2, bd, bh, bw].  ``box`` = (z0, y0, x0, bd, bh, bw) restricts the transform to a part of the volume that holds every site
+    (default: the whole volume); +inf where a map has no site."""
+    if not sites.is_cuda or sites.dtype != torch.uint8 or sites.dim() != 4 or sites.shape[0] != 2 or sites.numel() == 0:
+        raise Mi355SegError("edt3d: expected a uint8 tensor [2, D, H, W] on the GPU")
+    sz, sy, sx = _spacing3(spacing, "edt3d")
+    sites = sites.contiguous()
+    D, H, W = sites.shape[1:]
+    z0, y0, x0, bd, bh, bw = box or _full_box(sites.shape[1:])
+    L = lib()
+    ws = workspace(L.query("mi355seg_edt3d_ws_bytes", bd, bh, bw), sites.device)
+    dt2 = torch.empty((2, bd, bh, bw), dtype=torch.float64, device=sites.device)
+    L.call("mi355seg_edt3d_f64", _p(sites), D, H, W, z0, y0, x0, bd, bh, bw, sz, sy, sx, _p(dt2), _p(ws), ws.numel(), _stream())
+    return dt2
+
+
+def surface_distances(edges, dt2, n_gt, n_pred, box=None):
+    """(distances from the edge voxels of gt to the surface of pred, and from those of pred to the surface of gt): two fp64 vectors
+    of n_gt / n_pred elements in no particular order.  ``edges`` and the counts come from ``mask_edges``, ``dt2`` from ``edt3d``."""
+    if not edges.is_cuda or edges.dtype != torch.uint8 or edges.dim() != 4 or dt2.dtype != torch.float64 or not dt2.is_cuda:
+        raise Mi355SegError("surface_distances: expected uint8 edges [2, D, H, W] and fp64 squared distances on the GPU")
+    D, H, W = edges.shape[1:]
+    z0, y0, x0, bd, bh, bw = box or _full_box(edges.shape[1:])
+    if tuple(dt2.shape) != (2, bd, bh, bw):
+        raise Mi355SegError(f"surface_distances: squared distances of shape {tuple(dt2.shape)} do not match the box {(2, bd, bh, bw)}")
+    n_gt, n_pred = int(n_gt), int(n_pred)
+    stride = max(n_gt, n_pred, 1)
+    dist = torch.empty((2, stride), dtype=torch.float64, device=edges.device)
+    cursor = torch.empty(2, dtype=torch.int64, device=edges.device)
+    lib().call("mi355seg_surface_distances_f64", _p(edges.contiguous()), D, H, W, z0, y0, x0, bd, bh, bw, _p(dt2.contiguous()), n_gt, n_pred,
+               _p(dist), stride, _p(cursor), _stream())
+    return dist[0, :n_gt], dist[1, :n_pred]
+
+
+def _percentile(v, q):
+    """np.percentile(v, q) with linear interpolation between the order statistics at position q/100 * (n - 1); NaN for no samples."""
+    n = v.numel()
+    if n == 0:
+        return torch.full((), float("nan"), dtype=torch.float64, device=v.device)
+    s = torch.sort(v).values
+    pos = q / 100.0 * (n - 1)
+    lo = min(int(pos), n - 1)
+    hi = min(lo + 1, n - 1)
+    a, b = s[lo], s[hi]
+    return torch.where(a == b, a, a + (b - a) * (pos - lo))      # a == b: also keeps inf - inf out of it
+
+
+def hd95(gt, pred, spacing, percentile=95.0):
+    """Symmetric percentile Hausdorff distance between the surfaces of two int64 label volumes on the GPU, in the units of
+    ``spacing`` = (sz, sy, sx): what ``compute_hausdorff_distance(pred, gdth, percentile=95, spacing=spacing)`` of
+    utils/metric.py:32 returns.  -> 0-dim fp64 device tensor; not finite when either mask has no foreground.
+    The eight integers of ``mask_edges`` (edge counts and box) are read back to size the launches; nothing else leaves the device.
+    The transforms run on the bounding box of the two surfaces only: no site lies outside it and no distance is read outside it."""
+    sp = _spacing3(spacing, "hd95")
+    if not 0 <= float(percentile) <= 100:
+        raise Mi355SegError(f"hd95: percentile must lie in [0, 100], got {percentile}")
+    edges, info = mask_edges(gt, pred)
+    n_gt, n_pred, z0, y0, x0, z1, y1, x1 = info.tolist()
+    if n_gt == 0 or n_pred == 0:
+        return torch.full((), float("nan"), dtype=torch.float64, device=edges.device)
+    box = (z0, y0, x0, z1 - z0, y1 - y0, x1 - x0)
+    dt2 = edt3d(edges, sp, box)
+    d_gt, d_pred = surface_distances(edges, dt2, n_gt, n_pred, box)
+    return torch.maximum(_percentile(d_gt, float(percentile)), _percentile(d_pred, float(percentile)))
+
+
 class _BCEArgmaxDice(Function):
     """train.py:204,209,221 in ONE pass over the logits: BCE-with-logits mean loss (differentiable w.r.t. the logits),
     pred.argmax(1, keepdim) and the four integer Dice counters of metric(gt.argmax, mask)."""

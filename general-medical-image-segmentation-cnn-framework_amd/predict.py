@@ -6,7 +6,11 @@ The patch grid and the 'crop' aggregation restate torchio's GridSampler / GridAg
 torchio==0.20.3 in the reference's requirements.txt, absent here): per axis the patch origins are
 ``range(0, size + 1 - patch, patch - overlap)`` plus a last origin flush with the border; each predicted patch
 is cropped by ``overlap // 2`` on every side that does not touch the volume border before it is pasted.
-NIfTI / HD95 output (SimpleITK, monai) is out of scope; volumes are ``.npy`` and metrics go to metrics.csv.
+NIfTI output (SimpleITK) is out of scope; volumes are ``.npy`` and metrics go to metrics.csv.
+
+``config.spacing=sz,sy,sx`` (optional; one voxel spacing for every volume of the run) switches the metrics to the five numbers the
+reference computes with ``metric(gt_t, pred_t, spacing)`` (predict.py:154): metrics.csv then holds ``file, precision, recall,
+jaccard, dice, hs95`` and a last ``mean`` row (predict.py:186-200).  Without the key the file is ``file, jaccard, dice``, no mean row.
 """
 import csv
 import glob
@@ -20,7 +24,7 @@ from . import functional as F
 from .config import compose, parse_patch_size
 from .engine import mixed_precision_dtype
 from .registry import build_model
-from .utils.metric import metric_from_counts
+from .utils.metric import metric_from_counts, metric_with_spacing
 
 
 def grid_locations(size, patch, overlap):
@@ -121,6 +125,35 @@ def znorm(v):
     return (v - v.mean()) / std
 
 
+METRIC_COLUMNS = ("precision", "recall", "jaccard", "dice", "hs95")
+
+
+def parse_spacing(config):
+    """``config.spacing`` -> (sz, sy, sx) floats, or None when the key is absent or empty (metrics stay jaccard / dice)."""
+    sp = getattr(config, "spacing", None)
+    if sp is None or str(sp) in ("", "None", "none", "null"):
+        return None
+    vals = [float(v) for v in (str(sp).strip("()[] ").split(",") if isinstance(sp, str) else (sp if hasattr(sp, "__len__") else [sp]))]
+    if len(vals) == 1:
+        vals = vals * 3
+    if len(vals) != 3 or not all(v > 0 for v in vals):
+        raise ValueError(f"config.spacing must be three positive numbers sz,sy,sx, got {sp!r}")
+    return tuple(vals)
+
+
+def write_metrics_csv(path, rows):
+    """rows of {file, jaccard, dice}: those three columns, as they are.  Rows that also hold precision / recall / hs95 (a run with
+    config.spacing): the reference's five columns in its order and a last row of their means (predict.py:186-200)."""
+    full = bool(rows) and all(k in rows[0] for k in METRIC_COLUMNS)
+    fields = ["file"] + (list(METRIC_COLUMNS) if full else ["jaccard", "dice"])
+    with open(path, "w", newline="") as fh:
+        wr = csv.DictWriter(fh, fieldnames=fields)
+        wr.writeheader()
+        wr.writerows(rows)
+        if full:
+            wr.writerow({"file": "mean", **{k: float(np.mean([r[k] for r in rows])) for k in METRIC_COLUMNS}})
+
+
 def predict(config, model, log=print):
     device = torch.device("cuda", 0)
     if config.ckpt and str(config.ckpt) != "None":
@@ -143,18 +176,22 @@ def predict(config, model, log=print):
             y = torch.from_numpy(np.load(os.path.join(config.pred_gt_path, os.path.basename(f))).astype(np.float32))
             cases.append((os.path.splitext(os.path.basename(f))[0], x[None] if x.dim() == 3 else x, y[None] if y.dim() == 3 else y))
     rows = []
+    spacing = parse_spacing(config)
     for name, x, gt in cases:
         vol = znorm(x.to(device))
         mask = sliding_window_predict(model, vol, ps, overlap, batch_size=max(1, int(config.batch_size)), dtype=mixed_precision_dtype(config))
-        counts = F.dice_counts(gt.to(device).to(torch.int64).reshape(mask.shape), mask)
-        jac, dice = metric_from_counts(counts.cpu().tolist())
+        gt_lab = gt.to(device).to(torch.int64).reshape(mask.shape)
         np.save(os.path.join(config.hydra_path, f"{name}_pred.npy"), mask.cpu().numpy().astype(np.uint8))
+        if spacing:
+            row = dict(zip(METRIC_COLUMNS, metric_with_spacing(gt_lab, mask, spacing)))
+            rows.append({"file": name, **row})
+            log(f"{name}: " + " ".join(f"{k} {row[k]:.4f}" for k in METRIC_COLUMNS))
+            continue
+        counts = F.dice_counts(gt_lab, mask)
+        jac, dice = metric_from_counts(counts.cpu().tolist())
         rows.append({"file": name, "jaccard": jac, "dice": dice})
         log(f"{name}: dice {dice:.4f} jaccard {jac:.4f}")
-    with open(os.path.join(config.hydra_path, "metrics.csv"), "w", newline="") as fh:
-        wr = csv.DictWriter(fh, fieldnames=["file", "jaccard", "dice"])
-        wr.writeheader()
-        wr.writerows(rows)
+    write_metrics_csv(os.path.join(config.hydra_path, "metrics.csv"), rows)
     return rows
 
 

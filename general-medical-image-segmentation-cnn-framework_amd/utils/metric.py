@@ -1,6 +1,17 @@
 """Dice / Jaccard metric on the MI355X -- drop-in for ``metric(gt, pred, spacing=None)``
 of the reference's utils/metric.py:20-75.  The integer counters are reduced on the device
-(exact), only four int64 values cross PCIe; the final ratios use the reference's formula."""
+(exact), only four int64 values cross PCIe; the final ratios use the reference's formula.
+
+With ``spacing`` the reference returns five numbers, ``precision, recall, jaccard, dice, hs95`` (utils/metric.py:29-32,58-59,
+72-73, called as ``metric(gt_t, pred_t, spacing)`` by predict.py:154); so does this, from ``functional.confusion_counts`` and
+``functional.hd95``.  PINNED by the reference's own text: the order of the five, precision and recall, and the call
+``compute_hausdorff_distance(pred, gdth, percentile=95, spacing=spacing)``.  UNPINNED restatement: what monai's function does
+inside.  monai is absent here and the reference holds no fixture for it; restated from monai 1.3.1 (the reference's pin) without
+the source at hand as: the edge voxels of each mask by erosion with the default six-neighbour structure (outside the array is
+background), ``scipy.ndimage.distance_transform_edt(~edges_other, sampling=spacing)`` read at the edge voxels of the first, the
+percentile with linear interpolation between order statistics, the maximum of the two directions, and no channel dropped because
+there is one channel.  The result for a mask without foreground is the least certain part: it is NaN here, and the tests ask only
+that it is not finite."""
 import torch
 
 from .. import functional as F
@@ -13,9 +24,26 @@ def metric_from_counts(counts):
     return inter / (union + smooth), 2 * inter / (gsum + psum + smooth)
 
 
+def rates_from_counts(counts):
+    """counts = the eight integers of functional.confusion_counts -> (precision, recall), utils/metric.py:57-59."""
+    gsum, psum, tp = int(counts[0]), int(counts[1]), int(counts[4])
+    smooth = 0.001
+    return tp / (psum + smooth), tp / (gsum + smooth)
+
+
+def metric_with_spacing(gt, pred, spacing):
+    """(precision, recall, jaccard, dice, hs95) of two int64 device label volumes, [D, H, W] with leading singleton dimensions."""
+    counts = F.confusion_counts(gt, pred)
+    hs95 = F.hd95(gt, pred, spacing, 95)
+    counts = counts.cpu().tolist()
+    precision, recall = rates_from_counts(counts)
+    jaccard, dice = metric_from_counts(counts[:4])
+    return precision, recall, jaccard, dice, float(hs95)
+
+
 def metric(gt, pred, spacing=None):
     if spacing:
-        raise NotImplementedError("HD95 (monai) branch is out of scope (SURVEY.md section 2 row 10)")
+        return metric_with_spacing(gt.to(torch.int64), pred.to(torch.int64), spacing)
     gt = gt.to(torch.int64) if gt.dtype != torch.int64 else gt
     pred = pred.to(torch.int64) if pred.dtype != torch.int64 else pred
     return metric_from_counts(F.dice_counts(gt, pred).cpu().tolist())

@@ -421,6 +421,38 @@ int mi355seg_argmax_ch_f32(const float* logits, long long N, int K, long long S,
 int mi355seg_dice_counts_i64(const int64_t* gt, const int64_t* pred, long long numel,
                              int64_t* counts, void* ws, size_t ws_bytes, void* stream);
 
+/* The predict-time metrics beside Dice: metric(gt_t, pred_t, spacing) of predict.py:154 (utils/metric.py:29-32,45-59,72-73).
+ * All volumes are int64 label volumes [D,H,W]; foreground is != 0.
+ *
+ * counts[0..3] as mi355seg_dice_counts_i64; counts[4..7] = tp, fp, fn, tn of utils/metric.py:45-55: VALUE sums of gdth & pred,
+ * of pred where pred - gdth >= 1, of gdth where gdth - pred >= 1, and of 1 - (gdth | pred).
+ * ws: mi355seg_confusion_counts_ws_bytes(numel). */
+size_t mi355seg_confusion_counts_ws_bytes(long long numel);
+int mi355seg_confusion_counts_i64(const int64_t* gt, const int64_t* pred, long long numel,
+                                  int64_t* counts, void* ws, size_t ws_bytes, void* stream);
+
+/* Surface voxels of both masks in one pass (the get_mask_edges step of monai's compute_hausdorff_distance, utils/metric.py:32):
+ * a foreground voxel is an edge voxel when one of its six face neighbours is background; outside the array is background.
+ * edges: uint8 [2][D][H][W] (0 = gt, 1 = pred).  info: int64[8] = edge voxels of gt, of pred, then the bounding box of both edge
+ * sets together, lo z, y, x and hi z, y, x (hi exclusive); with no edge voxel at all lo = (D, H, W) and hi = 0. */
+int mi355seg_mask_edges_i64(const int64_t* gt, const int64_t* pred, int D, int H, int W, uint8_t* edges, int64_t* info, void* stream);
+
+/* Exact Euclidean distance transform with voxel spacing (sz, sy, sx), the distance_transform_edt step of the same call, for both
+ * edge maps at once, restricted to the box [z0, z0+bd) x [y0, y0+bh) x [x0, x0+bw) of the volume (every site must lie inside it):
+ * dt2[m][z][y][x] (fp64, box-relative, [2][bd][bh][bw]) = min over the sites s of sites[m] of (sz*dz)^2 + (sy*dy)^2 + (sx*dx)^2,
+ * the SQUARED distance; +inf where sites[m] is empty.  sites: uint8 [2][D][H][W] as mi355seg_mask_edges_i64 writes it.
+ * ws: mi355seg_edt3d_ws_bytes(bd, bh, bw). */
+size_t mi355seg_edt3d_ws_bytes(int bd, int bh, int bw);
+int mi355seg_edt3d_f64(const uint8_t* sites, int D, int H, int W, int z0, int y0, int x0, int bd, int bh, int bw,
+                       double sz, double sy, double sx, double* dt2, void* ws, size_t ws_bytes, void* stream);
+
+/* The two directed surface-distance sets of the same call: dist[0][0..n_gt) = sqrt(dt2[1]) at the edge voxels of gt,
+ * dist[1][0..n_pred) = sqrt(dt2[0]) at the edge voxels of pred; rows are row_stride doubles apart and the order inside a row is
+ * unspecified (the percentile sorts).  n_gt / n_pred are info[0] / info[1] of mi355seg_mask_edges_i64; cursor: int64[2] scratch. */
+int mi355seg_surface_distances_f64(const uint8_t* edges, int D, int H, int W, int z0, int y0, int x0, int bd, int bh, int bw,
+                                   const double* dt2, long long n_gt, long long n_pred, double* dist, long long row_stride,
+                                   int64_t* cursor, void* stream);
+
 /* The 2-channel target of the live loop (train.py:190-193): out[n][0] = (gt[n] == 0), out[n][1] = gt[n], float [N,2,S]. */
 int mi355seg_two_channel_gt_f32(const float* gt, float* out, long long N, long long S, void* stream);
 
