@@ -93,6 +93,10 @@ __global__ __launch_bounds__(256) void bce_bwd_kernel(const float* __restrict__ 
     }
 }
 
+// torch.argmax's order: the first maximum in scan order wins and a NaN beats every number (the first NaN wins), as
+// maxpool2_fwd_kernel (pool.hip) does for its window
+__device__ __forceinline__ bool nan_first_gt(float v, float best) { return v > best || (v != v && best == best); }
+
 __global__ __launch_bounds__(256) void argmax_kernel(const float* __restrict__ x, long long N, int K, long long S,
                                                       int64_t* __restrict__ mask) {
     const long long total = N * S;
@@ -100,7 +104,7 @@ __global__ __launch_bounds__(256) void argmax_kernel(const float* __restrict__ x
         long long n = i / S, s = i % S;
         const float* p = x + n * K * S + s;
         float best = p[0]; int bi = 0;
-        for (int k = 1; k < K; ++k) { float v = p[(long long)k * S]; if (v > best) { best = v; bi = k; } }
+        for (int k = 1; k < K; ++k) { float v = p[(long long)k * S]; if (nan_first_gt(v, best)) { best = v; bi = k; } }
         mask[i] = bi;
     }
 }
@@ -155,8 +159,8 @@ __global__ __launch_bounds__(kLossThreads) void bce_argmax_dice_kernel(const flo
         for (int k = 1; k < K; ++k) {
             float vx = px[(long long)k * S], vt = pt[(long long)k * S];
             l += bce_term(vx, vt);
-            if (vx > bx) { bx = vx; ix = k; }
-            if (vt > bt) { bt = vt; it = k; }
+            if (nan_first_gt(vx, bx)) { bx = vx; ix = k; }
+            if (nan_first_gt(vt, bt)) { bt = vt; it = k; }
         }
         lacc[0] += (double)l;
         mask[i] = ix;
@@ -327,6 +331,10 @@ __global__ __launch_bounds__(256) void softmax_ch_bwd_kernel(const float* __rest
     }
 }
 
+// cross_entropy_3D (loss_function.py:8-16: log_softmax + F.nll_loss(reduction="sum"), divided by the voxel count).  Labels: a voxel
+// whose label is not in [0, K) is IGNORED -- no term in the sum, a zero gradient row, the divisor stays N * S.  That is what
+// F.nll_loss does for its default ignore_index = -100; for every other such label (where ATen raises) it keeps the kernels one pass,
+// without a device-side flag and a synchronising read of it, and no label value ever indexes the logits or the class weights.
 __global__ __launch_bounds__(kLossThreads) void ce3d_fwd_kernel(const float* __restrict__ x, const int64_t* __restrict__ lab,
         const float* __restrict__ w, long long N, int K, long long S, double* __restrict__ part) {
     __shared__ double sh[4];
@@ -339,9 +347,11 @@ __global__ __launch_bounds__(kLossThreads) void ce3d_fwd_kernel(const float* __r
         for (int k = 0; k < K; ++k) m = fmaxf(m, p[(long long)k * S]);
         float sum = 0.f;
         for (int k = 0; k < K; ++k) sum += expf(p[(long long)k * S] - m);
-        const int l = (int)lab[i];
-        const float nll = (m + logf(sum)) - p[(long long)l * S];
-        acc[0] += (double)(w ? w[l] * nll : nll);
+        const long long l = lab[i];
+        if ((unsigned long long)l < (unsigned long long)K) {     // any other label (F.nll_loss's ignore_index -100 among them): no term
+            const float nll = logf(sum) - (p[l * S] - m);     // log_softmax's order: rounds at the size of the term, not of the logits
+            acc[0] += (double)(w ? w[l] * nll : nll);
+        }
     }
     block_sum<1>(acc, sh);
     if (threadIdx.x == 0) part[blockIdx.x] = acc[0];
@@ -356,10 +366,11 @@ __global__ __launch_bounds__(256) void ce3d_bwd_kernel(const float* __restrict__
         for (int k = 0; k < K; ++k) m = fmaxf(m, x[base + (long long)k * S]);
         float sum = 0.f;
         for (int k = 0; k < K; ++k) sum += expf(x[base + (long long)k * S] - m);
-        const int l = (int)lab[i];
-        const float sc = g * (w ? w[l] : 1.f), inv = 1.f / sum;
+        const long long l = lab[i];
+        const bool valid = (unsigned long long)l < (unsigned long long)K;      // an ignored voxel gets an exact zero, whatever its logits
+        const float sc = valid ? g * (w ? w[l] : 1.f) : 0.f, inv = 1.f / sum;
         for (int k = 0; k < K; ++k)
-            dx[base + (long long)k * S] = sc * (expf(x[base + (long long)k * S] - m) * inv - (k == l ? 1.f : 0.f));
+            dx[base + (long long)k * S] = valid ? sc * (expf(x[base + (long long)k * S] - m) * inv - (k == l ? 1.f : 0.f)) : 0.f;
     }
 }
 

@@ -223,6 +223,16 @@ def _require_cuda(t, what, allow_bf16=False):
         raise Mi355SegError(f"{what}: expected float32{' or bfloat16' if allow_bf16 else ''}, got {t.dtype}")
 
 
+def aligned_contiguous(t):
+    """``t.contiguous()`` at a 16-byte aligned address.  ``.contiguous()`` alone returns an already contiguous tensor as it is, and
+    with it a misaligned storage offset (``x[1:]`` of a batch, a view into a flat buffer); the kernels' 16 B/lane paths need the
+    alignment, so such a tensor is copied into storage of its own (the allocator hands out 256-byte aligned blocks)."""
+    t = t.contiguous()
+    if t.data_ptr() % 16:
+        t = t.clone(memory_format=torch.contiguous_format)
+    return t
+
+
 def cl_view(t, what="tensor", allow_bf16=True):
     """Return (tensor, ld) with tensor laid out NDHWC (last stride 1, dense in N,D,H,W with
     voxel pitch ld >= C).  Copies only if the given tensor does not already satisfy that."""
@@ -236,7 +246,7 @@ def cl_view(t, what="tensor", allow_bf16=True):
     ok = ok and (H == 1 or s[2] == W * ld) and (D == 1 or s[1] == H * W * ld) and (N == 1 or s[0] == D * H * W * ld)
     ok = ok and t.data_ptr() % 16 == 0          # the float4 paths assume a 16-byte aligned base
     if not ok:
-        t = t.contiguous()
+        t = aligned_contiguous(t)
         ld = C
     return t, ld
 
@@ -1502,8 +1512,8 @@ class _BCEWithLogits(Function):
     @staticmethod
     def forward(ctx, logits, target):
         _require_cuda(logits, "bce_with_logits input")
-        logits = logits.contiguous()
-        target = target.contiguous().to(torch.float32)
+        logits = aligned_contiguous(logits)
+        target = aligned_contiguous(target.to(torch.float32))
         if logits.shape != target.shape:
             raise ValueError(f"Target size ({tuple(target.shape)}) must be the same as input size ({tuple(logits.shape)})")
         L = lib()
@@ -1673,7 +1683,7 @@ class _BCEArgmaxDice(Function):
     @staticmethod
     def forward(ctx, logits, target):
         _require_cuda(logits, "bce_argmax_dice input")
-        logits, target = logits.contiguous(), target.contiguous().to(torch.float32)
+        logits, target = aligned_contiguous(logits), aligned_contiguous(target.to(torch.float32))     # (the backward is the float4 BCE kernel)
         if logits.shape != target.shape:
             raise ValueError(f"Target size ({tuple(target.shape)}) must be the same as input size ({tuple(logits.shape)})")
         N, K = logits.shape[0], logits.shape[1]
@@ -1721,7 +1731,7 @@ def two_channel_gt(gt):
 def znormalize(x):
     """tio.ZNormalization() of one volume on the device: (x - mean) / std over all voxels (unbiased std)."""
     _require_cuda(x, "znormalize input")
-    x = x.contiguous().to(torch.float32)
+    x = aligned_contiguous(x.to(torch.float32))
     L = lib()
     ws = workspace(L.query("mi355seg_znorm_ws_bytes", x.numel()), x.device)
     y = torch.empty_like(x)
@@ -1826,7 +1836,7 @@ class _SoftmaxCh(Function):
 
 
 def softmax_channels(x):
-    """torch.softmax(x, dim=1) for an NCDHW tensor."""
+    """torch.softmax(x, dim=1) for an NCDHW tensor of at most 16 classes (more: Mi355SegError)."""
     return _SoftmaxCh.apply(x)
 
 
@@ -1862,6 +1872,11 @@ class _CE3D(Function):
 
 
 def cross_entropy_3d(logits, labels, weight=None, size_average=True):
+    """loss_function.py:8-16: ``F.nll_loss(log_softmax(logits, 1), labels, weight, reduction="sum")``, divided by ``labels.numel()``
+    when ``size_average``.  Labels: a voxel whose label lies outside ``[0, K)`` is IGNORED -- it adds nothing to the sum, its
+    gradient row is exactly zero and the divisor stays ``labels.numel()``.  For ``-100`` that is F.nll_loss's own rule (its default
+    ``ignore_index``); for any other such value (``K``, ``-1``, ``2**40``), where F.nll_loss raises, this call does NOT raise: a
+    check would cost a device-to-host read per step, and the kernels never index the logits or ``weight`` with such a label."""
     return _CE3D.apply(logits, labels, weight, size_average)
 
 

@@ -76,7 +76,9 @@ class DiceLoss(nn.Module):
 
 
 class DiceLossss(nn.Module):
-    """loss_function.py:148-185 -- per-class 1 - (2 sum s*t + eps) / (sum s^2 + sum t^2 + eps), weighted mean."""
+    """loss_function.py:148-185 -- per-class 1 - (2 sum s*t + eps) / (sum s^2 + sum t^2 + eps), weighted mean.
+    ``softmax=True`` goes through functional.softmax_channels, which holds a voxel's classes in registers and raises
+    Mi355SegError for more than 16 classes; without it any class count is taken."""
 
     def __init__(self, n_classes):
         super().__init__()

@@ -413,7 +413,8 @@ int mi355seg_bce_logits_fwd_f32(const float* logits, const float* target, long l
 int mi355seg_bce_logits_bwd_f32(const float* logits, const float* target, const float* gscale,
                                 long long numel, float* dlogits, void* stream);
 
-/* pred.argmax(dim=1, keepdim=True) (train.py:204, predict.py:139): first max wins; int64 out [N,1,S] */
+/* pred.argmax(dim=1, keepdim=True) (train.py:204, predict.py:139): first max wins, a NaN beats every number and the first NaN
+ * wins (torch.argmax's order; mi355seg_bce_argmax_dice_f32 follows it for both of its argmaxes); int64 out [N,1,S] */
 int mi355seg_argmax_ch_f32(const float* logits, long long N, int K, long long S, int64_t* mask, void* stream);
 
 /* Integer counters of utils/metric.py:34-43 on two int64 label volumes:
@@ -495,7 +496,9 @@ int mi355seg_softmax_ch_f32(const float* x, float* y, long long N, int K, long l
 int mi355seg_softmax_ch_bwd_f32(const float* y, const float* dy, float* dx, long long N, int K, long long S, void* stream);
 
 /* cross_entropy_3D (loss_function.py:8-16): loss[0] = sum_v w[label_v] * (logsumexp_k x[v,k] - x[v,label_v]),
- * divided by the voxel count when size_average.  logits NCDHW [N,K,S], labels int64 [N,S], weight [K] or NULL. */
+ * divided by the voxel count when size_average.  logits NCDHW [N,K,S], labels int64 [N,S], weight [K] or NULL.
+ * A voxel whose label is outside [0, K) (F.nll_loss's ignore_index -100 among them) is ignored: no term in the sum, a zero
+ * gradient row, the divisor unchanged; no label value indexes the logits or the weights. */
 int mi355seg_ce3d_fwd_f32(const float* logits, const int64_t* labels, const float* weight, long long N, int K, long long S,
                           int size_average, float* loss, void* ws, size_t ws_bytes, void* stream);
 int mi355seg_ce3d_bwd_f32(const float* logits, const int64_t* labels, const float* weight, const float* gscale,

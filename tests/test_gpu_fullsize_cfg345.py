@@ -27,8 +27,11 @@ def _rnd(shape, seed, device="cpu"):
     return torch.randn(shape, generator=torch.Generator().manual_seed(seed)).to(device)
 
 
-def _step_twice(seg, build, xshape, classes, dtype):
+def _step_twice(seg, build, xshape, classes, dtype, criterion="bce"):
+    """criterion: "bce" (train.py:115) or "ce+dice", cfg 4's own -- cross_entropy_3D + DiceLoss on the library losses, as the
+    benchmark's cfg-4 leg steps it"""
     from mi355seg.engine import weights_init_normal
+    from mi355seg.utils import loss_function as LF
     F = seg.functional
 
     def run():
@@ -45,7 +48,10 @@ def _step_twice(seg, build, xshape, classes, dtype):
         opt.zero_grad(set_to_none=True)
         with seg.autocast(dtype):
             pred = m(x)
-        loss = F.bce_with_logits(pred, tgt)
+        if criterion == "ce+dice":
+            loss = LF.cross_entropy_3D(pred, lab[:, 0].contiguous()) + LF.DiceLoss()(pred, tgt)
+        else:
+            loss = F.bce_with_logits(pred, tgt)
         loss.backward()
         grads = torch.cat([p.grad.reshape(-1) for p in m.parameters() if p.grad is not None])
         opt.step()
@@ -67,7 +73,7 @@ def test_cfg3_vnet_full_size_step_is_deterministic(seg, dtype):
 @pytest.mark.parametrize("dtype", [BF, torch.float32])
 def test_cfg4_resunet_full_size_step_is_deterministic(seg, dtype):
     from mi355seg.models.three_d.residual_unet3d import UNet
-    _step_twice(seg, lambda: UNet(4, 4, 32), (1, 4, 160, 192, 160), 4, dtype)
+    _step_twice(seg, lambda: UNet(4, 4, 32), (1, 4, 160, 192, 160), 4, dtype, criterion="ce+dice")
 
 
 @pytest.mark.parametrize("dtype", [BF, torch.float32])
