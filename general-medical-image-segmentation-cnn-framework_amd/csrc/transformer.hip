@@ -20,6 +20,7 @@ struct GemmArgs {
     float* slabs;                   // [S][M][N] partial products when S > 1
     float* arowsum;                 // (direct kernels, one batch) arowsum[m] = sum_k A[m][k]: a Linear layer's bias gradient out of its weight-gradient GEMM
     const float* emul; const float* eadd; long long e_rs;      // (direct kernels, one batch) after bias / ReLU: C = C * emul[m][n] + eadd[m][n] (dropout mask, residual)
+    int lowp;                       // (gemm_kernel) round both operands to bf16 (RNE) on their way into LDS: the arithmetic of the bf16 small-GEMM kernels
 };
 
 constexpr int GT = 64, GK = 32, LDA_S = GK + 1, LDB_S = GT + 1;
@@ -83,6 +84,13 @@ struct TileMover {
 // MFMA accumulator each), K walked in steps of 32 with the next step's operands prefetched into registers while the
 // current one is multiplied.  blockIdx.z = batch * S + split; with S > 1 the raw partial tile goes to its slab and
 // gemm_splitk_epilogue applies alpha / bias / accumulate / ReLU after a fixed-order sum (deterministic).
+// g.lowp: a mi355seg_gemm_lowp_f32 shape outside the small-GEMM kernels' range (K % 8 != 0, a misaligned operand, more than 4,096 tiles).  The
+// operands are rounded to bf16 before they are multiplied -- a product of two bf16 values is exact in fp32, so this is the bf16 kernels' arithmetic
+// (bf16 operands, fp32 accumulation) and what autocast(bfloat16) computes does not depend on which kernel a shape or an address selects.
+__device__ __forceinline__ void round_to_bf16(float (&r)[8]) {
+#pragma unroll
+    for (int e = 0; e < 8; ++e) r[e] = (float)(bf16)r[e];
+}
 __global__ __launch_bounds__(256) void gemm_kernel(GemmArgs g) {
     __shared__ float As[GT * LDA_S];
     __shared__ float Bs[GK * LDB_S];
@@ -102,6 +110,7 @@ __global__ __launch_bounds__(256) void gemm_kernel(GemmArgs g) {
     ta.load(kbeg, tid, ra);
     tb.load(kbeg, tid, rb);
     for (int k0 = kbeg; k0 < kend; k0 += GK) {
+        if (g.lowp) { round_to_bf16(ra); round_to_bf16(rb); }
         ta.store(As, LDA_S, 1, tid, ra);
         tb.store(Bs, 1, LDB_S, tid, rb);
         __syncthreads();
@@ -671,7 +680,7 @@ static int gemm_impl(int lowp, const float* A, long long a_rs, long long a_cs, l
     const int avec = vec_ok(A, a_ofast ? a_rs : a_cs, a_ofast ? a_cs : a_rs, a_b0, a_b1);
     const int bvec = vec_ok(B, b_ofast ? b_cs : b_rs, b_ofast ? b_rs : b_cs, b_b0, b_b1);
     GemmArgs g{A, B, C, bias, a_rs, a_cs, a_b0, a_b1, b_rs, b_cs, b_b0, b_b1, c_rs, c_b0, c_b1, M, N, K, nb1, alpha, relu, accumulate,
-               S, kchunk, avec, bvec, (float*)ws, nullptr, nullptr, nullptr, 0};
+               S, kchunk, avec, bvec, (float*)ws, nullptr, nullptr, nullptr, 0, lowp};
     dim3 grid(cdiv(N, GT), cdiv(M, GT), nb0 * nb1 * S);
     hipLaunchKernelGGL(gemm_kernel, grid, dim3(256), 0, (hipStream_t)stream, g);
     SEG_CHECK_LAUNCH();
@@ -690,8 +699,8 @@ int mi355seg_gemm_f32(const float* A, long long a_rs, long long a_cs, long long 
                       void* ws, size_t ws_bytes, void* stream) {
     return gemm_impl(0, A, a_rs, a_cs, a_b0, a_b1, B, b_rs, b_cs, b_b0, b_b1, C, c_rs, c_b0, c_b1, bias, M, N, K, nb0, nb1, alpha, relu, accumulate, ws, ws_bytes, stream);
 }
-// fp32 tensors, products on the bf16 matrix cores (operands rounded to bf16 in registers, fp32 accumulation and result): the small-GEMM
-// kernel only; shapes outside its range run the fp32 kernels
+// fp32 tensors, bf16 products (operands rounded to bf16 in registers, fp32 accumulation and result): on the bf16 matrix cores in the small-GEMM
+// kernel; shapes outside its range run the 64x64-tile kernel on operands rounded the same way (GemmArgs::lowp)
 int mi355seg_gemm_lowp_f32(const float* A, long long a_rs, long long a_cs, long long a_b0, long long a_b1,
                            const float* B, long long b_rs, long long b_cs, long long b_b0, long long b_b1,
                            float* C, long long c_rs, long long c_b0, long long c_b1, const float* bias,

@@ -2220,6 +2220,26 @@ def dropout_pool_take(shape, p, device, fallback):
 
 
 # ----------------------------------------------------------------------------- UNETR encoder ops
+def _require_param(t, n, what):
+    """A parameter the kernels read as ``n`` consecutive floats on the activations' device: checked here, before any launch (the kernels
+    take a bare pointer, so a shorter / narrower / host tensor would be read out of bounds)."""
+    if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.float32 or t.numel() != n or not t.is_contiguous():
+        got = f"{tuple(t.shape)} {t.dtype} on {t.device}{'' if t.is_contiguous() else ', not contiguous'}" if isinstance(t, torch.Tensor) else type(t).__name__
+        raise Mi355SegError(f"{what}: expected {n} contiguous float32 values on the device, got {got}")
+
+
+def _check_heads(E, heads, what):
+    if heads <= 0 or E % heads:
+        raise Mi355SegError(f"{what}: {heads} heads do not divide the embedding width {E}")
+
+
+def _check_keep(keep, shape):
+    if keep is not None:
+        _require_cuda(keep, "attention dropout mask")
+        if tuple(keep.shape) != tuple(shape):
+            raise Mi355SegError(f"attention: dropout mask {tuple(keep.shape)} does not match the scores {tuple(shape)}")
+
+
 def _lowp_now():
     """Inside autocast(torch.bfloat16) the token path's GEMMs take bf16 products (fp32 accumulate), as the reference's nn.Linear / matmul do
     under torch.autocast; a Function records the mode at its forward and keeps it for its backward."""
@@ -2247,8 +2267,13 @@ class _Linear(Function):
         _require_cuda(x, "linear input")
         shp = x.shape
         x2 = x.contiguous().view(-1, shp[-1])
+        if w.dim() != 2 or w.shape[1] != shp[-1]:
+            raise Mi355SegError(f"linear: weight {tuple(w.shape)} does not match an input of width {shp[-1]} (expected [N, {shp[-1]}])")
         w = w.contiguous()
         M, K, N = x2.shape[0], x2.shape[1], w.shape[0]
+        _require_param(w, N * K, "linear weight")
+        if b is not None:
+            _require_param(b, N, "linear bias")
         y = torch.empty((M, N), dtype=x.dtype, device=x.device)
         if relu and residual is not None:
             raise Mi355SegError("linear: ReLU and a residual sum in one call are not supported (the backward keys the ReLU on the output)")
@@ -2359,6 +2384,8 @@ class _LayerNorm(Function):
         _require_cuda(x, "layer_norm input")
         shp = x.shape
         E = shp[-1]
+        _require_param(gamma, E, "layer_norm weight")
+        _require_param(beta, E, "layer_norm bias")
         x2 = x.contiguous().view(-1, E)
         rows = x2.shape[0]
         y = torch.empty_like(x2)
@@ -2391,6 +2418,8 @@ class _LayerNormFork(Function):
         _require_cuda(x, "layer_norm input")
         shp = x.shape
         E = shp[-1]
+        _require_param(gamma, E, "layer_norm weight")
+        _require_param(beta, E, "layer_norm bias")
         x2 = x.contiguous().view(-1, E)
         rows = x2.shape[0]
         y = torch.empty_like(x2)
@@ -2434,8 +2463,14 @@ class _Attention(Function):
     def forward(ctx, q, k, v, heads, keep):
         lowp = ctx.lowp = _lowp_now()
         _require_cuda(q, "attention input")
+        if q.dim() != 3 or k.shape != q.shape or v.shape != q.shape:
+            raise Mi355SegError(f"attention: q, k, v must be three [B, P, E] tensors of one shape, got {tuple(q.shape)}, {tuple(k.shape)}, {tuple(v.shape)}")
+        _require_cuda(k, "attention input")
+        _require_cuda(v, "attention input")
         q, k, v = q.contiguous(), k.contiguous(), v.contiguous()
         B, P, E = q.shape
+        _check_heads(E, heads, "attention")
+        _check_keep(keep, (B, heads, P, P))
         d = E // heads
         alpha = 1.0 / (d ** 0.5)
         scores = torch.empty((B, heads, P, P), dtype=q.dtype, device=q.device)
@@ -2477,9 +2512,13 @@ class _AttentionQKV(Function):
     def forward(ctx, qkv, heads, keep):
         lowp = ctx.lowp = _lowp_now()
         _require_cuda(qkv, "attention input")
+        if qkv.dim() != 3 or qkv.shape[2] % 3:
+            raise Mi355SegError(f"attention_qkv: expected the fused projection [B, P, 3E], got {tuple(qkv.shape)}")
         qkv = qkv.contiguous()
         B, P, E3 = qkv.shape
         E = E3 // 3
+        _check_heads(E, heads, "attention_qkv")
+        _check_keep(keep, (B, heads, P, P))
         d = E // heads
         alpha = 1.0 / (d ** 0.5)
         q, k, v = _p(qkv), _p(qkv) + 4 * E, _p(qkv) + 8 * E
@@ -2508,7 +2547,10 @@ class _AttentionQKV(Function):
         dpd = torch.empty_like(probs)                                   # dP = dO V^T
         L = lib()
         # r6: the two pairs of independent GEMMs (dP with dV: both read dO; dQ with dK: both read dS) as one launch each
-        pairs = lowp and not os.environ.get("MI355SEG_NO_GEMM_PAIRS") and \
+        # (the query looks at sizes only; the pair kernel also reads 16 bytes per lane along k, so every operand must start on a 16-byte boundary
+        # with pitches that keep its rows there -- a contiguous view at an odd offset into a larger buffer takes the two launches)
+        pairs = lowp and not os.environ.get("MI355SEG_NO_GEMM_PAIRS") and E % 4 == 0 and P % 4 == 0 and \
+            all(t.data_ptr() % 16 == 0 for t in (qkv, do, pd, probs)) and \
             L.query("mi355seg_gemm_pair_supported_f32", P, P, d, P, d, P, B, heads) != 0 and L.query("mi355seg_gemm_pair_supported_f32", P, d, P, P, d, P, B, heads) != 0
         if pairs:
             L.call("mi355seg_gemm_pair_lowp_f32", _p(do), E, 1, P * E, d, v, 1, E3, P * E3, d, _p(dpd), P, HPP, PP, P, P, d, 1.0,

@@ -124,7 +124,7 @@ class SelfAttention(nn.Module):
     def _seat_qkv(self):
         """Seat query / key / value .weight and .bias as consecutive slices of one buffer each: the fused [3E, E] projection then exists
         in place (no torch.cat per step) while the module keeps the reference's six parameters and state_dict keys (unetr.py:66-68).
-        load_state_dict copies into the slices; Module.to() / .cuda() re-seats them (``_apply`` below)."""
+        load_state_dict copies into the slices; Module.to() / .cuda() and copy.deepcopy / pickle re-seat them (``_apply``, ``__setstate__`` below)."""
         ws = [self.query.weight, self.key.weight, self.value.weight]
         bs = [self.query.bias, self.key.bias, self.value.bias]
         with torch.no_grad():
@@ -137,6 +137,12 @@ class SelfAttention(nn.Module):
         super()._apply(fn, *args, **kwargs)
         self._seat_qkv()
         return self
+
+    def __setstate__(self, state):
+        """copy.deepcopy and pickle rebuild every parameter in storage of its own: seat the copy's again, or it would run the
+        torch.cat path from then on without a word."""
+        super().__setstate__(state)
+        self._seat_qkv()
 
     def forward(self, hidden_states, residual=None):
         """``residual``: the block's residual stream -- the result is then residual + proj_dropout(out(attention)) (unetr.py:98-100,160),

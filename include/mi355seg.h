@@ -516,7 +516,9 @@ int mi355seg_gemm_f32(const float* A, long long a_rs, long long a_cs, long long 
 /* The same GEMM with its products on the bf16 matrix cores: fp32 operands rounded to bf16 (RNE) in registers, v_mfma_f32_32x32x16_bf16,
  * fp32 accumulation and result -- the arithmetic of the reference's nn.Linear / matmul under torch.autocast(bfloat16)
  * (/root/reference/models/three_d/unetr.py:59-138), used by the token path inside functional.autocast(torch.bfloat16).  Few-hundred-row
- * shapes (the small-GEMM kernel); other shapes run the fp32 kernels of mi355seg_gemm_f32. */
+ * shapes run the small-GEMM kernel on the bf16 matrix cores; other shapes (K % 8 != 0, an operand that is not 16-byte aligned, more than
+ * 4,096 32x32 tiles) run the 64x64-tile kernel of mi355seg_gemm_f32 on operands rounded to bf16 in the same way: the same arithmetic
+ * (a product of two bf16 values is exact in fp32), so the result does not depend on which kernel a shape or an address selects. */
 int mi355seg_gemm_lowp_f32(const float* A, long long a_rs, long long a_cs, long long a_b0, long long a_b1,
                       const float* B, long long b_rs, long long b_cs, long long b_b0, long long b_b1,
                       float* C, long long c_rs, long long c_b0, long long c_b1, const float* bias,
