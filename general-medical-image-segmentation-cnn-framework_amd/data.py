@@ -2,7 +2,8 @@
 (dataloader.py:52-67) as batch dicts ``{"source": {"data": x}, "gt": {"data": y}}``; torchio/NIfTI I/O is out
 of scope, so this module yields the same dict shape from (a) a device-resident synthetic generator or (b) a
 device-resident patch queue over a directory of ``.npy`` volumes (Queue / UniformSampler / ZNormalization semantics of
-dataloader.py:52-67,94)."""
+dataloader.py:52-67,94).  With ``config.aug`` both apply the reference's training augmentation (dataloader.py:69-86) on the
+device: parameters drawn on the host per subject visit (``AugmentParams``), one resampling launch per batch."""
 import glob
 import os
 
@@ -10,13 +11,90 @@ import numpy as np
 import torch
 
 
+def _require_device(device, what):
+    if torch.device(device).type != "cuda":
+        from ._lib import Mi355SegError
+        raise Mi355SegError(f"{what}: aug=True resamples with the HIP kernels of csrc/augment.hip and needs an MI355X (cuda/HIP) "
+                            f"device, got {device}; there is no CPU fallback in this package")
+
+
+class AugmentParams:
+    """UNPINNED restatement of the random parameters of the reference's training transform (dataloader.py:69-86 with
+    ``config.aug=True``: ``Compose([RandomBiasField(), ZNormalization(), RandomNoise(), RandomFlip(axes=(0,)), OneOf({RandomAffine(): 0.8,
+    RandomElasticDeformation(): 0.2})])``), with torchio's defaults for the five transforms constructed without arguments (torchio is
+    absent from the build image and the reference holds no fixture of its data pipeline; tests/test_augment.py checks the properties
+    stated here).  One instance belongs to one subject VISIT and is shared by that visit's patches, as torchio transforms the subject
+    and then cuts patches.  Spatial axes are (D, H, W) = axes 0, 1, 2 of the volume, n = shape, c = (n - 1) / 2.
+
+    ``bias``   float32[20]: polynomial coefficients ~ U(-0.5, 0.5) of the order-3 bias field, torchio's loop order
+    ``sigma``  noise std ~ U(0, 0.25);  ``seed``: key of the counter-based noise generator, an integer in [0, 2^63)
+    ``flip``   axis 0 mirrored (probability 0.5);  ``elastic``: OneOf picked the elastic deformation (probability 0.2)
+    ``scales`` / ``degrees``  per-axis scale ~ U(0.9, 1.1) and Euler angle ~ U(-10, 10) degrees of an affine visit (else ones / zeros)
+    ``cp``     float32 [3,7,7,7] control-point displacements ~ U(-7.5, 7.5) voxels of an elastic visit, the two outermost layers of
+               every face zero (locked_borders=2); ``None`` for an affine visit
+    ``matrix`` float32 [3,4], output voxel -> source voxel: ``F . (c + diag(1/s) R^T (p - c))`` with ``R = Rz Ry Rx`` (rotations about
+               axes 2, 1, 0), no translation, ``F`` the flip ``q0 -> D - 1 - q0`` or the identity; for an elastic visit just ``F``, and the
+               B-spline displacement of ``cp`` at p is added to the mapped point.
+    The draw order is bias, sigma, seed, flip, OneOf, then the chosen transform's own parameters."""
+
+    def __init__(self, shape, bias, sigma, seed, flip, elastic, scales=(1.0, 1.0, 1.0), degrees=(0.0, 0.0, 0.0), cp=None):
+        self.shape = tuple(int(s) for s in shape)
+        self.bias = np.ascontiguousarray(bias, dtype=np.float32)
+        self.sigma, self.seed, self.flip, self.elastic = float(sigma), int(seed), bool(flip), bool(elastic)
+        self.scales = np.asarray(scales, dtype=np.float64)
+        self.degrees = np.asarray(degrees, dtype=np.float64)
+        self.cp = None if cp is None else np.ascontiguousarray(cp, dtype=np.float32)
+        if len(self.shape) != 3 or self.bias.shape != (20,) or (self.elastic and (self.cp is None or self.cp.shape != (3, 7, 7, 7))):
+            raise ValueError("AugmentParams: expected a 3D shape, 20 bias coefficients and, for an elastic visit, cp [3,7,7,7]")
+        self.matrix = self._matrix()
+
+    @classmethod
+    def identity(cls, shape, flip=False):
+        """No intensity change beyond the z-normalisation and no resampling beyond the optional flip (tests, debugging)."""
+        return cls(shape, np.zeros(20, np.float32), 0.0, 0, flip, False)
+
+    @classmethod
+    def draw(cls, rng, shape):
+        """One visit's parameters from ``rng`` (a ``np.random.Generator``); needs no GPU."""
+        bias = rng.uniform(-0.5, 0.5, 20)
+        sigma = rng.uniform(0.0, 0.25)
+        seed = int(rng.integers(0, 1 << 63))
+        flip = bool(rng.random() < 0.5)
+        if rng.random() < 0.8:
+            return cls(shape, bias, sigma, seed, flip, False, scales=rng.uniform(0.9, 1.1, 3), degrees=rng.uniform(-10.0, 10.0, 3))
+        cp = rng.uniform(-7.5, 7.5, (3, 7, 7, 7))
+        locked = np.ones((7, 7, 7), dtype=bool)
+        locked[2:5, 2:5, 2:5] = False
+        cp[:, locked] = 0.0
+        return cls(shape, bias, sigma, seed, flip, True, cp=cp)
+
+    def _matrix(self):
+        n = np.asarray(self.shape, dtype=np.float64)
+        c = (n - 1.0) / 2.0
+        a0, a1, a2 = np.deg2rad(self.degrees)
+        r0 = np.array([[1, 0, 0], [0, np.cos(a0), -np.sin(a0)], [0, np.sin(a0), np.cos(a0)]])
+        r1 = np.array([[np.cos(a1), 0, np.sin(a1)], [0, 1, 0], [-np.sin(a1), 0, np.cos(a1)]])
+        r2 = np.array([[np.cos(a2), -np.sin(a2), 0], [np.sin(a2), np.cos(a2), 0], [0, 0, 1]])
+        a = np.diag(1.0 / self.scales) @ (r2 @ r1 @ r0).T
+        m = np.concatenate([a, (c - a @ c)[:, None]], axis=1)
+        if self.flip:
+            m[0] = -m[0]
+            m[0, 3] += n[0] - 1.0
+        return np.ascontiguousarray(m, dtype=np.float32)
+
+
 class SyntheticPatches:
     """x ~ N(0,1) (mimics ZNormalization), labels from a thresholded low-frequency field; generated on the
-    device so no host->device copy sits in the step."""
+    device so no host->device copy sits in the step.  ``aug=True``: every generated sample is a one-patch subject (volume = patch,
+    origin 0) put through the training augmentation of ``AugmentParams`` (dataloader.py:69-86), one sampling launch per batch."""
 
-    def __init__(self, patch_size, in_channels, batch_size, iters, device, seed=1234, n_labels=2):
+    def __init__(self, patch_size, in_channels, batch_size, iters, device, seed=1234, n_labels=2, aug=False):
         self.ps = (patch_size,) * 3 if isinstance(patch_size, int) else tuple(patch_size)
         self.cin, self.bs, self.iters, self.device = in_channels, batch_size, iters, device
+        self.aug = bool(aug)
+        if self.aug:
+            _require_device(device, "SyntheticPatches")
+            self.rng = np.random.default_rng(seed)
         self.gen = torch.Generator(device=device).manual_seed(seed)
         self.n_labels = n_labels
 
@@ -29,7 +107,18 @@ class SyntheticPatches:
             coarse = torch.rand((self.bs, 1) + tuple(max(2, p // 8) for p in self.ps), generator=self.gen, device=self.device)
             field = torch.nn.functional.interpolate(coarse, size=self.ps, mode="trilinear", align_corners=False)
             gt = (field > 0.6).to(torch.float32)
+            if self.aug:
+                x, gt = self._augment(x, gt)
             yield {"source": {"data": x}, "gt": {"data": gt}}
+
+    def _augment(self, x, gt):
+        from . import functional as F
+        patches = []
+        for xi, yi in zip(x, gt):
+            prm = AugmentParams.draw(self.rng, self.ps)
+            cp = torch.from_numpy(prm.cp).to(self.device) if prm.elastic else None
+            patches.append((xi, yi, F.augment_stats(xi, prm), cp, (0, 0, 0), prm))
+        return F.augment_sample(patches, self.ps)
 
 
 class DevicePatchQueue:
@@ -42,10 +131,20 @@ class DevicePatchQueue:
     and cached in HBM up to ``cache_gb`` -- 288 GB per MI355X holds whole cohorts -- so a step costs no host I/O and
     no host->device copy.  Queue semantics as torchio's: subjects are visited in a shuffled order, each contributes
     ``samples_per_volume`` uniformly placed patches, the queue is refilled to ``queue_length`` patches and shuffled
-    whenever it runs dry, and a batch pops ``batch_size`` patches."""
+    whenever it runs dry, and a batch pops ``batch_size`` patches.
+
+    ``aug=True`` (dataloader.py:69-86, ``config.aug``; UNPINNED like the rest, see ``AugmentParams``): the RAW volumes are cached, every
+    subject visit draws one ``AugmentParams`` from the queue's generator (after which its ``samples_per_volume`` origins are drawn as
+    before) and has its statistics computed on the device (``functional.augment_stats``), the queue holds patch descriptors instead
+    of views, and a batch is one small table upload and one resampling launch (``functional.augment_sample``); ``last_patches`` keeps
+    the descriptors of the batch yielded last.  With ``aug=False`` nothing changes."""
 
     def __init__(self, data_path, gt_path, patch_size, batch_size, iters, device, seed=1234, queue_length=10,
-                 samples_per_volume=10, cache_gb=200.0):
+                 samples_per_volume=10, cache_gb=200.0, aug=False):
+        self.aug = bool(aug)
+        if self.aug:
+            _require_device(device, "DevicePatchQueue")
+        self.last_patches = None
         self.files = sorted(glob.glob(os.path.join(data_path, "*.npy")))
         if not self.files:
             raise FileNotFoundError(f"no .npy volumes under {data_path}")
@@ -60,7 +159,8 @@ class DevicePatchQueue:
         return self.iters
 
     def _subject(self, idx):
-        """(x, y) of subject ``idx`` on the device, x already z-normalised; cached while the budget lasts."""
+        """(x, y) of subject ``idx`` on the device, x already z-normalised (the raw volume with ``aug=True``: the normalisation is
+        then part of the resampling); cached while the budget lasts."""
         hit = self.cache.get(idx)
         if hit is not None:
             return hit
@@ -71,7 +171,9 @@ class DevicePatchQueue:
         y = y[None] if y.dim() == 3 else y
         if any(s < p for s, p in zip(x.shape[1:], self.ps)):
             raise ValueError(f"{f}: volume {tuple(x.shape[1:])} is smaller than the patch {self.ps}")
-        if x.is_cuda:                                     # one fused statistics pass + one apply pass (HIP)
+        if self.aug:                                      # raw: bias field, z-normalisation and noise ride in the sampling kernel
+            x, y = x.contiguous(), y.contiguous()
+        elif x.is_cuda:                                   # one fused statistics pass + one apply pass (HIP)
             from . import functional as F
             x = F.znormalize(x)
         else:                                             # CPU plumbing tests only
@@ -87,6 +189,15 @@ class DevicePatchQueue:
             if not self._order:
                 self._order = list(self.rng.permutation(len(self.files)))
             x, y = self._subject(int(self._order.pop()))
+            if self.aug:
+                from . import functional as F
+                prm = AugmentParams.draw(self.rng, x.shape[1:])
+                stats = F.augment_stats(x, prm)
+                cp = torch.from_numpy(prm.cp).to(self.device) if prm.elastic else None
+                for _ in range(self.spv):
+                    o = tuple(int(self.rng.integers(0, s - p + 1)) for s, p in zip(x.shape[1:], self.ps))
+                    self._queue.append((x, y, stats, cp, o, prm))
+                continue
             for _ in range(self.spv):
                 o = [int(self.rng.integers(0, s - p + 1)) for s, p in zip(x.shape[1:], self.ps)]
                 sl = (slice(None),) + tuple(slice(a, a + p) for a, p in zip(o, self.ps))
@@ -94,7 +205,22 @@ class DevicePatchQueue:
         perm = self.rng.permutation(len(self._queue))
         self._queue = [self._queue[i] for i in perm]
 
+    def _iter_augmented(self):
+        from . import functional as F
+        for _ in range(self.iters):
+            patches = []
+            for _b in range(self.bs):
+                if not self._queue:
+                    self._refill()
+                patches.append(self._queue.pop())
+            self.last_patches = patches
+            xb, yb = F.augment_sample(patches, self.ps)
+            yield {"source": {"data": xb}, "gt": {"data": yb}}
+
     def __iter__(self):
+        if self.aug:
+            yield from self._iter_augmented()
+            return
         for _ in range(self.iters):
             xs, ys = [], []
             for _b in range(self.bs):
@@ -111,8 +237,9 @@ NpyPatches = DevicePatchQueue
 
 def make_loader(config, device, in_channels, seed=1234):
     iters = int(getattr(config, "iters_per_epoch", 4))
+    aug = bool(getattr(config, "aug", False))             # conf/config.yaml:27; dataloader.py:69
     if str(config.data_path) == "synthetic":
-        return SyntheticPatches(config.patch_size, in_channels, config.batch_size, iters, device, seed)
+        return SyntheticPatches(config.patch_size, in_channels, config.batch_size, iters, device, seed, aug=aug)
     return DevicePatchQueue(config.data_path, config.gt_path, config.patch_size, config.batch_size, iters, device, seed,
                             queue_length=int(getattr(config, "queue_length", 10)),
-                            samples_per_volume=int(getattr(config, "samples_per_volume", 10)))
+                            samples_per_volume=int(getattr(config, "samples_per_volume", 10)), aug=aug)

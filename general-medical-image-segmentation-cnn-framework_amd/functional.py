@@ -11,6 +11,7 @@ Activations inside the package are channel-last: a 5-D fp32 tensor of logical sh
 import os
 import threading
 
+import numpy as np
 import torch
 from torch.autograd import Function
 
@@ -1737,6 +1738,81 @@ def znormalize(x):
     y = torch.empty_like(x)
     L.call("mi355seg_znorm_f32", _p(x), x.numel(), _p(y), _p(ws), ws.numel(), _stream())
     return y
+
+
+AUG_DESC_WORDS = 64             # MI355SEG_AUG_DESC_WORDS: int32 words of one patch descriptor (layout in include/mi355seg.h)
+
+
+def augment_stats(x, params):
+    """The intensity statistics of one subject visit (dataloader.py:71-73: RandomBiasField -> ZNormalization -> RandomNoise) of the
+    raw volume ``x`` [C,D,H,W]: float32[4] = (mu, rho, min V, sigma) on the device, in three launches and without a host round
+    trip (``augment_sample`` reads them through the descriptor).  ``params``: the visit's ``data.AugmentParams`` (``bias`` float32[20],
+    ``sigma``, ``seed``).  UNPINNED, as the rest of the data path: the definitions in include/mi355seg.h are the specification."""
+    _require_cuda(x, "augment_stats volume")
+    if x.dim() != 4 or min(x.shape[1:]) < 2 or x[0].numel() >= 1 << 31:
+        raise Mi355SegError(f"augment_stats: expected a volume [C,D,H,W] with every spatial dim >= 2 and D*H*W < 2^31, got {tuple(x.shape)}")
+    if not x.is_contiguous():
+        raise Mi355SegError("augment_stats: the volume must be contiguous (the patch descriptors address it as it is)")
+    bias = np.ascontiguousarray(params.bias, dtype=np.float32)
+    if bias.shape != (20,):
+        raise Mi355SegError(f"augment_stats: expected 20 bias-field coefficients, got {bias.shape}")
+    L = lib()
+    ws = workspace(L.query("mi355seg_augment_ws_bytes", x.numel()), x.device)
+    stats = torch.empty(4, dtype=torch.float32, device=x.device)
+    C, D, H, W = x.shape
+    L.call("mi355seg_augment_stats_f32", _p(x), C, D, H, W, bias.ctypes.data, float(params.sigma), int(params.seed), _p(stats), _p(ws),
+           ws.numel(), _stream())
+    return stats
+
+
+def augment_sample(patches, patch_size):
+    """One augmented batch (dataloader.py:69-86 with config.aug=True, then the queue's patch cut) in ONE launch:
+    ``patches`` is a sequence of ``(x [C,D,H,W], y [Cy,D,H,W], stats, cp, origin, params)`` -- the raw device volume and its labels,
+    ``augment_stats(x, params)``, the visit's control points as a device float32 [3,7,7,7] (``None`` for an affine visit), the patch
+    origin (z, y, x) in the augmented volume and the visit's ``data.AugmentParams`` (``matrix`` float32 [3,4] output -> source,
+    ``elastic``, ``bias``, ``sigma``, ``seed``).  Returns ``(xb [B,C,pd,ph,pw], yb [B,Cy,pd,ph,pw])``.  One small table upload, no
+    synchronisation.  UNPINNED (see ``augment_stats``)."""
+    ps = tuple(int(p) for p in ((patch_size,) * 3 if isinstance(patch_size, int) else patch_size))
+    if not patches:
+        raise Mi355SegError("augment_sample: no patches")
+    x0, y0 = patches[0][0], patches[0][1]
+    _require_cuda(x0, "augment_sample volume")
+    C, Cy, dev = x0.shape[0], y0.shape[0], x0.device
+    tab = np.zeros((len(patches), AUG_DESC_WORDS), dtype=np.int32)
+    t64, tf = tab.view(np.int64), tab.view(np.float32)
+    for i, (x, y, stats, cp, origin, prm) in enumerate(patches):
+        _require_cuda(x, "augment_sample volume")
+        _require_cuda(y, "augment_sample labels")
+        _require_cuda(stats, "augment_sample stats")
+        if x.dim() != 4 or y.dim() != 4 or x.shape[0] != C or y.shape[0] != Cy or x.shape[1:] != y.shape[1:] or x.device != dev \
+                or y.device != dev or stats.device != dev or not (x.is_contiguous() and y.is_contiguous()) or stats.numel() != 4:
+            raise Mi355SegError(f"augment_sample: patch {i}: expected contiguous x [{C},D,H,W] / y [{Cy},D,H,W] of one spatial shape on "
+                                f"{dev} and float32[4] stats, got {tuple(x.shape)} / {tuple(y.shape)}")
+        if min(x.shape[1:]) < 2 or x[0].numel() >= 1 << 31:
+            raise Mi355SegError(f"augment_sample: patch {i}: every spatial dim must be >= 2 and D*H*W < 2^31, got {tuple(x.shape)}")
+        if len(origin) != 3 or any(int(o) < 0 or int(o) + p > 1 << 24 for o, p in zip(origin, ps)):
+            raise Mi355SegError(f"augment_sample: patch {i}: origin {tuple(origin)} must be non-negative (and below 2^24)")
+        m = np.ascontiguousarray(prm.matrix, dtype=np.float32)
+        bias = np.ascontiguousarray(prm.bias, dtype=np.float32)
+        if m.shape != (3, 4) or bias.shape != (20,) or not np.isfinite(m).all():
+            raise Mi355SegError(f"augment_sample: patch {i}: expected a finite 3x4 matrix and 20 bias coefficients")
+        t64[i, 0], t64[i, 1], t64[i, 2] = x.data_ptr(), y.data_ptr(), stats.data_ptr()
+        if prm.elastic:
+            if cp is None or not cp.is_cuda or cp.device != dev or cp.dtype != torch.float32 or cp.numel() != 3 * 343 or not cp.is_contiguous():
+                raise Mi355SegError(f"augment_sample: patch {i}: an elastic visit needs its control points as a device float32 [3,7,7,7]")
+            t64[i, 3] = cp.data_ptr()
+        tab[i, 8:11] = x.shape[1:]
+        tab[i, 11:14] = [int(o) for o in origin]
+        tab[i, 14] = 1 if prm.elastic else 0
+        tf[i, 16:28] = m.reshape(-1)
+        tf[i, 28:48] = bias
+        tf[i, 48] = float(prm.sigma)
+        t64[i, 25] = int(prm.seed)
+    table = torch.from_numpy(tab).to(dev)
+    xb = torch.empty((len(patches), C) + ps, dtype=torch.float32, device=dev)
+    yb = torch.empty((len(patches), Cy) + ps, dtype=torch.float32, device=dev)
+    lib().call("mi355seg_augment_sample_f32", _p(table), len(patches), C, Cy, ps[0], ps[1], ps[2], _p(xb), _p(yb), _stream())
+    return xb, yb
 
 
 def dice_sums(x, t, apply_sigmoid=False):

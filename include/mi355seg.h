@@ -611,6 +611,35 @@ int mi355seg_gather_patches_f32(const float* vol, int C, int D, int H, int W, co
 int mi355seg_paste_labels_i64(const int64_t* labels, const int* table, int first, int count, int pd, int ph, int pw,
                               int64_t* out, int D, int H, int W, void* stream);
 
+/* ------------------------------------------------------------------ Training augmentation of the patch queue (dataloader.py:69-86)
+ * config.aug=True: Compose([RandomBiasField(), ZNormalization(), RandomNoise(), RandomFlip(axes=(0,)), OneOf({RandomAffine(): 0.8,
+ * RandomElasticDeformation(): 0.2})]) as ONE resampling gather per batch over the cached raw volumes x [C,D,H,W] / labels [Cy,D,H,W].
+ * UNPINNED (torchio is absent and the reference holds no fixture of its data pipeline): the definitions here are the specification.
+ *   b(q)    = exp(sum c_ijk a0^i a1^j a2^k), i,j,k >= 0, i+j+k <= 3 (20 coefficients, i outermost, k innermost), a_d = (2 q_d + 1 - n_d) / (n_d - 1)
+ *   mu, rho = mean and 1 / (unbiased std) of x * b over every voxel of every channel (fp64 sums)
+ *   g(seed, e): standard normal, Philox-4x32-10 (counter = e, the linear element index in [C,D,H,W]; key = seed) + Box-Muller
+ *   V(e)    = (x(e) * b(q) - mu) * rho + sigma * g(seed, e), each of the four fp32 operations rounded once; never materialised
+ * mi355seg_augment_stats_f32 (dataloader.py:71-73, the intensity transforms of one subject visit): three launches -- fixed-order fp64
+ * partial sums, min V per block, finalise -- write stats[0..3] = (mu, rho, min V, sigma) on the DEVICE; bitwise reproducible (no atomics).
+ * bias_host: the 20 coefficients in HOST memory (read during the call).  Spatial dims >= 2, D*H*W < 2^31.
+ * mi355seg_augment_sample_f32 (dataloader.py:74-84, flip + affine / elastic, then the queue's patch cut): one launch writes the batch
+ * out_x [count,C,pd,ph,pw] and out_y [count,Cy,pd,ph,pw] from a device table of int32 [count][MI355SEG_AUG_DESC_WORDS], one descriptor per
+ * patch (patches of a batch may come from different subjects; pointers as lo, hi words; floats as their bit patterns):
+ *   0-1 x   2-3 labels   4-5 stats (the four floats above)   6-7 control points float [3][7][7][7] (mode 1, else unused)
+ *   8-10 D, H, W   11-13 patch origin z, y, x   14 mode (0 affine, 1 elastic)   16-27 M, the 3x4 output -> source map (row-major)
+ *   28-47 the 20 bias coefficients   48 sigma   50-51 seed lo, hi   (15, 49, 52-63 reserved)
+ * For the output voxel p = origin + offset: t = M [p; 1] (+ the uniform cubic B-spline displacement of the control grid in mode 1:
+ * u_d = 4 p_d / (n_d - 1), i_d = min(floor(u_d), 3), f_d = u_d - i_d, sum B_a(f_0) B_b(f_1) B_c(f_2) cp[:, i_0+a, i_1+b, i_2+c]);
+ * inside when -0.5 <= t_d < n_d - 0.5 on every axis.  Image: trilinear interpolation of V over the 8 corners (indices clamped to the
+ * volume) inside, stats[2] (torchio's default_pad_value='minimum') outside; label: the source label at floor(t + 0.5) inside, 0 outside.
+ * Neither entry point allocates or synchronises; the caller guarantees that every descriptor tells the truth about its volume. */
+#define MI355SEG_AUG_DESC_WORDS 64
+size_t mi355seg_augment_ws_bytes(long long n);
+int mi355seg_augment_stats_f32(const float* x, int C, int D, int H, int W, const float* bias_host, float sigma, long long seed,
+                               float* stats, void* ws, size_t ws_bytes, void* stream);
+int mi355seg_augment_sample_f32(const int* table, int count, int C, int Cy, int pd, int ph, int pw, float* out_x, float* out_y,
+                                void* stream);
+
 /* ------------------------------------------------------------------ Layout helpers */
 int mi355seg_ncdhw_to_ndhwc_f32(const float* src, float* dst, int lddst, long long N, int C, long long S, void* stream);
 int mi355seg_ndhwc_to_ncdhw_f32(const float* src, int ldsrc, float* dst, long long N, int C, long long S, void* stream);
