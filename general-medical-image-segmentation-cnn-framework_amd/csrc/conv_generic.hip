@@ -442,6 +442,9 @@ int x3_shape() { return g_x3_shape; }
 // (f16x3 shares the plans, tiles and launch paths of the bf16x6 policy; the kernels that have a two-piece form ask x3_f16())
 int f32_conv_policy() { return g_conv_math == MI355SEG_MATH_FP32 ? MATH_F32 : MATH_X3; }
 bool x3_f16() { return g_conv_math == MI355SEG_MATH_F16X3 && g_x3_shape == 16; }
+// the branch the last fp32 convolution dispatcher took (MI355SEG_PATH_*, mi355seg_last_conv_path): one host-side store per call
+static int g_conv_path = MI355SEG_PATH_NONE;
+void note_conv_path(int code) { g_conv_path = code; }
 }
 
 // ---- patch embedding (kernel = stride, no padding; UNETR's k16 s16 conv, unetr.py:141-156) as a plain GEMM:
@@ -501,6 +504,7 @@ int mi355seg_set_x3_shape(int shape) {
     return MI355SEG_OK;
 }
 int mi355seg_get_x3_shape(void) { return g_x3_shape; }
+int mi355seg_last_conv_path(void) { return g_conv_path; }
 
 size_t mi355seg_conv3d_ws_bytes(int N, int D, int H, int W, int Cin, int Cout, int k, int stride, int pad) {
     size_t a = conv_generic_ws_bytes(N, D, H, W, Cin, Cout, k, stride, pad);
@@ -586,15 +590,18 @@ static int conv3d_fwd_impl(const float* x, int ldx, const float* w, const float*
     SEG_CHECK_ARG((stats_sum == nullptr) == (stats_sq == nullptr), "conv3d_fwd: stats_sum/stats_sq must come together");
     hipStream_t st = (hipStream_t)stream;
     const int pol = f32_conv_policy();
+    // (the matrix-core branches are recorded inside conv_fwd_mfma: MI355SEG_PATH_FWD_MFMA_X3S / _X3 / _F32)
     if (pol != MATH_F32 && conv_mfma_supported(pol, N, D, H, W, Cin, Cout, k, stride, pad, ldx, ldy)) {
         if (y_amax) *amax_done = true;
         return conv_fwd_mfma(pol, x, ldx, w, bias, y, ldy, N, D, H, W, Cin, Cout, k, /*dgrad=*/0, stats_sum, stats_sq, ws, ws_bytes, st,
                              nullptr, 0, 0.f, nullptr, x_amax, w_amax, nullptr, 0, nullptr, nullptr, y_amax);
     }
-    if (conv_mfma_supported(MATH_F32, N, D, H, W, Cin, Cout, k, stride, pad, ldx, ldy))
+    if (conv_mfma_supported(MATH_F32, N, D, H, W, Cin, Cout, k, stride, pad, ldx, ldy)) {
         return conv_fwd_mfma(MATH_F32, x, ldx, w, bias, y, ldy, N, D, H, W, Cin, Cout, k, /*dgrad=*/0, stats_sum, stats_sq, ws, ws_bytes, st);
+    }
     if (patch_embed_supported(D, H, W, Cin, k, stride, pad)) {
         float* A; void* rest; size_t rest_bytes;
+        note_conv_path(MI355SEG_PATH_FWD_PATCH_EMBED);
         rc = patch_embed_matrix(x, ldx, N, D, H, W, Cin, k, ws, ws_bytes, &A, &rest, &rest_bytes, st);
         if (rc) return rc;
         const int M = N * (D / k) * (H / k) * (W / k), K = Cin * k * k * k;
@@ -602,30 +609,37 @@ static int conv3d_fwd_impl(const float* x, int ldx, const float* w, const float*
         if (rc || !stats_sum) return rc;
         return channel_sums(y, ldy, M, Cout, stats_sum, stats_sq, nullptr, 0, ws, ws_bytes, st);
     }
-    if (conv_gather_fwd_supported(MATH_F32, N, D, H, W, Cin, Cout, k, stride, pad, ldx, ldy) && ((uintptr_t)x % 16) == 0)
+    if (conv_gather_fwd_supported(MATH_F32, N, D, H, W, Cin, Cout, k, stride, pad, ldx, ldy) && ((uintptr_t)x % 16) == 0) {
+        note_conv_path(MI355SEG_PATH_FWD_GATHER);
         return conv_gather_fwd_mfma(MATH_F32, x, ldx, w, bias, y, ldy, N, D, H, W, Cin, Cout, k, stride, pad, stats_sum, stats_sq, ws, ws_bytes, st);
+    }
     if (headk_supported(Cin, Cout, k, stride, pad, ldx, ldy, false) && ((uintptr_t)x % 16) == 0 && ((uintptr_t)y % 8) == 0) {
+        note_conv_path(MI355SEG_PATH_FWD_HEADK);
         rc = headk_conv(false, x, ldx, w, bias, y, ldy, N, D, H, W, Cin, k, ws, ws_bytes, st);
         if (rc || !stats_sum) return rc;
         return channel_sums(y, ldy, (long long)N * D * H * W, Cout, stats_sum, stats_sq, nullptr, 0, ws, ws_bytes, st);
     }
     if (stemk_supported(Cin, Cout, k, stride, pad, ldx, ldy) && ((uintptr_t)x % 8) == 0 && ((uintptr_t)y % 16) == 0) {
+        note_conv_path(MI355SEG_PATH_FWD_STEMK);
         rc = stemk_fwd(x, ldx, w, bias, y, ldy, N, D, H, W, Cin, Cout, ws, ws_bytes, st);
         if (rc || !stats_sum) return rc;
         return channel_sums(y, ldy, (long long)N * D * H * W, Cout, stats_sum, stats_sq, nullptr, 0, ws, ws_bytes, st);
     }
-    if (stem_supported(Cin, Cout, k, stride, pad, ldy))
+    if (stem_supported(Cin, Cout, k, stride, pad, ldy))          // (stem_fwd records which of its kernels: MI355SEG_PATH_FWD_STEM_*)
         return stem_fwd(x, ldx, w, bias, y, ldy, N, D, H, W, Cin, Cout, stats_sum, stats_sq, ws, ws_bytes, st, y_amax, amax_done);
     if (tinypw_supported(Cin, Cout, k, stride, pad)) {
+        note_conv_path(MI355SEG_PATH_FWD_TINYPW);
         rc = tinypw_fwd(x, ldx, w, bias, y, ldy, (long long)N * D * H * W, Cin, Cout, st);
         if (rc || !stats_sum) return rc;
         return channel_sums(y, ldy, (long long)N * D * H * W, Cout, stats_sum, stats_sq, nullptr, 0, ws, ws_bytes, st);
     }
     if (head_supported(Cin, Cout, k, stride, pad, ldx)) {
+        note_conv_path(MI355SEG_PATH_FWD_HEAD);
         rc = head_fwd(x, ldx, w, bias, y, ldy, N, D, H, W, Cin, Cout, st);
         if (rc || !stats_sum) return rc;
         return channel_sums(y, ldy, (long long)N * D * H * W, Cout, stats_sum, stats_sq, nullptr, 0, ws, ws_bytes, st);
     }
+    note_conv_path(MI355SEG_PATH_FWD_GENERIC);
     return conv_fwd_generic(x, ldx, w, bias, y, ldy, g, stats_sum, stats_sq, ws, ws_bytes, st);
 }
 
@@ -734,24 +748,38 @@ int mi355seg_conv3d_dgrad_ax_f32(const float* dy, int lddy, const float* w, floa
     hipStream_t st = (hipStream_t)stream;
     // k3 s1 p1: dgrad is the same convolution with flipped taps and Cin<->Cout swapped
     const int pol = f32_conv_policy();
-    if (pol != MATH_F32 && conv_mfma_supported(pol, N, D, H, W, Cout, Cin, k, stride, pad, lddy, lddx))
+    if (pol != MATH_F32 && conv_mfma_supported(pol, N, D, H, W, Cout, Cin, k, stride, pad, lddy, lddx)) {
         return conv_fwd_mfma(pol, dy, lddy, w, nullptr, dx, lddx, N, D, H, W, Cout, Cin, k, /*dgrad=*/1, nullptr, nullptr, ws, ws_bytes, st,
                              nullptr, 0, 0.f, nullptr, dy_amax, w_amax);
-    if (conv_mfma_supported(MATH_F32, N, D, H, W, Cout, Cin, k, stride, pad, lddy, lddx))
+    }
+    if (conv_mfma_supported(MATH_F32, N, D, H, W, Cout, Cin, k, stride, pad, lddy, lddx)) {
         return conv_fwd_mfma(MATH_F32, dy, lddy, w, nullptr, dx, lddx, N, D, H, W, Cout, Cin, k, /*dgrad=*/1, nullptr, nullptr, ws, ws_bytes, st);
-    if (conv_gather_dgrad_supported(MATH_F32, N, D, H, W, Cin, Cout, k, stride, pad, lddy, lddx) && ((uintptr_t)dy % 16) == 0)
+    }
+    if (conv_gather_dgrad_supported(MATH_F32, N, D, H, W, Cin, Cout, k, stride, pad, lddy, lddx) && ((uintptr_t)dy % 16) == 0) {
+        note_conv_path(MI355SEG_PATH_DGRAD_GATHER);
         return conv_gather_dgrad_mfma(MATH_F32, dy, lddy, w, dx, lddx, N, D, H, W, Cin, Cout, k, stride, pad, ws, ws_bytes, st);
-    if (headk_supported(Cin, Cout, k, stride, pad, lddy, lddx, true) && ((uintptr_t)dy % 8) == 0 && ((uintptr_t)dx % 16) == 0)
+    }
+    if (headk_supported(Cin, Cout, k, stride, pad, lddy, lddx, true) && ((uintptr_t)dy % 8) == 0 && ((uintptr_t)dx % 16) == 0) {
+        note_conv_path(MI355SEG_PATH_DGRAD_HEADK);
         return headk_conv(true, dy, lddy, w, nullptr, dx, lddx, N, D, H, W, Cin, k, ws, ws_bytes, st);
-    if (head_supported(Cin, Cout, k, stride, pad, lddx))
+    }
+    if (head_supported(Cin, Cout, k, stride, pad, lddx)) {
+        note_conv_path(MI355SEG_PATH_DGRAD_HEAD);
         return head_dgrad(dy, lddy, w, dx, lddx, N, D, H, W, Cin, Cout, st);
-    if (tinypw_supported(Cin, Cout, k, stride, pad)) return tinypw_dgrad(dy, lddy, w, dx, lddx, (long long)N * D * H * W, Cin, Cout, st);
+    }
+    if (tinypw_supported(Cin, Cout, k, stride, pad)) {
+        note_conv_path(MI355SEG_PATH_DGRAD_TINYPW);
+        return tinypw_dgrad(dy, lddy, w, dx, lddx, (long long)N * D * H * W, Cin, Cout, st);
+    }
     // k2 s2 p0 (V-Net's down-convolutions, vnet3d.py:66): the windows do not overlap, so the input gradient IS the forward of
     // ConvTranspose3d k2 s2 with the same weight tensor read as (Cin_T = Cout, Cout_T = Cin, 2, 2, 2) -- also for Cin = 16,
     // which the 32-column tiles of the gather dgrad cannot cut (the transposed conv tiles the flat (child, channel) axis)
     if (k == 2 && stride == 2 && pad == 0 && D % 2 == 0 && H % 2 == 0 && W % 2 == 0 && ((uintptr_t)dy % 16) == 0 &&
-        convt_mfma_supported(MATH_F32, N, D / 2, H / 2, W / 2, Cout, Cin, lddy, lddx))
+        convt_mfma_supported(MATH_F32, N, D / 2, H / 2, W / 2, Cout, Cin, lddy, lddx)) {
+        note_conv_path(MI355SEG_PATH_DGRAD_K2S2_CONVT);
         return convt_fwd_mfma(MATH_F32, dy, lddy, w, nullptr, dx, lddx, N, D / 2, H / 2, W / 2, Cout, Cin, ws, ws_bytes, st);
+    }
+    note_conv_path(MI355SEG_PATH_DGRAD_GENERIC);
     return conv_dgrad_generic(dy, lddy, w, dx, lddx, g, ws, ws_bytes, st);
 }
 
@@ -786,7 +814,7 @@ int mi355seg_conv3d_dgrad_bnsums_ax_f32(const float* dy, int lddy, const float* 
         rc = conv_fwd_mfma(pol, dy, lddy, w, nullptr, dx, lddx, N, D, H, W, Cout, Cin, k, /*dgrad=*/1, nullptr, nullptr, ws, ws_bytes, st, nullptr, 0, 0.f, &e,
                            dy_amax, w_amax);
         if (rc || e.done) return rc;
-    } else {
+    } else {                 // (the plain dispatcher: it records its own branch)
         rc = mi355seg_conv3d_dgrad_ax_f32(dy, lddy, w, dx, lddx, N, D, H, W, Cin, Cout, k, stride, pad, dy_amax, w_amax, ws, ws_bytes, stream);
         if (rc) return rc;
     }
@@ -815,6 +843,7 @@ int mi355seg_conv3d_wgrad_ax_f32(const float* dy, int lddy, const float* x, int 
     }
     if (patch_embed_supported(D, H, W, Cin, k, stride, pad)) {          // dW[co][(ci, tap)] = sum_tokens dy[token][co] * patch[token][(ci, tap)]
         float* A; void* rest; size_t rest_bytes;
+        note_conv_path(MI355SEG_PATH_WGRAD_PATCH_EMBED);
         rc = patch_embed_matrix(x, ldx, N, D, H, W, Cin, k, ws, ws_bytes, &A, &rest, &rest_bytes, st);
         if (rc) return rc;
         const int M = N * (D / k) * (H / k) * (W / k), K = Cin * k * k * k;
@@ -823,11 +852,14 @@ int mi355seg_conv3d_wgrad_ax_f32(const float* dy, int lddy, const float* x, int 
     if (f32_conv_policy() == MATH_X3 && wgrad_lowp_supported(MATH_X3, N, D, H, W, Cin, Cout, k, stride, pad, ldx, lddy) &&
         ((uintptr_t)x % 16) == 0 && ((uintptr_t)dy % 16) == 0)
         return conv_wgrad_lowp(MATH_X3, dy, lddy, x, ldx, dw, N, D, H, W, Cin, Cout, k, stride, accumulate, ws, ws_bytes, st, x_amax, dy_amax);
-    if (wgrad_mfma_supported(N, D, H, W, Cin, Cout, k, stride, pad, ldx, lddy) && ((uintptr_t)x % 16) == 0 && ((uintptr_t)dy % 16) == 0)
+    if (wgrad_mfma_supported(N, D, H, W, Cin, Cout, k, stride, pad, ldx, lddy) && ((uintptr_t)x % 16) == 0 && ((uintptr_t)dy % 16) == 0) {
+        note_conv_path(MI355SEG_PATH_WGRAD_MFMA);
         return conv_wgrad_mfma(dy, lddy, x, ldx, dw, N, D, H, W, Cin, Cout, k, accumulate, ws, ws_bytes, st);
+    }
     if (k == 1 && stride == 1 && pad == 0 && f32_conv_policy() == MATH_X3 && pw_wgrad_lowp_supported((long long)N * D * H * W, Cin, Cout, ldx, lddy, 4) &&
         ((uintptr_t)x % 16) == 0 && ((uintptr_t)dy % 16) == 0) {
         float* part; int nstrips;
+        note_conv_path(MI355SEG_PATH_WGRAD_PW_LOWP);
         rc = pw_wgrad_lowp(dy, lddy, x, ldx, N, D, H, W, Cin, Cout, &part, &nstrips, ws, ws_bytes, st);
         if (rc) return rc;
         wgrad_reduce(part, dw, nstrips, 1, Cin, Cout, accumulate, st);
@@ -836,26 +868,38 @@ int mi355seg_conv3d_wgrad_ax_f32(const float* dy, int lddy, const float* x, int 
     }
     if (k == 1 && stride == 1 && pad == 0 && pw_wgrad_supported((long long)N * D * H * W, Cin, Cout, 1, ldx, lddy)) {
         float* part; int nstrips;
+        note_conv_path(MI355SEG_PATH_WGRAD_PW_MFMA);
         rc = pw_wgrad_mfma(dy, lddy, x, ldx, N, D, H, W, Cin, Cout, 1, &part, &nstrips, ws, ws_bytes, st);
         if (rc) return rc;
         wgrad_reduce(part, dw, nstrips, 1, Cin, Cout, accumulate, st);
         SEG_CHECK_LAUNCH();
         return MI355SEG_OK;
     }
-    if (tinypw_supported(Cin, Cout, k, stride, pad))
+    if (tinypw_supported(Cin, Cout, k, stride, pad)) {
+        note_conv_path(MI355SEG_PATH_WGRAD_TINYPW);
         return tinypw_wgrad(dy, lddy, x, ldx, dw, (long long)N * D * H * W, Cin, Cout, accumulate, ws, ws_bytes, st);
-    if (stem_supported(Cin, Cout, k, stride, pad, lddy))
+    }
+    if (stem_supported(Cin, Cout, k, stride, pad, lddy))         // (stem_wgrad records which of its kernels: MI355SEG_PATH_WGRAD_STEM*)
         return stem_wgrad(dy, lddy, x, ldx, dw, N, D, H, W, Cin, Cout, accumulate, ws, ws_bytes, st);
-    if (head_supported(Cin, Cout, k, stride, pad, ldx))
+    if (head_supported(Cin, Cout, k, stride, pad, ldx)) {
+        note_conv_path(MI355SEG_PATH_WGRAD_HEAD);
         return head_wgrad(dy, lddy, x, ldx, dw, N, D, H, W, Cin, Cout, accumulate, ws, ws_bytes, st);
-    if (headk_wgrad_supported(Cin, Cout, k, stride, pad, ldx, lddy) && ((uintptr_t)x % 16) == 0 && ((uintptr_t)dy % 8) == 0)
+    }
+    if (headk_wgrad_supported(Cin, Cout, k, stride, pad, ldx, lddy) && ((uintptr_t)x % 16) == 0 && ((uintptr_t)dy % 8) == 0) {
+        note_conv_path(MI355SEG_PATH_WGRAD_HEADK);
         return headk_wgrad(dy, lddy, x, ldx, dw, N, D, H, W, Cin, k, accumulate, ws, ws_bytes, st);
-    if (smallcin_wgrad_supported(Cin, Cout, k))
+    }
+    if (smallcin_wgrad_supported(Cin, Cout, k))                  // (smallcin_wgrad records MI355SEG_PATH_WGRAD_SMALLCIN[_K5_TILED])
         return smallcin_wgrad(dy, lddy, x, ldx, dw, N, D, H, W, Cin, Cout, k, stride, pad, accumulate, ws, ws_bytes, st);
-    if (smallcout_wgrad_supported(Cin, Cout, k, ldx) && ((uintptr_t)x % 16) == 0)
+    if (smallcout_wgrad_supported(Cin, Cout, k, ldx) && ((uintptr_t)x % 16) == 0) {
+        note_conv_path(MI355SEG_PATH_WGRAD_SMALLCOUT);
         return smallcout_wgrad(dy, lddy, x, ldx, dw, N, D, H, W, Cin, Cout, k, stride, pad, accumulate, ws, ws_bytes, st);
-    if (gwgrad_supported(N, D, H, W, Cin, Cout, k, stride, pad, ldx, lddy) && ((uintptr_t)x % 16) == 0 && ((uintptr_t)dy % 16) == 0)
+    }
+    if (gwgrad_supported(N, D, H, W, Cin, Cout, k, stride, pad, ldx, lddy) && ((uintptr_t)x % 16) == 0 && ((uintptr_t)dy % 16) == 0) {
+        note_conv_path(MI355SEG_PATH_WGRAD_GWGRAD);
         return conv_gwgrad(dy, lddy, x, ldx, dw, N, D, H, W, Cin, Cout, k, stride, pad, accumulate, ws, ws_bytes, st);
+    }
+    note_conv_path(MI355SEG_PATH_WGRAD_GENERIC);
     return conv_wgrad_generic(dy, lddy, x, ldx, dw, g, accumulate, ws, ws_bytes, st);
 }
 

@@ -465,6 +465,13 @@ int conv_fwd_mfma(int math, const void* x, int ldx, const float* w, const float*
     // fp32 tensors, bf16x6, 16-wide tiles: the 16x16x32-MFMA kernel (conv_x3s.hip) with its own weight packing
     const bool x3s = x3w || (math == MATH_X3 && x3s_enabled() && x3s_plan_ok(p, x, ldx, ksplit > 1 ? (void*)slabs : y, ksplit > 1 ? Cout : ldy, (long long)D * H * W));
     // the BatchNorm-backward sums of the layer in front ride in that kernel's epilogue (whole-K launches only)
+    // the one place that records the igemm branches of the fp32 dispatchers (mi355seg_last_conv_path): every caller on fp32 tensors --
+    // conv3d_fwd / _fused / _pro, conv3d_dgrad / _bnsums -- comes through here, and only here is it known which tiles run
+    if (math != MATH_B16)
+        note_conv_path(pro ? MI355SEG_PATH_FWD_PRO_X3S
+                       : math == MATH_F32 ? (dgrad ? MI355SEG_PATH_DGRAD_MFMA_F32 : MI355SEG_PATH_FWD_MFMA_F32)
+                       : x3s ? (dgrad ? MI355SEG_PATH_DGRAD_MFMA_X3S : MI355SEG_PATH_FWD_MFMA_X3S)
+                             : (dgrad ? MI355SEG_PATH_DGRAD_MFMA_X3 : MI355SEG_PATH_FWD_MFMA_X3));
     const bool bn_epi = bne && x3s && ksplit == 1 && !ssum && !bias && !act && (bne->ldx % 4) == 0 && ((uintptr_t)bne->x % 16) == 0 && Cout % 4 == 0;
     float* bnpart = bn_epi ? cv.take<float>((size_t)p.nM * Cout * 2) : nullptr;
     double* rtmp = (bn_epi || spart) ? reinterpret_cast<double*>(cv.take<char>(part_reduce_ws_bytes(Cout))) : nullptr;

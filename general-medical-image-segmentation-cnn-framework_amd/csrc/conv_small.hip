@@ -888,6 +888,7 @@ int smallcin_wgrad(const T* dy, int lddy, const T* x, int ldx, float* dw, int N,
         SmallGeom sg{N, D, H, W, 1, Cout, ldx, 0};
         const int TX = 256 / (Cout / 4);
         if (W % TX == 0 && H % S1_TY == 0 && D % S1_TZ == 0) {      // LDS-tiled k5 stem wgrad: one block per (tile strip, dz plane)
+            if constexpr (sizeof(T) == 4) note_conv_path(MI355SEG_PATH_WGRAD_SMALLCIN_K5_TILED);
             const int ntiles = (int)(nvox / ((long long)S1_TZ * S1_TY * TX));
             int nb = ntiles < 128 ? ntiles : 128;
             SEG_CHECK_WS((size_t)nb * 125 * Cout * sizeof(float), ws_bytes);
@@ -904,6 +905,7 @@ int smallcin_wgrad(const T* dy, int lddy, const T* x, int ldx, float* dw, int N,
             return MI355SEG_OK;
         }
     }
+    if constexpr (sizeof(T) == 4) note_conv_path(MI355SEG_PATH_WGRAD_SMALLCIN);
     const int vw = (Cout % 4 == 0) ? 4 : 1, lpv = Cout / vw;
     int nblk = small_grid(nvox, 256 / lpv);
     if (nblk > 512) nblk = 512;
@@ -986,6 +988,7 @@ int stem_fwd(const T* x, int ldx, const float* w, const float* bias, T* y, int l
         const size_t sp_bytes = align_up((size_t)nb * Cout * 3 * sizeof(float), 256);
         const bool in_kernel = ssum && nb > 512 && sp_bytes + part_reduce_ws_bytes(Cout) <= ws_bytes;
         if (in_kernel) spart = (float*)ws;
+        if constexpr (sizeof(T) == 4) note_conv_path(in_kernel ? MI355SEG_PATH_FWD_STEM_TILED_STATS : MI355SEG_PATH_FWD_STEM_TILED);
         {
             ProfScope ps(PF_DIRECT, 2.0 * nvox * 27.0 * Cin * Cout, (double)sizeof(T) * nvox * (Cin + Cout), st);
             if (in_kernel) {
@@ -1005,6 +1008,7 @@ int stem_fwd(const T* x, int ldx, const float* w, const float* bias, T* y, int l
     }
     {
         ProfScope ps(PF_DIRECT, 2.0 * nvox * 27.0 * Cin * Cout, (double)sizeof(T) * nvox * (Cin + Cout), st);
+        if constexpr (sizeof(T) == 4) note_conv_path(Cin == 1 ? MI355SEG_PATH_FWD_STEM_C1 : (Cin == 2 ? MI355SEG_PATH_FWD_STEM_C2 : MI355SEG_PATH_FWD_STEM_C4));
         if (Cin == 1) hipLaunchKernelGGL((stem_fwd_kernel<T, 1>), dim3(nblk), dim3(256), lds, st, x, w, bias, y, spart, g);
         else if (Cin == 2) hipLaunchKernelGGL((stem_fwd_kernel<T, 2>), dim3(nblk), dim3(256), lds, st, x, w, bias, y, spart, g);
         else hipLaunchKernelGGL((stem_fwd_kernel<T, 4>), dim3(nblk), dim3(256), lds, st, x, w, bias, y, spart, g);
@@ -1028,6 +1032,7 @@ int stem_wgrad(const T* dy, int lddy, const T* x, int ldx, float* dw, int N, int
     if (stem1_tiled_ok(g)) {
         const int ntiles = (int)(nvox / ((long long)S1_TZ * S1_TY * (256 / (Cout / 4))));   // tile = 2 x 4 x TX voxels
         int nb = ntiles < 512 ? ntiles : 512;
+        if constexpr (sizeof(T) == 4) note_conv_path(MI355SEG_PATH_WGRAD_STEM_TILED);
         {
             ProfScope ps(PF_DIRECT, 2.0 * nvox * 27.0 * Cin * Cout, (double)sizeof(T) * nvox * (Cin + Cout), st);
             hipLaunchKernelGGL(stem1_wgrad_kernel<T>, dim3(nb), dim3(256), stem1_lds(Cout), st, x, dy, part, g, lddy, ntiles);
@@ -1038,10 +1043,12 @@ int stem_wgrad(const T* dy, int lddy, const T* x, int ldx, float* dw, int N, int
         return MI355SEG_OK;
     }
     if (Cin == 4 && ldx % 4 == 0 && ((uintptr_t)x % (4 * sizeof(T))) == 0 && (size_t)4 * 9 * 4 * Cout * 4 <= 64 * 1024) {
+        if constexpr (sizeof(T) == 4) note_conv_path(MI355SEG_PATH_WGRAD_STEM_C4);
         ProfScope ps(PF_DIRECT, 2.0 * nvox * 27.0 * Cin * Cout, (double)sizeof(T) * nvox * (Cin + Cout), st);
         hipLaunchKernelGGL((stem4_wgrad_kernel<T>), dim3(nblk, 3), dim3(256), (size_t)4 * 9 * 4 * Cout * 4, st, x, dy, part, g, lddy);
         SEG_CHECK_LAUNCH();
     } else {
+        if constexpr (sizeof(T) == 4) note_conv_path(MI355SEG_PATH_WGRAD_STEM);
         ProfScope ps(PF_DIRECT, 2.0 * nvox * 27.0 * Cin * Cout, (double)sizeof(T) * nvox * (Cin + Cout), st);
         hipLaunchKernelGGL((stem_wgrad_kernel<T, 0>), dim3(nblk, Cin), dim3(256), lds, st, x, dy, part, g, lddy);
         SEG_CHECK_LAUNCH();

@@ -1,5 +1,7 @@
 // convt_api.inc -- ConvTranspose3d k2 s2 entry points, compiled once per storage type (TT = float with TT_MATH = MATH_F32,
 // TT = bf16 with TT_MATH = MATH_B16).  Weights, bias and weight gradients are always fp32.
+// The fp32 entry points record the branch they take (MI355SEG_PATH_CONVT_*, mi355seg_last_conv_path).
+#define CONVT_NOTE(code) do { if (sizeof(TT) == 4) note_conv_path(code); } while (0)
 int FN(convt3d_k2s2_fwd)(const TT* x, int ldx, const float* w, const float* bias,
                                   TT* y, int ldy, int N, int D, int H, int W, int Cin, int Cout,
                                   void* ws, size_t ws_bytes, void* stream) {
@@ -15,14 +17,19 @@ int FN(convt3d_k2s2_fwd_ax)(const TT* x, int ldx, const float* w, const float* b
     SEG_CHECK_ARG(!(y_amax && sizeof(TT) != 4), "convt3d_k2s2_fwd_ax: y_amax is for fp32 tensors");
     hipStream_t st = (hipStream_t)stream;
     if ((sizeof(TT) == 2 || f32_conv_policy() == MATH_X3) && convt_direct_supported((int)sizeof(TT), false, N, D, H, W, Cin, Cout, ldx, ldy) &&
-        ((uintptr_t)x % 16) == 0 && ((uintptr_t)y % 16) == 0 && ((uintptr_t)bias % 16) == 0)
+        ((uintptr_t)x % 16) == 0 && ((uintptr_t)y % 16) == 0 && ((uintptr_t)bias % 16) == 0) {
+        CONVT_NOTE(MI355SEG_PATH_CONVT_FWD_DIRECT);
         return convt_direct<TT>(false, x, ldx, w, bias, y, ldy, N, D, H, W, Cin, Cout, ws, ws_bytes, st, y_amax);
+    }
     struct AmaxAfter {                        // the other forms have no such epilogue: one pass over what they wrote
         const TT* y; int ldy; long long rows; int C; float* slot; hipStream_t st;
         ~AmaxAfter() { if constexpr (sizeof(TT) == 4) { if (slot) tensor_amax((const float*)y, ldy, rows, C, nullptr, slot, st); } }
     } after{y, ldy, (long long)N * 8 * D * H * W, Cout, y_amax, st};
-    if (convt_mfma_supported(TT_MATH, N, D, H, W, Cin, Cout, ldx, ldy) && ((uintptr_t)x % 16) == 0)
+    if (convt_mfma_supported(TT_MATH, N, D, H, W, Cin, Cout, ldx, ldy) && ((uintptr_t)x % 16) == 0) {
+        CONVT_NOTE(MI355SEG_PATH_CONVT_FWD_MFMA);
         return convt_fwd_mfma(TT_MATH, x, ldx, w, bias, y, ldy, N, D, H, W, Cin, Cout, ws, ws_bytes, st);
+    }
+    CONVT_NOTE(MI355SEG_PATH_CONVT_FWD_PLAIN);
     Carver cv(ws);
     float* wp = cv.take<float>((size_t)8 * Cin * Cout);
     SEG_CHECK_WS(cv.used(), ws_bytes);
@@ -41,10 +48,15 @@ int FN(convt3d_k2s2_dgrad)(const TT* dy, int lddy, const float* w, TT* dx, int l
                   "convt3d_k2s2_dgrad: bad arguments");
     hipStream_t st = (hipStream_t)stream;
     if ((sizeof(TT) == 2 || f32_conv_policy() == MATH_X3) && convt_direct_supported((int)sizeof(TT), true, N, D, H, W, Cin, Cout, lddx, lddy) &&
-        ((uintptr_t)dy % 16) == 0 && ((uintptr_t)dx % 16) == 0)
+        ((uintptr_t)dy % 16) == 0 && ((uintptr_t)dx % 16) == 0) {
+        CONVT_NOTE(MI355SEG_PATH_CONVT_DGRAD_DIRECT);
         return convt_direct<TT>(true, dy, lddy, w, nullptr, dx, lddx, N, D, H, W, Cin, Cout, ws, ws_bytes, st);
-    if (convt_mfma_supported(TT_MATH, N, D, H, W, Cin, Cout, lddx, lddy) && ((uintptr_t)dy % 16) == 0)
+    }
+    if (convt_mfma_supported(TT_MATH, N, D, H, W, Cin, Cout, lddx, lddy) && ((uintptr_t)dy % 16) == 0) {
+        CONVT_NOTE(MI355SEG_PATH_CONVT_DGRAD_MFMA);
         return convt_dgrad_mfma(TT_MATH, dy, lddy, w, dx, lddx, N, D, H, W, Cin, Cout, ws, ws_bytes, st);
+    }
+    CONVT_NOTE(MI355SEG_PATH_CONVT_DGRAD_PLAIN);
     Carver cv(ws);
     float* wd = cv.take<float>((size_t)8 * Cin * Cout);
     SEG_CHECK_WS(cv.used(), ws_bytes);
@@ -71,6 +83,7 @@ int FN(convt3d_k2s2_wgrad)(const TT* dy, int lddy, const TT* x, int ldx,
     if ((sizeof(TT) == 2 || f32_conv_policy() == MATH_X3) && convt_wgrad_lowp_supported(nvox, Cin, Cout, ldx, lddy, (int)sizeof(TT)) &&
         ((uintptr_t)x % 16) == 0 && ((uintptr_t)dy % 16) == 0) {
         float* part; int nstrips;
+        CONVT_NOTE(MI355SEG_PATH_CONVT_WGRAD_LOWP);
         int rc = convt_wgrad_lowp(dy, lddy, x, ldx, N, D, H, W, Cin, Cout, &part, &nstrips, ws, ws_bytes, st);
         if (rc) return rc;
         convt_wgrad_reduce(part, dw, nstrips, Cin, Cout, st);
@@ -79,12 +92,14 @@ int FN(convt3d_k2s2_wgrad)(const TT* dy, int lddy, const TT* x, int ldx,
     }
     if (pw_wgrad_supported(nvox, Cin, Cout, 8, ldx, lddy) && ((uintptr_t)x % (4 * sizeof(TT))) == 0 && ((uintptr_t)dy % (4 * sizeof(TT))) == 0) {
         float* part; int nstrips;
+        CONVT_NOTE(MI355SEG_PATH_CONVT_WGRAD_MFMA);
         int rc = pw_wgrad_mfma(dy, lddy, x, ldx, N, D, H, W, Cin, Cout, 8, &part, &nstrips, ws, ws_bytes, st);
         if (rc) return rc;
         convt_wgrad_reduce(part, dw, nstrips, Cin, Cout, st);
         SEG_CHECK_LAUNCH();
         return MI355SEG_OK;
     }
+    CONVT_NOTE(MI355SEG_PATH_CONVT_WGRAD_PLAIN);
     const int splits = convt_splits(nvox, Cin, Cout);
     Carver cv(ws);
     float* part = cv.take<float>((size_t)splits * 8 * Cin * Cout);
@@ -98,3 +113,4 @@ int FN(convt3d_k2s2_wgrad)(const TT* dy, int lddy, const TT* x, int ldx,
     return MI355SEG_OK;
 }
 
+#undef CONVT_NOTE

@@ -231,6 +231,73 @@ int mi355seg_convt3d_k2s2_wgrad_f32(const float* dy, int lddy, const float* x, i
                                     float* dw, float* db, int N, int D, int H, int W, int Cin, int Cout,
                                     void* ws, size_t ws_bytes, void* stream);
 
+/* ------------------------------------------------------------------ which branch ran
+ * Every fp32 Conv3d / ConvTranspose3d k2 s2 dispatcher (mi355seg_conv3d_{fwd,dgrad,wgrad}[_ax|_pro_ax|_yamax_ax]_f32,
+ * mi355seg_conv3d_fwd_fused_f32, mi355seg_conv3d_dgrad_bnsums[_ax]_f32, mi355seg_convt3d_k2s2_{fwd,dgrad,wgrad}[_ax]_f32) records the branch of its if-chain it took in one host-side integer before it
+ * launches: a test asks after the call and so knows which kernel it has graded (tests/test_gpu_conv_paths.py).  One code per
+ * branch; a branch that chooses between kernels has one per kernel.  Process-wide like the conv math, not thread-local; the bf16
+ * entry points and mi355seg_stem_wgrad_bnbwd_f32 (one kernel, no choice) do not record.  0 before the first call. */
+enum {
+    MI355SEG_PATH_NONE = 0,
+    /* mi355seg_conv3d_fwd*_f32 */
+    MI355SEG_PATH_FWD_MFMA_X3S = 1,          /* split-precision igemm, 16x16x32 tiles (conv_x3s.hip) */
+    MI355SEG_PATH_FWD_MFMA_X3 = 2,           /* split-precision igemm, generic 32x32x16 tiles */
+    MI355SEG_PATH_FWD_MFMA_F32 = 3,          /* fp32 MFMA igemm */
+    MI355SEG_PATH_FWD_PATCH_EMBED = 4,       /* kernel = stride as one GEMM */
+    MI355SEG_PATH_FWD_GATHER = 5,            /* gather igemm (strided / even kernels) */
+    MI355SEG_PATH_FWD_HEADK = 6,             /* z-marching head, Cout = 2 */
+    MI355SEG_PATH_FWD_STEMK = 7,             /* z-marching k5 stem, Cin = 1 | 2 */
+    MI355SEG_PATH_FWD_STEM_TILED_STATS = 8,  /* k3 stem, LDS-tiled 1-channel kernel with in-kernel statistics */
+    MI355SEG_PATH_FWD_STEM_TILED = 9,        /* k3 stem, LDS-tiled 1-channel kernel */
+    MI355SEG_PATH_FWD_STEM_C1 = 10,          /* k3 stem, direct kernel, Cin = 1 */
+    MI355SEG_PATH_FWD_STEM_C2 = 11,
+    MI355SEG_PATH_FWD_STEM_C4 = 12,
+    MI355SEG_PATH_FWD_TINYPW = 13,           /* k1, at most 4 channels on either side */
+    MI355SEG_PATH_FWD_HEAD = 14,             /* k1 head, Cout = 2 | 4 */
+    MI355SEG_PATH_FWD_GENERIC = 15,
+    MI355SEG_PATH_FWD_PRO_X3S = 16,          /* mi355seg_conv3d_fwd_pro_ax_f32 */
+    /* mi355seg_conv3d_dgrad*_f32 */
+    MI355SEG_PATH_DGRAD_MFMA_X3S = 20,
+    MI355SEG_PATH_DGRAD_MFMA_X3 = 21,
+    MI355SEG_PATH_DGRAD_MFMA_F32 = 22,
+    MI355SEG_PATH_DGRAD_GATHER = 23,
+    MI355SEG_PATH_DGRAD_HEADK = 24,
+    MI355SEG_PATH_DGRAD_HEAD = 25,
+    MI355SEG_PATH_DGRAD_TINYPW = 26,
+    MI355SEG_PATH_DGRAD_K2S2_CONVT = 27,     /* k2 s2 p0 as the forward of ConvTranspose3d k2 s2 */
+    MI355SEG_PATH_DGRAD_GENERIC = 28,
+    /* mi355seg_conv3d_wgrad*_f32 */
+    MI355SEG_PATH_WGRAD_PATCH_EMBED = 40,
+    MI355SEG_PATH_WGRAD_LOWP_WIDE = 41,      /* conv_wgrad_lowp, 32 x 64 channel blocks */
+    MI355SEG_PATH_WGRAD_LOWP_SWAPPED = 42,   /* conv_wgrad_lowp, the wide kernel with the operands' roles swapped */
+    MI355SEG_PATH_WGRAD_LOWP_NARROW = 43,    /* conv_wgrad_lowp, 32 x 32 channel blocks */
+    MI355SEG_PATH_WGRAD_MFMA = 44,           /* fp32 MFMA, k3 / k5 s1 */
+    MI355SEG_PATH_WGRAD_PW_LOWP = 45,        /* k1, split-precision planes */
+    MI355SEG_PATH_WGRAD_PW_MFMA = 46,        /* k1, fp32 MFMA */
+    MI355SEG_PATH_WGRAD_TINYPW = 47,
+    MI355SEG_PATH_WGRAD_STEM_TILED = 48,     /* k3 stem, LDS-tiled 1-channel kernel */
+    MI355SEG_PATH_WGRAD_STEM_C4 = 49,        /* k3 stem, stem4_wgrad_kernel */
+    MI355SEG_PATH_WGRAD_STEM = 50,           /* k3 stem, direct kernel */
+    MI355SEG_PATH_WGRAD_HEAD = 51,
+    MI355SEG_PATH_WGRAD_HEADK = 52,
+    MI355SEG_PATH_WGRAD_SMALLCIN_K5_TILED = 53,
+    MI355SEG_PATH_WGRAD_SMALLCIN = 54,
+    MI355SEG_PATH_WGRAD_SMALLCOUT = 55,
+    MI355SEG_PATH_WGRAD_GWGRAD = 56,         /* MFMA gather weight gradient */
+    MI355SEG_PATH_WGRAD_GENERIC = 57,
+    /* mi355seg_convt3d_k2s2_*_f32 */
+    MI355SEG_PATH_CONVT_FWD_DIRECT = 60,
+    MI355SEG_PATH_CONVT_FWD_MFMA = 61,
+    MI355SEG_PATH_CONVT_FWD_PLAIN = 62,
+    MI355SEG_PATH_CONVT_DGRAD_DIRECT = 63,
+    MI355SEG_PATH_CONVT_DGRAD_MFMA = 64,
+    MI355SEG_PATH_CONVT_DGRAD_PLAIN = 65,
+    MI355SEG_PATH_CONVT_WGRAD_LOWP = 66,
+    MI355SEG_PATH_CONVT_WGRAD_MFMA = 67,
+    MI355SEG_PATH_CONVT_WGRAD_PLAIN = 68
+};
+int mi355seg_last_conv_path(void);
+
 /* ------------------------------------------------------------------ Batch / Instance norm
  * Replaces nn.BatchNorm3d in training mode (native_batch_norm, unet3d.py:88,100;
  * vnet3d.py:27,49,66,88,112) and nn.InstanceNorm3d (residual_unet3d.py:27..106), fused
