@@ -23,43 +23,29 @@ from ._lib import lib
 _p, _stream, _sfx = F._p, F._stream, F._sfx
 
 
-def _geom(x, w, stride, pad):
-    N, D, H, W, Cin = x.shape
-    Cout, k = w.shape[0], w.shape[2]
-    Do, Ho, Wo = [(e + 2 * pad - k) // stride + 1 for e in (D, H, W)]
-    return N, D, H, W, Cin, Cout, k, Do, Ho, Wo
-
-
 # ------------------------------------------------------------------------------------------------ Conv3d
 @torch.library.custom_op("mi355seg::conv3d", mutates_args=())
 def conv3d(x: Tensor, weight: Tensor, bias: Optional[Tensor], stride: int, padding: int) -> Tensor:
     xv, ldx = F.cl_view(x, "conv3d input")
-    w = F._w32(weight, "conv3d weight")
-    N, D, H, W, Cin, Cout, k, Do, Ho, Wo = _geom(xv, w, stride, padding)
-    y = torch.empty((N, Do, Ho, Wo, Cout), dtype=xv.dtype, device=xv.device)
+    g, w = F._conv_geom(xv, weight, stride, padding, "conv3d")
+    y = torch.empty(g.out_shape, dtype=xv.dtype, device=xv.device)
     L = lib()
-    ws = F.workspace(F._conv_ws(L, xv, N, D, H, W, Cin, Cout, k, stride, padding), xv.device)
-    L.call("mi355seg_conv3d_fwd_" + _sfx(xv), _p(xv), ldx, _p(w), _p(bias), _p(y), Cout, N, D, H, W, Cin, Cout, k, stride, padding,
-           None, None, _p(ws), ws.numel(), _stream())
+    F._conv_fwd(L, g, xv, ldx, w, bias, y, g.Cout, F.workspace(g.ws_bytes(L, xv.dtype), xv.device))
     return y
 
 
 @conv3d.register_fake
 def _(x, weight, bias, stride, padding):
-    N, D, H, W, Cin, Cout, k, Do, Ho, Wo = _geom(x, weight, stride, padding)
-    return x.new_empty((N, Do, Ho, Wo, Cout))
+    return x.new_empty(F._conv_geom(x, weight, stride, padding, "conv3d")[0].out_shape)
 
 
 @torch.library.custom_op("mi355seg::conv3d_dgrad", mutates_args=())
 def conv3d_dgrad(dy: Tensor, weight: Tensor, D: int, H: int, W: int, stride: int, padding: int) -> Tensor:
     dyv, lddy = F.cl_view(dy, "conv3d grad")
-    w = F._w32(weight, "conv3d weight")
-    N, Cout, Cin, k = dyv.shape[0], w.shape[0], w.shape[1], w.shape[2]
-    dx = torch.empty((N, D, H, W, Cin), dtype=dyv.dtype, device=dyv.device)
+    g, w = F._conv_geom((dyv.shape[0], D, H, W, weight.shape[1]), weight, stride, padding, "conv3d")
+    dx = torch.empty(g.args[:5], dtype=dyv.dtype, device=dyv.device)
     L = lib()
-    ws = F.workspace(F._conv_ws(L, dyv, N, D, H, W, Cin, Cout, k, stride, padding), dyv.device)
-    L.call("mi355seg_conv3d_dgrad_" + _sfx(dyv), _p(dyv), lddy, _p(w), _p(dx), Cin, N, D, H, W, Cin, Cout, k, stride, padding,
-           _p(ws), ws.numel(), _stream())
+    F._conv_dgrad(L, g, dyv, lddy, w, dx, g.Cin, F.workspace(g.ws_bytes(L, dyv.dtype), dyv.device))
     return dx
 
 
@@ -73,14 +59,11 @@ def conv3d_wgrad(dy: Tensor, x: Tensor, kernel_size: int, stride: int, padding: 
     """(dw fp32 (Cout, Cin, k, k, k), db fp32 (Cout) -- zeros(0) when with_bias is False)."""
     dyv, lddy = F.cl_view(dy, "conv3d grad")
     xv, ldx = F.cl_view(F._like(x, dyv), "conv3d input")
-    N, D, H, W, Cin = xv.shape
-    Cout, k = dyv.shape[-1], kernel_size
-    dw = torch.empty((Cout, Cin, k, k, k), dtype=torch.float32, device=xv.device)
-    db = torch.empty(Cout if with_bias else 0, dtype=torch.float32, device=xv.device)
+    g = F._ConvGeom(*xv.shape, dyv.shape[-1], kernel_size, stride, padding)
+    dw = torch.empty((g.Cout, g.Cin) + (g.k,) * 3, dtype=torch.float32, device=xv.device)
+    db = torch.empty(g.Cout if with_bias else 0, dtype=torch.float32, device=xv.device)
     L = lib()
-    ws = F.workspace(F._conv_ws(L, xv, N, D, H, W, Cin, Cout, k, stride, padding), xv.device)
-    L.call("mi355seg_conv3d_wgrad_" + _sfx(xv), _p(dyv), lddy, _p(xv), ldx, _p(dw), _p(db) if with_bias else None, N, D, H, W, Cin, Cout,
-           k, stride, padding, 0, _p(ws), ws.numel(), _stream())
+    F._conv_wgrad(L, g, dyv, lddy, xv, ldx, dw, db if with_bias else None, F.workspace(g.ws_bytes(L, xv.dtype), xv.device))
     return dw, db
 
 
@@ -129,17 +112,8 @@ def conv_transpose3d_k2s2_backward(dy: Tensor, x: Tensor, weight: Tensor, with_b
     xv, ldx = F.cl_view(x, "conv_transpose3d input")
     dyv, lddy = F.cl_view(F._like(dy, xv), "conv_transpose3d grad")
     w = F._w32(weight, "conv_transpose3d weight")
-    N, D, H, W, Cin = xv.shape
-    Cout = w.shape[1]
-    L = lib()
-    ws = F.workspace(L.query("mi355seg_convt3d_k2s2_ws_bytes", N, D, H, W, Cin, Cout), xv.device)
-    dx = torch.empty((N, D, H, W, Cin), dtype=xv.dtype, device=xv.device)
-    dw = torch.empty_like(w)
-    db = torch.empty(Cout if with_bias else 0, dtype=torch.float32, device=xv.device)
-    L.call("mi355seg_convt3d_k2s2_dgrad_" + _sfx(xv), _p(dyv), lddy, _p(w), _p(dx), Cin, N, D, H, W, Cin, Cout, _p(ws), ws.numel(), _stream())
-    L.call("mi355seg_convt3d_k2s2_wgrad_" + _sfx(xv), _p(dyv), lddy, _p(xv), ldx, _p(dw), _p(db) if with_bias else None, N, D, H, W, Cin, Cout,
-           _p(ws), ws.numel(), _stream())
-    return dx, dw, db
+    dx, dw, db = F._convt_k2s2_bwd(lib(), xv, ldx, dyv, lddy, w, with_bias, True, True)
+    return dx, dw, (db if with_bias else torch.empty(0, dtype=torch.float32, device=xv.device))
 
 
 @conv_transpose3d_k2s2_backward.register_fake
@@ -451,21 +425,16 @@ def conv_bn_act(x: Tensor, weight: Tensor, bias: Optional[Tensor], gamma: Tensor
     mean, rstd, updated running_mean, updated running_var); ``conv_bn_act_train`` below writes the last two back into the
     module's buffers, as aten's native_batch_norm callers do."""
     xv, ldx = F.cl_view(x, "conv3d input")
-    w = F._w32(weight, "conv3d weight")
-    N, D, H, W, Cin, Cout, k, Do, Ho, Wo = _geom(xv, w, stride, padding)
+    g, w = F._conv_geom(xv, weight, stride, padding, "conv3d")
+    Cout, rows = g.Cout, g.rows_out
     dev = xv.device
     L = lib()
-    rows = N * Do * Ho * Wo
-    ws = F.workspace(max(F._conv_ws(L, xv, N, D, H, W, Cin, Cout, k, stride, padding), L.query("mi355seg_norm_ws_bytes", rows, 1, Cout)), dev)
-    y = torch.empty((N, Do, Ho, Wo, Cout), dtype=xv.dtype, device=dev)
+    ws = F.workspace(max(g.ws_bytes(L, xv.dtype), L.query("mi355seg_norm_ws_bytes", rows, 1, Cout)), dev)
+    y = torch.empty(g.out_shape, dtype=xv.dtype, device=dev)
     sums = torch.empty(2 * Cout, dtype=torch.float64, device=dev)
-    L.call("mi355seg_conv3d_fwd_" + _sfx(xv), _p(xv), ldx, _p(w), _p(bias), _p(y), Cout, N, D, H, W, Cin, Cout, k, stride, padding,
-           sums.data_ptr(), sums.data_ptr() + 8 * Cout, _p(ws), ws.numel(), _stream())
-    mean = torch.empty(Cout, dtype=torch.float32, device=dev)
-    rstd = torch.empty(Cout, dtype=torch.float32, device=dev)
+    F._conv_fwd(L, g, xv, ldx, w, bias, y, Cout, ws, sums)
     new_rm, new_rv = running_mean.detach().clone(), running_var.detach().clone()
-    L.call("mi355seg_norm_stats_from_sums_f32", sums.data_ptr(), sums.data_ptr() + 8 * Cout, rows, Cout, eps, _p(mean), _p(rstd),
-           _p(new_rm), _p(new_rv), momentum, _stream())
+    mean, rstd = F._stats_from_sums(L, sums, rows, Cout, eps, new_rm, new_rv, momentum)
     a = torch.empty_like(y)
     L.call("mi355seg_norm_act_fwd_" + _sfx(xv), _p(y), Cout, _p(mean), _p(rstd), _p(gamma), _p(beta), None, 0, _p(a), Cout, rows, 1, Cout, act, slope, _stream())
     return a, y, mean, rstd, new_rm, new_rv
@@ -473,9 +442,9 @@ def conv_bn_act(x: Tensor, weight: Tensor, bias: Optional[Tensor], gamma: Tensor
 
 @conv_bn_act.register_fake
 def _(x, weight, bias, gamma, beta, running_mean, running_var, stride, padding, momentum, eps, act, slope):
-    N, D, H, W, Cin, Cout, k, Do, Ho, Wo = _geom(x, weight, stride, padding)
-    f = lambda: torch.empty(Cout, dtype=torch.float32, device=x.device)
-    return x.new_empty((N, Do, Ho, Wo, Cout)), x.new_empty((N, Do, Ho, Wo, Cout)), f(), f(), f(), f()
+    shape = F._conv_geom(x, weight, stride, padding, "conv3d")[0].out_shape
+    f = lambda: torch.empty(shape[-1], dtype=torch.float32, device=x.device)
+    return x.new_empty(shape), x.new_empty(shape), f(), f(), f(), f()
 
 
 @torch.library.custom_op("mi355seg::conv_bn_act_backward", mutates_args=())
@@ -485,12 +454,11 @@ def conv_bn_act_backward(da: Tensor, x: Tensor, weight: Tensor, y: Tensor, mean:
     input and weight gradients of the convolution."""
     xv, ldx = F.cl_view(x, "conv3d input")
     dav, ldda = F.cl_view(F._like(da, xv), "conv+norm grad")
-    w = F._w32(weight, "conv3d weight")
-    N, D, H, W, Cin, Cout, k, Do, Ho, Wo = _geom(xv, w, stride, padding)
+    g, w = F._conv_geom(xv, weight, stride, padding, "conv3d")
+    Cout, rows = g.Cout, g.rows_out
     dev = xv.device
     L = lib()
-    rows = N * Do * Ho * Wo
-    ws = F.workspace(max(F._conv_ws(L, xv, N, D, H, W, Cin, Cout, k, stride, padding), L.query("mi355seg_norm_ws_bytes", rows, 1, Cout)), dev)
+    ws = F.workspace(max(g.ws_bytes(L, xv.dtype), L.query("mi355seg_norm_ws_bytes", rows, 1, Cout)), dev)
     dy = torch.empty_like(y)
     dgamma = torch.empty(Cout, dtype=torch.float32, device=dev)
     dbeta = torch.empty(Cout, dtype=torch.float32, device=dev)
@@ -499,9 +467,9 @@ def conv_bn_act_backward(da: Tensor, x: Tensor, weight: Tensor, y: Tensor, mean:
            _p(dy), Cout, _p(dgamma), _p(dbeta), None, 0, _p(db) if with_bias else None, rows, 1, Cout, act, slope, _p(ws), ws.numel(), _stream())
     dx = torch.empty(xv.shape if need_dx else (0,), dtype=xv.dtype, device=dev)
     if need_dx:
-        L.call("mi355seg_conv3d_dgrad_" + _sfx(xv), _p(dy), Cout, _p(w), _p(dx), Cin, N, D, H, W, Cin, Cout, k, stride, padding, _p(ws), ws.numel(), _stream())
+        F._conv_dgrad(L, g, dy, Cout, w, dx, g.Cin, ws)
     dw = torch.empty_like(w)
-    L.call("mi355seg_conv3d_wgrad_" + _sfx(xv), _p(dy), Cout, _p(xv), ldx, _p(dw), None, N, D, H, W, Cin, Cout, k, stride, padding, 0, _p(ws), ws.numel(), _stream())
+    F._conv_wgrad(L, g, dy, Cout, xv, ldx, dw, None, ws)
     return dx, dw, db, dgamma, dbeta
 
 
@@ -531,10 +499,9 @@ torch.library.register_autograd("mi355seg::conv_bn_act", _cba_backward, setup_co
 
 def conv_bn_act_train(x, conv, bn, act, slope=0.0):
     """One conv -> BatchNorm3d -> activation unit of the reference's blocks (unet3d.py:80-98) through the dispatcher, training mode."""
-    stride = conv.stride[0] if isinstance(conv.stride, (tuple, list)) else conv.stride
-    pad = conv.padding[0] if isinstance(conv.padding, (tuple, list)) else conv.padding
+    stride, pad = F._module_stride_pad(conv, "conv_bn_act_train")
     a, _y, _m, _r, rm, rv = torch.ops.mi355seg.conv_bn_act(x, conv.weight, conv.bias, bn.weight, bn.bias, bn.running_mean, bn.running_var,
-                                                            int(stride), int(pad), float(bn.momentum), float(bn.eps), int(act), float(slope))
+                                                            stride, pad, float(bn.momentum), float(bn.eps), int(act), float(slope))
     with torch.no_grad():
         bn.running_mean.copy_(rm)
         bn.running_var.copy_(rv)

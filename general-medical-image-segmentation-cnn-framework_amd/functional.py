@@ -261,15 +261,62 @@ def _like(g, x):
     return g if g.dtype == x.dtype else g.to(x.dtype)
 
 
-def _conv_ws(L, x, N, D, H, W, Cin, Cout, k, stride, pad):
-    name = "mi355seg_conv3d_ws_bytes_bf16" if x.dtype == torch.bfloat16 else "mi355seg_conv3d_ws_bytes"
-    return L.query(name, N, D, H, W, Cin, Cout, k, stride, pad)
-
-
 def _w32(w, what):
     if w.dtype != torch.float32:
         raise Mi355SegError(f"{what}: parameters are fp32 masters, got {w.dtype}")
     return w.contiguous()
+
+
+def _iso(v, what):
+    if isinstance(v, (tuple, list)):
+        if len(set(v)) != 1:
+            raise NotImplementedError(f"{what} must be isotropic, got {v}")
+        return int(v[0])
+    return int(v)
+
+
+class _ConvGeom:
+    """A Conv3d's geometry.  ``*g`` is (N, D, H, W, Cin, Cout, k, stride, pad): the nine arguments every mi355seg_conv3d_* entry point
+    takes, in its order.  What the nodes read again and again on a launch-bound step is worked out once, here."""
+    __slots__ = ("N", "D", "H", "W", "Cin", "Cout", "k", "stride", "pad", "args", "out_shape", "rows_in", "rows_out")
+
+    def __init__(self, N, D, H, W, Cin, Cout, k, stride, pad):
+        self.N, self.D, self.H, self.W, self.Cin, self.Cout, self.k, self.stride, self.pad = self.args = (N, D, H, W, Cin, Cout, k, stride, pad)
+        Do, Ho, Wo = [(e + 2 * pad - k) // stride + 1 for e in (D, H, W)]
+        self.out_shape = (N, Do, Ho, Wo, Cout)
+        self.rows_in, self.rows_out = N * D * H * W, N * Do * Ho * Wo
+
+    def __iter__(self):
+        return iter(self.args)
+
+    def ws_bytes(self, L, dtype):
+        return L.query("mi355seg_conv3d_ws_bytes_bf16" if dtype == torch.bfloat16 else "mi355seg_conv3d_ws_bytes", *self.args)
+
+
+def _conv_ws(L, x, *geom):
+    return _ConvGeom(*geom).ws_bytes(L, x.dtype)
+
+
+def _conv_geom(x, w, stride, pad, what):
+    """(geometry, contiguous fp32 weight) of ``what`` = a convolution of x -- a channel-last [N, D, H, W, Cin] tensor, or that shape --
+    with the weight w (Cout, Cin, k, k, k)."""
+    N, D, H, W, Cin = getattr(x, "shape", x)
+    Cout, Cin_w, k, kh, kw = w.shape
+    if Cin_w != Cin or kh != k or kw != k:
+        raise Mi355SegError(f"{what}: weight {tuple(w.shape)} does not match input channels {Cin} / cubic kernel")
+    return _ConvGeom(N, D, H, W, Cin, Cout, k, int(stride), int(pad)), _w32(w, what + " weight")
+
+
+def _module_stride_pad(conv, what):
+    """(stride, padding) of the nn.Conv3d module ``conv``; what the kernels do not implement is refused here, for every entry that takes a module."""
+    if conv.groups != 1 or _iso(conv.dilation, "dilation") != 1 or conv.padding_mode != "zeros":
+        raise NotImplementedError(f"{what}: only groups=1, dilation=1, zero padding are implemented")
+    return _iso(conv.stride, "stride"), _iso(conv.padding, "padding")
+
+
+def _module_geom(x, conv, what):
+    """The geometry of the nn.Conv3d module ``conv`` applied to x (as _conv_geom, behind the checks of _module_stride_pad)."""
+    return _conv_geom(x, conv.weight, *_module_stride_pad(conv, what), what)[0]
 
 
 def to_channels_last(x, dtype=None):
@@ -482,76 +529,127 @@ def _weight_amax(w):
 
 
 # ----------------------------------------------------------------------------- conv
+# The three passes of a convolution.  These launchers are the only places that name a plain mi355seg_conv3d_{fwd,dgrad,wgrad} entry
+# point (the pro / yamax / bnsums / fused / stem forms have one caller each and stay with it).  fp32 tensors always take the _ax
+# entry: the library defines each plain fp32 entry as exactly that call with NULL maxima (NULL = the pass measures what it needs).
+def _sums_ptrs(sums, C):
+    """(sum, sum of squares): the two halves of an fp64 [2 * C] buffer a convolution's epilogue reduces its output into."""
+    return (None, None) if sums is None else (sums.data_ptr(), sums.data_ptr() + 8 * C)
+
+
+def _conv_fwd(L, g, x, ldx, w, b, y, ldy, ws, sums=None, xa=None, wa=None, res=None):
+    """y = conv(x) + b.  sums: see _sums_ptrs (the batch statistics of y); xa / wa: f16x3 operand maxima; res = (tensor, ld), bf16
+    only: y = conv(x) + b + res, the sum in the convolution's epilogue where the launch allows."""
+    if x.dtype == torch.float32:
+        if res is not None:
+            raise Mi355SegError("conv3d: the residual epilogue exists for bf16 tensors only")
+        L.call("mi355seg_conv3d_fwd_ax_f32", _p(x), ldx, _p(w), _p(b), _p(y), ldy, *g, *_sums_ptrs(sums, g.Cout), _p(xa), _p(wa),
+               _p(ws), ws.numel(), _stream())
+    elif res is not None:
+        L.call("mi355seg_conv3d_fwd_res_bf16", _p(x), ldx, _p(w), _p(b), _p(res[0]), res[1], _p(y), ldy, *g, _p(ws), ws.numel(), _stream())
+    else:
+        L.call("mi355seg_conv3d_fwd_bf16", _p(x), ldx, _p(w), _p(b), _p(y), ldy, *g, *_sums_ptrs(sums, g.Cout), _p(ws), ws.numel(), _stream())
+
+
+def _conv_dgrad(L, g, dy, lddy, w, dx, lddx, ws, da=None, wa=None, res=None):
+    """dx = the input gradient of the convolution g.  res = (tensor, ld), bf16 only: dx = that + res (a second gradient of the same input)."""
+    if dy.dtype == torch.float32:
+        if res is not None:
+            raise Mi355SegError("conv3d: the residual epilogue exists for bf16 tensors only")
+        L.call("mi355seg_conv3d_dgrad_ax_f32", _p(dy), lddy, _p(w), _p(dx), lddx, *g, _p(da), _p(wa), _p(ws), ws.numel(), _stream())
+    elif res is not None:
+        L.call("mi355seg_conv3d_dgrad_res_bf16", _p(dy), lddy, _p(w), _p(res[0]), res[1], _p(dx), lddx, *g, _p(ws), ws.numel(), _stream())
+    else:
+        L.call("mi355seg_conv3d_dgrad_bf16", _p(dy), lddy, _p(w), _p(dx), lddx, *g, _p(ws), ws.numel(), _stream())
+
+
+def _conv_wgrad(L, g, dy, lddy, x, ldx, dw, db, ws, da=None, xa=None):
+    """dw (and db = the column sums of dy, where given) of the convolution g."""
+    if x.dtype == torch.float32:
+        L.call("mi355seg_conv3d_wgrad_ax_f32", _p(dy), lddy, _p(x), ldx, _p(dw), _p(db), *g, 0, _p(da), _p(xa), _p(ws), ws.numel(), _stream())
+    else:
+        L.call("mi355seg_conv3d_wgrad_bf16", _p(dy), lddy, _p(x), ldx, _p(dw), _p(db), *g, 0, _p(ws), ws.numel(), _stream())
+
+
+def _operand_amax(g, x, ldx, w, xa_in, measure_x):
+    """The f16x3 operand maxima (xa, wa) that the three passes of the layer g are handed -- or None where none of them reads maxima (bf16
+    tensors, the other conv maths, a layer without an f16x3 form).  xa_in: the maximum x carries, if any; it is kept whenever some
+    pass reads maxima and dropped otherwise (_Conv3d, _ConvBnAct and _DoubleConvBnAct always agreed on that).  max |w| is taken
+    where the forward or the input gradient reads it.  measure_x: x is measured here, once, when nothing carried its maximum and
+    both its readers -- the forward and the weight gradient -- want it; a caller passes False when its weight gradient will not run
+    (_Conv3d: the weight may need no gradient), and either reader then measures for itself.  A member that stays None means the same."""
+    use = _amax_use(x, *g)
+    if not use:
+        return None
+    wa = _weight_amax(w) if use & 3 else None
+    xa = xa_in
+    if xa is None and measure_x and (use & 1) and (use & 4):
+        xa = _measure_amax(x, ldx, g.rows_in, g.Cin)
+    return xa, wa
+
+
+def _stats_from_sums(L, sums, rows, C, eps, running_mean, running_var, momentum):
+    """(mean, rstd) fp32 [C] from the fp64 column sums a convolution's epilogue left (_sums_ptrs); running statistics, where given, are
+    updated in place as nn.BatchNorm3d does in training mode."""
+    mean = torch.empty(C, dtype=torch.float32, device=sums.device)
+    rstd = torch.empty(C, dtype=torch.float32, device=sums.device)
+    L.call("mi355seg_norm_stats_from_sums_f32", *_sums_ptrs(sums, C), rows, C, eps, _p(mean), _p(rstd), _p(running_mean), _p(running_var),
+           momentum, _stream())
+    return mean, rstd
+
+
+def _concat_base(t, Cout, lead_shape, dtype):
+    """The concat buffer that ``t`` is the right channel slice of -- a contiguous 5-D ``dtype`` tensor of shape lead_shape + (Cout + C_t,)
+    with exactly Cout free channels on t's left -- or None if t is no such slice."""
+    base = getattr(t, "_base", None)
+    ok = (base is not None and base.dim() == 5 and base.is_contiguous() and tuple(base.shape) == tuple(lead_shape) + (Cout + t.shape[-1],)
+          and base.dtype == dtype and t.data_ptr() == base.data_ptr() + base.element_size() * Cout and t.stride() == base.stride())
+    return base if ok else None
+
+
 class _Conv3d(Function):
     @staticmethod
     def forward(ctx, x, w, b, stride, pad, res=None):
         xa_in = _get_amax(x)
         x, ldx = cl_view(x, "conv3d input")
-        N, D, H, W, Cin = x.shape
-        Cout, Cin_w, k = w.shape[0], w.shape[1], w.shape[2]
-        if Cin_w != Cin or w.shape[3] != k or w.shape[4] != k:
-            raise Mi355SegError(f"conv3d: weight {tuple(w.shape)} does not match input channels {Cin} / cubic kernel")
-        w = _w32(w, "conv3d weight")
-        Do, Ho, Wo = [(e + 2 * pad - k) // stride + 1 for e in (D, H, W)]
-        y = torch.empty((N, Do, Ho, Wo, Cout), dtype=x.dtype, device=x.device)
+        g, w = _conv_geom(x, w, stride, pad, "conv3d")
+        y = torch.empty(g.out_shape, dtype=x.dtype, device=x.device)
         L = lib()
-        ws = workspace(_conv_ws(L, x, N, D, H, W, Cin, Cout, k, stride, pad), x.device)
-        ctx.amax = None
-        use = _amax_use(x, N, D, H, W, Cin, Cout, k, stride, pad)
-        if use:
-            xa, wa = xa_in, (_weight_amax(w) if use & 3 else None)
-            if xa is None and (use & 1) and (use & 4) and ctx.needs_input_grad[1]:    # forward and weight gradient both read x: measure once
-                xa = _measure_amax(x, ldx, N * D * H * W, Cin)
-            L.call("mi355seg_conv3d_fwd_ax_f32", _p(x), ldx, _p(w), _p(b), _p(y), Cout, N, D, H, W, Cin, Cout, k, stride, pad,
-                   None, None, _p(xa), _p(wa), _p(ws), ws.numel(), _stream())
-            ctx.amax = (xa, wa)
-        elif res is not None:                # bf16: conv(x) + res, the sum in the convolution's epilogue where the launch allows
+        ws = workspace(g.ws_bytes(L, x.dtype), x.device)
+        if res is not None:                  # bf16: conv(x) + res, the sum in the convolution's epilogue where the launch allows
             res, ldres = cl_view(res, "conv3d residual")
             if res.shape != y.shape or res.dtype != x.dtype:
                 raise Mi355SegError(f"conv3d: residual {tuple(res.shape)} {res.dtype} does not match the output {tuple(y.shape)} {x.dtype}")
-            L.call("mi355seg_conv3d_fwd_res_bf16", _p(x), ldx, _p(w), _p(b), _p(res), ldres, _p(y), Cout, N, D, H, W, Cin, Cout, k, stride, pad,
-                   _p(ws), ws.numel(), _stream())
-        else:
-            L.call("mi355seg_conv3d_fwd_" + _sfx(x), _p(x), ldx, _p(w), _p(b), _p(y), Cout, N, D, H, W, Cin, Cout, k, stride, pad,
-                   None, None, _p(ws), ws.numel(), _stream())
+            res = (res, ldres)
+        # (a pair without members still says that some pass reads maxima: the backward then measures dy once for its two readers)
+        ctx.amax = _operand_amax(g, x, ldx, w, xa_in, ctx.needs_input_grad[1])
+        xa, wa = ctx.amax or (None, None)
+        _conv_fwd(L, g, x, ldx, w, b, y, g.Cout, ws, None, xa, wa, res)
         ctx.save_for_backward(x, w)
-        ctx.geom = (N, D, H, W, Cin, Cout, k, stride, pad, ldx, b is not None)
+        ctx.geom = (g, ldx, b is not None)
         ctx.has_res = res is not None
         return y
 
     @staticmethod
     def backward(ctx, dy):
         x, w = ctx.saved_tensors
-        N, D, H, W, Cin, Cout, k, stride, pad, ldx, has_b = ctx.geom
+        g, ldx, has_b = ctx.geom
         dy, lddy = cl_view(_like(dy, x), "conv3d grad")
         L = lib()
-        ws = workspace(_conv_ws(L, x, N, D, H, W, Cin, Cout, k, stride, pad), x.device)
+        ws = workspace(g.ws_bytes(L, x.dtype), x.device)
         dx = dw = db = None
         want_dw = ctx.needs_input_grad[1] or (has_b and ctx.needs_input_grad[2])
-        if ctx.amax is not None:
-            xa, wa = ctx.amax
-            da = _get_amax(dy)
-            if da is None and ctx.needs_input_grad[0] and want_dw:      # both gradients read dy: measure it once
-                da = _measure_amax(dy, lddy, N * D * H * W, Cout)
-            if ctx.needs_input_grad[0]:
-                dx = torch.empty((N, D, H, W, Cin), dtype=x.dtype, device=x.device)
-                L.call("mi355seg_conv3d_dgrad_ax_f32", _p(dy), lddy, _p(w), _p(dx), Cin, N, D, H, W, Cin, Cout, k, stride, pad,
-                       _p(da), _p(wa), _p(ws), ws.numel(), _stream())
-            if want_dw:
-                dw = torch.empty_like(w)
-                db = torch.empty(Cout, dtype=torch.float32, device=x.device) if has_b else None
-                L.call("mi355seg_conv3d_wgrad_ax_f32", _p(dy), lddy, _p(x), ldx, _p(dw), _p(db), N, D, H, W, Cin, Cout, k, stride, pad,
-                       0, _p(da), _p(xa), _p(ws), ws.numel(), _stream())
-            return dx, dw, db, None, None, None
+        xa, wa = ctx.amax or (None, None)
+        da = _get_amax(dy) if ctx.amax is not None else None
+        if ctx.amax is not None and da is None and ctx.needs_input_grad[0] and want_dw:      # both gradients read dy: measure it once
+            da = _measure_amax(dy, lddy, g.rows_out, g.Cout)
         if ctx.needs_input_grad[0]:
-            dx = torch.empty((N, D, H, W, Cin), dtype=x.dtype, device=x.device)
-            L.call("mi355seg_conv3d_dgrad_" + _sfx(x), _p(dy), lddy, _p(w), _p(dx), Cin, N, D, H, W, Cin, Cout, k, stride, pad,
-                   _p(ws), ws.numel(), _stream())
+            dx = torch.empty(x.shape, dtype=x.dtype, device=x.device)
+            _conv_dgrad(L, g, dy, lddy, w, dx, g.Cin, ws, da, wa)
         if want_dw:
             dw = torch.empty_like(w)
-            db = torch.empty(Cout, dtype=torch.float32, device=x.device) if has_b else None
-            L.call("mi355seg_conv3d_wgrad_" + _sfx(x), _p(dy), lddy, _p(x), ldx, _p(dw), _p(db), N, D, H, W, Cin, Cout, k, stride, pad,
-                   0, _p(ws), ws.numel(), _stream())
+            db = torch.empty(g.Cout, dtype=torch.float32, device=x.device) if has_b else None
+            _conv_wgrad(L, g, dy, lddy, x, ldx, dw, db, ws, da, xa)
         return dx, dw, db, None, None, (dy if ctx.has_res else None)        # d(conv + res) / d res = dy itself
 
 
@@ -560,9 +658,33 @@ def conv3d(x, weight, bias=None, stride=1, padding=0, residual=None):
     launch where the convolution's epilogue can take the sum, mi355seg_conv3d_fwd_res_bf16)."""
     if residual is None:
         return _Conv3d.apply(x, weight, bias, int(stride), int(padding))
-    if x.dtype == torch.bfloat16 and residual.dtype == torch.bfloat16 and not os.environ.get("MI355SEG_NO_RES_EPILOGUE"):
+    if x.dtype == torch.bfloat16 and residual.dtype == torch.bfloat16:
         return _Conv3d.apply(x, weight, bias, int(stride), int(padding), residual)
     return activation(_Conv3d.apply(x, weight, bias, int(stride), int(padding)), ACT_NONE, residual=residual)
+
+
+def _convt_k2s2_ws(L, x, Cout):
+    N, D, H, W, Cin = x.shape
+    return workspace(L.query("mi355seg_convt3d_k2s2_ws_bytes", N, D, H, W, Cin, Cout), x.device)
+
+
+def _convt_k2s2_bwd(L, x, ldx, dy, lddy, w, has_b, need_dx, need_dw):
+    """(dx, dw, db) of ConvTranspose3d k2 s2: x the layer's input, dy the gradient of its output -- possibly the left channel slice of a
+    wider gradient at pitch lddy; whatever is not needed (or does not exist: db without a bias) comes back as None."""
+    N, D, H, W, Cin = x.shape
+    Cout = w.shape[1]
+    ws = _convt_k2s2_ws(L, x, Cout)
+    dx = dw = db = None
+    if need_dx:
+        dx = torch.empty((N, D, H, W, Cin), dtype=x.dtype, device=x.device)
+        L.call("mi355seg_convt3d_k2s2_dgrad_" + _sfx(x), _p(dy), lddy, _p(w), _p(dx), Cin, N, D, H, W, Cin, Cout,
+               _p(ws), ws.numel(), _stream())
+    if need_dw:
+        dw = torch.empty_like(w)
+        db = torch.empty(Cout, dtype=torch.float32, device=x.device) if has_b else None
+        L.call("mi355seg_convt3d_k2s2_wgrad_" + _sfx(x), _p(dy), lddy, _p(x), ldx, _p(dw), _p(db), N, D, H, W, Cin, Cout,
+               _p(ws), ws.numel(), _stream())
+    return dx, dw, db
 
 
 class _ConvT3dK2S2(Function):
@@ -576,31 +698,20 @@ class _ConvT3dK2S2(Function):
         w = w.contiguous()
         y = torch.empty((N, 2 * D, 2 * H, 2 * W, Cout), dtype=x.dtype, device=x.device)
         L = lib()
-        ws = workspace(L.query("mi355seg_convt3d_k2s2_ws_bytes", N, D, H, W, Cin, Cout), x.device)
+        ws = _convt_k2s2_ws(L, x, Cout)
         L.call("mi355seg_convt3d_k2s2_fwd_" + _sfx(x), _p(x), ldx, _p(w), _p(b), _p(y), Cout, N, D, H, W, Cin, Cout,
                _p(ws), ws.numel(), _stream())
         ctx.save_for_backward(x, w)
-        ctx.geom = (N, D, H, W, Cin, Cout, ldx, b is not None)
+        ctx.geom = (ldx, b is not None)
         return y
 
     @staticmethod
     def backward(ctx, dy):
         x, w = ctx.saved_tensors
-        N, D, H, W, Cin, Cout, ldx, has_b = ctx.geom
+        ldx, has_b = ctx.geom
         dy, lddy = cl_view(_like(dy, x), "conv_transpose3d grad")
-        L = lib()
-        ws = workspace(L.query("mi355seg_convt3d_k2s2_ws_bytes", N, D, H, W, Cin, Cout), x.device)
-        dx = dw = db = None
-        if ctx.needs_input_grad[0]:
-            dx = torch.empty((N, D, H, W, Cin), dtype=x.dtype, device=x.device)
-            L.call("mi355seg_convt3d_k2s2_dgrad_" + _sfx(x), _p(dy), lddy, _p(w), _p(dx), Cin, N, D, H, W, Cin, Cout,
-                   _p(ws), ws.numel(), _stream())
-        if ctx.needs_input_grad[1] or (has_b and ctx.needs_input_grad[2]):
-            dw = torch.empty_like(w)
-            db = torch.empty(Cout, dtype=torch.float32, device=x.device) if has_b else None
-            L.call("mi355seg_convt3d_k2s2_wgrad_" + _sfx(x), _p(dy), lddy, _p(x), ldx, _p(dw), _p(db), N, D, H, W, Cin, Cout,
-                   _p(ws), ws.numel(), _stream())
-        return dx, dw, db
+        return _convt_k2s2_bwd(lib(), x, ldx, dy, lddy, w, has_b, ctx.needs_input_grad[0],
+                               ctx.needs_input_grad[1] or (has_b and ctx.needs_input_grad[2]))
 
 
 class _ConvT3dK2S2Cat(Function):
@@ -613,49 +724,34 @@ class _ConvT3dK2S2Cat(Function):
         x, ldx = cl_view(x, "conv_transpose3d input")
         N, D, H, W, Cin = x.shape
         Cout = w.shape[1]
-        base = skip._base
-        Cs = skip.shape[-1]
-        ok = (base is not None and base.dim() == 5 and base.is_contiguous() and tuple(base.shape[:4]) == (N, 2 * D, 2 * H, 2 * W)
-              and base.shape[-1] == Cout + Cs and skip.data_ptr() == base.data_ptr() + base.element_size() * Cout and skip.stride() == base.stride()
-              and base.dtype == x.dtype)
-        if not ok:
+        base = _concat_base(skip, Cout, (N, 2 * D, 2 * H, 2 * W), x.dtype)
+        if base is None:
             raise Mi355SegError("conv_transpose3d_k2s2_cat: `skip` is not the right channel slice of a matching concat buffer")
         w = w.contiguous()
         L = lib()
-        ws = workspace(L.query("mi355seg_convt3d_k2s2_ws_bytes", N, D, H, W, Cin, Cout), x.device)
+        ws = _convt_k2s2_ws(L, x, Cout)
         sa = _get_amax(skip) if _takes_amax(x) else None
         if sa is not None:
             # max |cat| = max(max |up-convolution| (from that kernel's epilogue), max |skip| (its own scalar, max-combined))
             ca = _amax_slot(x.device)
-            L.call("mi355seg_convt3d_k2s2_fwd_ax_f32", _p(x), ldx, _p(w), _p(b), _p(base), Cout + Cs, N, D, H, W, Cin, Cout, _p(ca),
+            L.call("mi355seg_convt3d_k2s2_fwd_ax_f32", _p(x), ldx, _p(w), _p(b), _p(base), base.shape[-1], N, D, H, W, Cin, Cout, _p(ca),
                    _p(ws), ws.numel(), _stream())
             _measure_amax(sa, 1, 1, 1, ca)
             _set_amax(base, ca)
         else:
-            L.call("mi355seg_convt3d_k2s2_fwd_" + _sfx(x), _p(x), ldx, _p(w), _p(b), _p(base), Cout + Cs, N, D, H, W, Cin, Cout,
+            L.call("mi355seg_convt3d_k2s2_fwd_" + _sfx(x), _p(x), ldx, _p(w), _p(b), _p(base), base.shape[-1], N, D, H, W, Cin, Cout,
                    _p(ws), ws.numel(), _stream())
         ctx.save_for_backward(x, w)
-        ctx.geom = (N, D, H, W, Cin, Cout, Cs, ldx, b is not None)
+        ctx.geom = (Cout, ldx, b is not None)
         return base
 
     @staticmethod
     def backward(ctx, dcat):
         x, w = ctx.saved_tensors
-        N, D, H, W, Cin, Cout, Cs, ldx, has_b = ctx.geom
+        Cout, ldx, has_b = ctx.geom
         dcat, ldd = cl_view(_like(dcat, x), "conv_transpose3d grad")
-        L = lib()
-        ws = workspace(L.query("mi355seg_convt3d_k2s2_ws_bytes", N, D, H, W, Cin, Cout), x.device)
-        dx = dw = db = None
-        if ctx.needs_input_grad[0]:
-            dx = torch.empty((N, D, H, W, Cin), dtype=x.dtype, device=x.device)
-            L.call("mi355seg_convt3d_k2s2_dgrad_" + _sfx(x), _p(dcat), ldd, _p(w), _p(dx), Cin, N, D, H, W, Cin, Cout,
-                   _p(ws), ws.numel(), _stream())
-        if ctx.needs_input_grad[1] or (has_b and ctx.needs_input_grad[2]):
-            dw = torch.empty_like(w)
-            db = torch.empty(Cout, dtype=torch.float32, device=x.device) if has_b else None
-            L.call("mi355seg_convt3d_k2s2_wgrad_" + _sfx(x), _p(dcat), ldd, _p(x), ldx, _p(dw), _p(db), N, D, H, W, Cin, Cout,
-                   _p(ws), ws.numel(), _stream())
-        return dx, dw, db, dcat[..., Cout:]
+        return _convt_k2s2_bwd(lib(), x, ldx, dcat, ldd, w, has_b, ctx.needs_input_grad[0],
+                               ctx.needs_input_grad[1] or (has_b and ctx.needs_input_grad[2])) + (dcat[..., Cout:],)
 
 
 def conv_transpose3d_k2s2_cat(x, weight, bias, skip):
@@ -676,37 +772,35 @@ class _ConvT3dAdjoint(Function):
             raise Mi355SegError(f"conv_transpose3d: weight {tuple(w.shape)} does not match input channels {Cin} / kernel {k}")
         w = w.contiguous()
         Cout = w.shape[1]
-        geom = (N, k * D, k * H, k * W, Cout, Cin, k, k, 0)             # the adjoint conv: Cout -> Cin channels, stride k
+        g = _ConvGeom(N, k * D, k * H, k * W, Cout, Cin, k, k, 0)             # the adjoint conv: Cout -> Cin channels, stride k
         y = torch.empty((N, k * D, k * H, k * W, Cout), dtype=x.dtype, device=x.device)
         L = lib()
-        ws = workspace(L.query("mi355seg_conv3d_ws_bytes", *geom), x.device)
-        L.call("mi355seg_conv3d_dgrad_f32", _p(x), ldx, _p(w), _p(y), Cout, *geom, _p(ws), ws.numel(), _stream())
+        ws = workspace(g.ws_bytes(L, x.dtype), x.device)
+        _conv_dgrad(L, g, x, ldx, w, y, Cout, ws)
         if b is not None:
             L.call("mi355seg_add_bias_f32", _p(y), Cout, _p(b), y.numel() // Cout, Cout, _stream())
         ctx.save_for_backward(x, w)
-        ctx.cfg = (geom, ldx, b is not None)
+        ctx.cfg = (g, ldx, b is not None)
         return y
 
     @staticmethod
     def backward(ctx, dy):
         x, w = ctx.saved_tensors
-        geom, ldx, has_b = ctx.cfg
-        N, D2, H2, W2, Cout, Cin, k = geom[:7]
+        g, ldx, has_b = ctx.cfg
         dy, lddy = cl_view(dy, "conv_transpose3d grad")
         L = lib()
-        ws = workspace(L.query("mi355seg_conv3d_ws_bytes", *geom), x.device)
+        ws = workspace(g.ws_bytes(L, x.dtype), x.device)
         dx = dw = db = None
         if ctx.needs_input_grad[0]:
             dx = torch.empty(x.shape, dtype=x.dtype, device=x.device)
-            L.call("mi355seg_conv3d_fwd_f32", _p(dy), lddy, _p(w), None, _p(dx), Cin, *geom, None, None, _p(ws), ws.numel(), _stream())
+            _conv_fwd(L, g, dy, lddy, w, None, dx, g.Cout, ws)
         if ctx.needs_input_grad[1]:
             dw = torch.empty_like(w)
-            L.call("mi355seg_conv3d_wgrad_f32", _p(x), ldx, _p(dy), lddy, _p(dw), None, *geom, 0, _p(ws), ws.numel(), _stream())
+            _conv_wgrad(L, g, x, ldx, dy, lddy, dw, None, ws)
         if has_b and ctx.needs_input_grad[2]:
-            rows = N * D2 * H2 * W2
-            cws = workspace(L.query("mi355seg_norm_ws_bytes", rows, 1, Cout), x.device)
-            db = torch.empty(Cout, dtype=x.dtype, device=x.device)
-            L.call("mi355seg_colsum_f32", _p(dy), lddy, rows, Cout, _p(db), _p(cws), cws.numel(), _stream())
+            cws = workspace(L.query("mi355seg_norm_ws_bytes", g.rows_in, 1, g.Cin), x.device)
+            db = torch.empty(g.Cin, dtype=x.dtype, device=x.device)
+            L.call("mi355seg_colsum_f32", _p(dy), lddy, g.rows_in, g.Cin, _p(db), _p(cws), cws.numel(), _stream())
         return dx, dw, db, None
 
 
@@ -805,89 +899,59 @@ class _ConvBnAct(Function):
         xa_in = _get_amax(x)
         x_arg = x
         x, ldx = cl_view(x, "conv3d input")
-        N, D, H, W, Cin = x.shape
-        Cout, k = w.shape[0], w.shape[2]
-        if w.shape[1] != Cin:
-            raise Mi355SegError(f"conv3d: weight {tuple(w.shape)} does not match input channels {Cin}")
-        w = w.contiguous()
-        Do, Ho, Wo = [(e + 2 * pad - k) // stride + 1 for e in (D, H, W)]
+        g, w = _conv_geom(x, w, stride, pad, "conv3d")
+        Cout, rows = g.Cout, g.rows_out
         dev = x.device
         L = lib()
-        ws = workspace(max(_conv_ws(L, x, N, D, H, W, Cin, Cout, k, stride, pad),
-                           L.query("mi355seg_norm_ws_bytes", N * Do * Ho * Wo, 1, Cout)), dev)
-        rows = N * Do * Ho * Wo
-        fused = (not training) and inference and x.data_ptr() % 16 == 0 and \
-            L.query("mi355seg_conv3d_fused_supported_" + _sfx(x), N, D, H, W, Cin, Cout, k, stride, pad, ldx, left_pad + Cout)
-        y = None if fused else torch.empty((N, Do, Ho, Wo, Cout), dtype=x.dtype, device=dev)
-        ax = training and _takes_amax(x)          # f16x3: operand maxima ride along (this layer's input, weights, and its output for the next layer)
-        ctx.amax = None
-        if ax:
-            sums = torch.empty(2 * Cout, dtype=torch.float64, device=dev)
-            use = _amax_use(x, N, D, H, W, Cin, Cout, k, stride, pad)
-            xa, wa = (xa_in if use else None), None
-            if use & 3:
-                wa = _weight_amax(w)
-            if xa is None and (use & 1) and (use & 4):
-                xa = _measure_amax(x, ldx, N * D * H * W, Cin)
-            L.call("mi355seg_conv3d_fwd_ax_f32", _p(x), ldx, _p(w), _p(b), _p(y), Cout, N, D, H, W, Cin, Cout, k, stride, pad,
-                   sums.data_ptr(), sums.data_ptr() + 8 * Cout, _p(xa), _p(wa), _p(ws), ws.numel(), _stream())
-            ctx.amax = (xa, wa)
-            mean = torch.empty(Cout, dtype=torch.float32, device=dev)
-            rstd = torch.empty(Cout, dtype=torch.float32, device=dev)
-            L.call("mi355seg_norm_stats_from_sums_f32", sums.data_ptr(), sums.data_ptr() + 8 * Cout, rows, Cout, eps,
-                   _p(mean), _p(rstd), _p(rmean), _p(rvar), momentum, _stream())
-        elif training:
-            sums = torch.empty(2 * Cout, dtype=torch.float64, device=dev)
-            L.call("mi355seg_conv3d_fwd_" + _sfx(x), _p(x), ldx, _p(w), _p(b), _p(y), Cout, N, D, H, W, Cin, Cout, k, stride, pad,
-                   sums.data_ptr(), sums.data_ptr() + 8 * Cout, _p(ws), ws.numel(), _stream())
-            mean = torch.empty(Cout, dtype=torch.float32, device=dev)
-            rstd = torch.empty(Cout, dtype=torch.float32, device=dev)
-            L.call("mi355seg_norm_stats_from_sums_f32", sums.data_ptr(), sums.data_ptr() + 8 * Cout, rows, Cout, eps,
-                   _p(mean), _p(rstd), _p(rmean), _p(rvar), momentum, _stream())
-        elif fused:
+        ws = workspace(max(g.ws_bytes(L, x.dtype), L.query("mi355seg_norm_ws_bytes", rows, 1, Cout)), dev)
+        if (not training) and inference and x.data_ptr() % 16 == 0 and \
+                L.query("mi355seg_conv3d_fused_supported_" + _sfx(x), *g, ldx, left_pad + Cout):
             # inference (model.eval() under no_grad, predict.py:79-81,133): eval-mode BatchNorm folded into the packed weights and
             # the bias slot, the activation in the convolution's epilogue -- one pass, nothing saved for a backward
             fold = torch.empty(2 * Cout, dtype=torch.float32, device=dev)
             L.call("mi355seg_bn_fold_f32", _p(gamma), _p(beta), _p(rmean), _p(rvar), _p(b), eps, Cout, fold.data_ptr(), fold.data_ptr() + 4 * Cout, _stream())
-            full = torch.empty((N, Do, Ho, Wo, left_pad + Cout), dtype=x.dtype, device=dev)
+            full = torch.empty(g.out_shape[:4] + (left_pad + Cout,), dtype=x.dtype, device=dev)
             a = full[..., left_pad:] if left_pad else full
             L.call("mi355seg_conv3d_fwd_fused_" + _sfx(x), _p(x), ldx, _p(w), fold.data_ptr(), fold.data_ptr() + 4 * Cout, act, slope,
-                   a.data_ptr(), left_pad + Cout, N, D, H, W, Cin, Cout, k, stride, pad, _p(ws), ws.numel(), _stream())
+                   a.data_ptr(), left_pad + Cout, *g, _p(ws), ws.numel(), _stream())
             return a
+        y = torch.empty(g.out_shape, dtype=x.dtype, device=dev)
+        ax = training and _takes_amax(x)          # f16x3: operand maxima ride along (this layer's input, weights, and its output for the next layer)
+        ctx.amax = None
+        if training:
+            sums = torch.empty(2 * Cout, dtype=torch.float64, device=dev)
+            xa, wa = _operand_amax(g, x, ldx, w, xa_in, True) or (None, None)
+            _conv_fwd(L, g, x, ldx, w, b, y, Cout, ws, sums, xa, wa)
+            if xa is not None or wa is not None:      # (no member: the backward draws no slot for max |dy| either)
+                ctx.amax = (xa, wa)
+            mean, rstd = _stats_from_sums(L, sums, rows, Cout, eps, rmean, rvar, momentum)
         else:
-            L.call("mi355seg_conv3d_fwd_" + _sfx(x), _p(x), ldx, _p(w), _p(b), _p(y), Cout, N, D, H, W, Cin, Cout, k, stride, pad,
-                   None, None, _p(ws), ws.numel(), _stream())
+            _conv_fwd(L, g, x, ldx, w, b, y, Cout, ws)
             mean = rmean
             rstd = torch.empty(Cout, dtype=torch.float32, device=dev)
             L.call("mi355seg_rstd_from_var_f32", _p(rvar), eps, _p(rstd), Cout, _stream())
         lda = left_pad + Cout
         ctx.cat = 0
         if cat_right is not None:
-            base = cat_right._base
-            Cs = cat_right.shape[-1]
-            if not (base is not None and base.dim() == 5 and base.is_contiguous() and tuple(base.shape) == (N, Do, Ho, Wo, Cout + Cs) and base.dtype == x.dtype
-                    and cat_right.data_ptr() == base.data_ptr() + base.element_size() * Cout and cat_right.stride() == base.stride() and not left_pad):
+            full = None if left_pad else _concat_base(cat_right, Cout, g.out_shape[:4], x.dtype)
+            if full is None:
                 raise Mi355SegError("conv_bn_act: `cat_right` is not the right channel slice of a matching concat buffer")
-            full, a, lda = base, base[..., :Cout], Cout + Cs
-            ctx.cat = Cs
+            a, lda = full[..., :Cout], full.shape[-1]
+            ctx.cat = lda - Cout
         elif left_pad:
             # the activation lands in the RIGHT channel slice of a wider buffer whose left `left_pad` channels a later
             # up-convolution fills (conv_transpose3d_k2s2_cat): the skip concatenation then costs no copy
-            full = torch.empty((N, Do, Ho, Wo, left_pad + Cout), dtype=x.dtype, device=dev)
+            full = torch.empty(g.out_shape[:4] + (left_pad + Cout,), dtype=x.dtype, device=dev)
             a = full[..., left_pad:]
         else:
             a = torch.empty_like(y)
-        if ax:
-            aa = _amax_slot(dev)
-            L.call("mi355seg_norm_act_fwd_ax_f32", _p(y), Cout, _p(mean), _p(rstd), _p(gamma), _p(beta), None, 0,
-                   a.data_ptr(), lda, rows, 1, Cout, act, slope, _p(aa), _stream())
-            if not ctx.cat:
-                _set_amax(a, aa)
-        else:
-            L.call("mi355seg_norm_act_fwd_" + _sfx(x), _p(y), Cout, _p(mean), _p(rstd), _p(gamma), _p(beta), None, 0,
-                   a.data_ptr(), lda, rows, 1, Cout, act, slope, _stream())
+        aa = _amax_slot(dev) if ax else None
+        L.call("mi355seg_norm_act_fwd_ax_" + _sfx(x), _p(y), Cout, _p(mean), _p(rstd), _p(gamma), _p(beta), None, 0,
+               a.data_ptr(), lda, rows, 1, Cout, act, slope, _p(aa), _stream())
+        if not ctx.cat:
+            _set_amax(a, aa)
         ctx.save_for_backward(x, w, y, mean, rstd, gamma, beta)
-        ctx.cfg = (N, D, H, W, Cin, Cout, k, stride, pad, ldx, b is not None, rows, act, slope, bool(training))
+        ctx.cfg = (g, ldx, b is not None, act, slope, bool(training))
         if fork:
             ctx.set_materialize_grads(False)
             return a, x_arg.view_as(x_arg)
@@ -898,7 +962,8 @@ class _ConvBnAct(Function):
     @staticmethod
     def backward(ctx, da, dpass=None):
         x, w, y, mean, rstd, gamma, beta = ctx.saved_tensors
-        N, D, H, W, Cin, Cout, k, stride, pad, ldx, has_b, rows, act, slope, training = ctx.cfg
+        g, ldx, has_b, act, slope, training = ctx.cfg
+        Cin, Cout, rows = g.Cin, g.Cout, g.rows_out
         if not training:
             raise Mi355SegError("backward through eval-mode BatchNorm (running statistics) is not supported")
         if da is None:                       # (fork, only the pass-through was used)
@@ -912,50 +977,28 @@ class _ConvBnAct(Function):
         da, ldda = cl_view(_like(da, x), "conv+norm grad")
         L = lib()
         dev = x.device
-        ws = workspace(max(_conv_ws(L, x, N, D, H, W, Cin, Cout, k, stride, pad),
-                           L.query("mi355seg_norm_ws_bytes", rows, 1, Cout)), dev)
+        ws = workspace(max(g.ws_bytes(L, x.dtype), L.query("mi355seg_norm_ws_bytes", rows, 1, Cout)), dev)
         dy = torch.empty_like(y)
         dgamma = torch.empty(Cout, dtype=torch.float32, device=dev) if gamma is not None else None      # no affine: instance norm
         dbeta = torch.empty(Cout, dtype=torch.float32, device=dev) if gamma is not None else None
         db = torch.empty(Cout, dtype=torch.float32, device=dev) if has_b else None
-        if ctx.amax is not None and (ctx.amax[0] is not None or ctx.amax[1] is not None):
-            xa, wa = ctx.amax
-            dya = _amax_slot(dev)
-            L.call("mi355seg_norm_act_bwd_colsum_ax_f32", _p(da), ldda, _p(y), Cout, _p(mean), _p(rstd), _p(gamma), _p(beta), None, 0,
-                   _p(dy), Cout, _p(dgamma), _p(dbeta), None, 0, _p(db), _p(dya), rows, 1, Cout, act, slope, _p(ws), ws.numel(), _stream())
-            dx = dw = None
-            if ctx.needs_input_grad[0]:
-                dx = torch.empty((N, D, H, W, Cin), dtype=x.dtype, device=dev)
-                L.call("mi355seg_conv3d_dgrad_ax_f32", _p(dy), Cout, _p(w), _p(dx), Cin, N, D, H, W, Cin, Cout, k, stride, pad,
-                       _p(dya), _p(wa), _p(ws), ws.numel(), _stream())
-                if dpass is not None:
-                    L.call("mi355seg_act_fwd_f32", _p(dx), Cin, _p(dpass), lddp, _p(dx), Cin, N * D * H * W, Cin, ACT_NONE, 0.0, _stream())
-            elif dpass is not None:
-                dx = dpass
-            if ctx.needs_input_grad[1]:
-                dw = torch.empty_like(w)
-                L.call("mi355seg_conv3d_wgrad_ax_f32", _p(dy), Cout, _p(x), ldx, _p(dw), None, N, D, H, W, Cin, Cout, k, stride, pad,
-                       0, _p(dya), _p(xa), _p(ws), ws.numel(), _stream())
-            return dx, dw, db, dgamma, dbeta, None, None, None, None, None, None, None, None, None, None, None, None, dcat
-        L.call("mi355seg_norm_act_bwd_colsum_" + _sfx(x), _p(da), ldda, _p(y), Cout, _p(mean), _p(rstd), _p(gamma), _p(beta), None, 0,
-               _p(dy), Cout, _p(dgamma), _p(dbeta), None, 0, _p(db), rows, 1, Cout, act, slope, _p(ws), ws.numel(), _stream())
+        xa, wa = ctx.amax or (None, None)
+        dya = _amax_slot(dev) if ctx.amax is not None else None       # f16x3: max |dy| from the kernel that writes dy
+        L.call("mi355seg_norm_act_bwd_colsum_ax_" + _sfx(x), _p(da), ldda, _p(y), Cout, _p(mean), _p(rstd), _p(gamma), _p(beta), None, 0,
+               _p(dy), Cout, _p(dgamma), _p(dbeta), None, 0, _p(db), _p(dya), rows, 1, Cout, act, slope, _p(ws), ws.numel(), _stream())
         dx = dw = None
         if ctx.needs_input_grad[0]:
-            dx = torch.empty((N, D, H, W, Cin), dtype=x.dtype, device=dev)
-            if dpass is not None and x.dtype == torch.bfloat16:       # input gradient + the pass-through's gradient: the sum in the kernel's epilogue
-                L.call("mi355seg_conv3d_dgrad_res_bf16", _p(dy), Cout, _p(w), _p(dpass), lddp, _p(dx), Cin, N, D, H, W, Cin, Cout, k, stride, pad,
-                       _p(ws), ws.numel(), _stream())
-            else:
-                L.call("mi355seg_conv3d_dgrad_" + _sfx(x), _p(dy), Cout, _p(w), _p(dx), Cin, N, D, H, W, Cin, Cout, k, stride, pad,
-                       _p(ws), ws.numel(), _stream())
-                if dpass is not None:
-                    L.call("mi355seg_act_fwd_" + _sfx(x), _p(dx), Cin, _p(dpass), lddp, _p(dx), Cin, N * D * H * W, Cin, ACT_NONE, 0.0, _stream())
+            dx = torch.empty(x.shape, dtype=x.dtype, device=dev)
+            # input gradient + the pass-through's gradient: bf16 sums in the kernel's epilogue, fp32 by an add of its own
+            res = (dpass, lddp) if dpass is not None and x.dtype == torch.bfloat16 else None
+            _conv_dgrad(L, g, dy, Cout, w, dx, Cin, ws, dya, wa, res)
+            if dpass is not None and res is None:
+                L.call("mi355seg_act_fwd_" + _sfx(x), _p(dx), Cin, _p(dpass), lddp, _p(dx), Cin, g.rows_in, Cin, ACT_NONE, 0.0, _stream())
         elif dpass is not None:
             dx = dpass
         if ctx.needs_input_grad[1]:
             dw = torch.empty_like(w)
-            L.call("mi355seg_conv3d_wgrad_" + _sfx(x), _p(dy), Cout, _p(x), ldx, _p(dw), None, N, D, H, W, Cin, Cout, k, stride, pad,
-                   0, _p(ws), ws.numel(), _stream())
+            _conv_wgrad(L, g, dy, Cout, x, ldx, dw, None, ws, dya, xa)
         return dx, dw, db, dgamma, dbeta, None, None, None, None, None, None, None, None, None, None, None, None, dcat
 
 
@@ -965,18 +1008,14 @@ def conv_in_act(x, conv, norm, act=ACT_NONE, slope=0.01, cat_right=None):
     statistics over the whole tensor, i.e. exactly what the convolution's epilogue already reduces for BatchNorm: the node of
     conv_bn_act without affine parameters and buffers (no separate statistics pass over y).  N > 1: convolution, then the
     instance-norm node."""
-    if x.shape[0] != 1 or norm.affine or norm.track_running_stats or not torch.is_grad_enabled():
+    g = _module_geom(x, conv, "conv_in_act")
+    if g.N != 1 or norm.affine or norm.track_running_stats or not torch.is_grad_enabled():
         a = norm.forward_act(conv(x), act, slope)
         return a if cat_right is None else cat_channels(a, cat_right)
-    stride = conv.stride[0] if isinstance(conv.stride, (tuple, list)) else conv.stride
-    pad = conv.padding[0] if isinstance(conv.padding, (tuple, list)) else conv.padding
     # cat_right: cat((result, cat_right), channels) -- written in place when cat_right is the right slice of a matching concat buffer
     # (instance_norm_act / activation_fork(..., left_pad=)), by two slice copies otherwise
-    base = getattr(cat_right, "_base", None) if cat_right is not None else None
-    inplace = base is not None and base.dim() == 5 and base.is_contiguous() and base.shape[-1] == conv.out_channels + cat_right.shape[-1] and \
-        cat_right.dtype == x.dtype and cat_right.data_ptr() == base.data_ptr() + base.element_size() * conv.out_channels and \
-        cat_right.stride() == base.stride() and not os.environ.get("MI355SEG_NO_CAT_FUSION")
-    out = _ConvBnAct.apply(x, conv.weight, conv.bias, None, None, None, None, int(stride), int(pad), True, 0.0, float(norm.eps),
+    inplace = cat_right is not None and _concat_base(cat_right, g.Cout, g.out_shape[:4], x.dtype) is not None
+    out = _ConvBnAct.apply(x, conv.weight, conv.bias, None, None, None, None, g.stride, g.pad, True, 0.0, float(norm.eps),
                            int(act), float(slope), 0, False, False, cat_right if inplace else None)
     return out if (cat_right is None or inplace) else cat_channels(out, cat_right)
 
@@ -987,13 +1026,12 @@ def conv_bn_act(x, conv, bn, act=ACT_NONE, slope=0.01, left_pad=0, fork=False):
     adds the pass-through's gradient to the input gradient it computes instead of leaving the sum to autograd."""
     if bn.momentum is None or not bn.affine or not bn.track_running_stats:
         raise NotImplementedError("conv_bn_act: BatchNorm3d must be affine with running statistics and a momentum")
-    stride = conv.stride[0] if isinstance(conv.stride, (tuple, list)) else conv.stride
-    pad = conv.padding[0] if isinstance(conv.padding, (tuple, list)) else conv.padding
+    stride, pad = _module_stride_pad(conv, "conv_bn_act")         # (checked before the counter moves: a refused call changes nothing)
     if bn.training:
         bump_counter(bn)
     # eval mode under torch.no_grad() (predict.py:79-81,133) takes the folded one-pass form where the layer has one
     forked = bool(fork) and bn.training and torch.is_grad_enabled()
-    out = _ConvBnAct.apply(x, conv.weight, conv.bias, bn.weight, bn.bias, bn.running_mean, bn.running_var, int(stride), int(pad),
+    out = _ConvBnAct.apply(x, conv.weight, conv.bias, bn.weight, bn.bias, bn.running_mean, bn.running_var, stride, pad,
                            bool(bn.training), float(bn.momentum), float(bn.eps), int(act), float(slope), int(left_pad),
                            not torch.is_grad_enabled(), forked)
     return (out, x) if (fork and not forked) else out
@@ -1017,31 +1055,21 @@ class _DoubleConvBnAct(Function):
         x, ldx = cl_view(x, "conv3d input")
         L = lib()
         dev = x.device
-        N = x.shape[0]
         ax = _takes_amax(x)           # f16x3: operand maxima ride along
+        cg1, w1 = _conv_geom(x, w1, *geo1, "conv3d")
+        cg2, w2 = _conv_geom(cg1.out_shape, w2, *geo2, "conv3d")
 
-        def layer(inp, ldin, w, b, g, be, rm, rv, geo, mom, eps, lp, xa, head=None, pool=False, fold=False, pro=None):
+        def layer(g, inp, ldin, w, b, gm, be, rm, rv, mom, eps, lp, xa, head=None, pool=False, fold=False, pro=None):
             """conv + batch statistics + (norm + activation).  fold: the norm + activation is NOT applied -- the layer hands back its
             folded form (al, be) and a bound on the activation's maximum for the next convolution's prologue; pro = (al, be): this
             convolution's input is the previous layer's RAW output, normalised + activated while its tiles are staged."""
-            D, H, W, Cin = inp.shape[1:]
-            Cout, k = w.shape[0], w.shape[2]
-            stride, pad = geo
-            if w.shape[1] != Cin:
-                raise Mi355SegError(f"conv3d: weight {tuple(w.shape)} does not match input channels {Cin}")
-            Do, Ho, Wo = [(e + 2 * pad - k) // stride + 1 for e in (D, H, W)]
-            rows = N * Do * Ho * Wo
-            ws = workspace(max(_conv_ws(L, inp, N, D, H, W, Cin, Cout, k, stride, pad), L.query("mi355seg_norm_ws_bytes", rows, 1, Cout)), dev)
-            y = torch.empty((N, Do, Ho, Wo, Cout), dtype=inp.dtype, device=dev)
+            N, Do, Ho, Wo, Cout = g.out_shape
+            rows = g.rows_out
+            ws = workspace(max(g.ws_bytes(L, inp.dtype), L.query("mi355seg_norm_ws_bytes", rows, 1, Cout)), dev)
+            y = torch.empty(g.out_shape, dtype=inp.dtype, device=dev)
             sums = torch.empty(2 * Cout, dtype=torch.float64, device=dev)
-            wa = aa = None
-            use = _amax_use(inp, N, D, H, W, Cin, Cout, k, stride, pad) if ax else 0
-            if use & 3:
-                wa = _weight_amax(w)
-            if not use:
-                xa = None
-            elif xa is None and (use & 1) and (use & 4):
-                xa = _measure_amax(inp, ldin, N * D * H * W, Cin)
+            aa = None
+            xa, wa = _operand_amax(g, inp, ldin, w, xa, True) or (None, None)
             ya = _amax_slot(dev) if fold else None
             if _CHECK_AMAX:
                 _assert_amax(w, wa, "conv weights")
@@ -1051,30 +1079,28 @@ class _DoubleConvBnAct(Function):
                 elif xa is not None:
                     _assert_amax(inp, xa, "conv input")
             if pro is not None:
-                L.call("mi355seg_conv3d_fwd_pro_ax_f32", _p(inp), ldin, _p(pro[0]), _p(pro[1]), act, slope, _p(w), _p(b), _p(y), Cout, N, D, H, W, Cin, Cout,
-                       k, stride, pad, sums.data_ptr(), sums.data_ptr() + 8 * Cout, _p(xa), _p(wa), _p(ws), ws.numel(), _stream())
+                L.call("mi355seg_conv3d_fwd_pro_ax_f32", _p(inp), ldin, _p(pro[0]), _p(pro[1]), act, slope, _p(w), _p(b), _p(y), Cout, *g,
+                       *_sums_ptrs(sums, Cout), _p(xa), _p(wa), _p(ws), ws.numel(), _stream())
             elif fold:
-                L.call("mi355seg_conv3d_fwd_yamax_ax_f32", _p(inp), ldin, _p(w), _p(b), _p(y), Cout, N, D, H, W, Cin, Cout, k, stride, pad,
-                       sums.data_ptr(), sums.data_ptr() + 8 * Cout, _p(xa), _p(wa), _p(ya), _p(ws), ws.numel(), _stream())
+                L.call("mi355seg_conv3d_fwd_yamax_ax_f32", _p(inp), ldin, _p(w), _p(b), _p(y), Cout, *g,
+                       *_sums_ptrs(sums, Cout), _p(xa), _p(wa), _p(ya), _p(ws), ws.numel(), _stream())
             else:
-                L.call("mi355seg_conv3d_fwd_ax_f32", _p(inp), ldin, _p(w), _p(b), _p(y), Cout, N, D, H, W, Cin, Cout, k, stride, pad,
-                       sums.data_ptr(), sums.data_ptr() + 8 * Cout, _p(xa), _p(wa), _p(ws), ws.numel(), _stream())
-            mean = torch.empty(Cout, dtype=torch.float32, device=dev)
-            rstd = torch.empty(Cout, dtype=torch.float32, device=dev)
-            cfg = (N, D, H, W, Cin, Cout, k, stride, pad, ldin, b is not None, rows)
+                _conv_fwd(L, g, inp, ldin, w, b, y, Cout, ws, sums, xa, wa)
+            cfg = (g, ldin, b is not None)
             if fold:                         # statistics + folded normalisation + the bound of the activation's maximum: one small launch
+                mean = torch.empty(Cout, dtype=torch.float32, device=dev)
+                rstd = torch.empty(Cout, dtype=torch.float32, device=dev)
                 alb = torch.empty(2 * Cout, dtype=torch.float32, device=dev)
                 aa = _amax_slot(dev)
-                L.call("mi355seg_norm_fold_f32", sums.data_ptr(), sums.data_ptr() + 8 * Cout, rows, Cout, eps, _p(g), _p(be), act,
+                L.call("mi355seg_norm_fold_f32", *_sums_ptrs(sums, Cout), rows, Cout, eps, _p(gm), _p(be), act,
                        _p(mean), _p(rstd), _p(rm), _p(rv), mom, _p(ya), alb.data_ptr(), alb.data_ptr() + 4 * Cout, _p(aa), _stream())
                 return y, mean, rstd, (alb[:Cout], alb[Cout:]), cfg, (xa, wa, aa)
-            L.call("mi355seg_norm_stats_from_sums_f32", sums.data_ptr(), sums.data_ptr() + 8 * Cout, rows, Cout, eps,
-                   _p(mean), _p(rstd), _p(rm), _p(rv), mom, _stream())
+            mean, rstd = _stats_from_sums(L, sums, rows, Cout, eps, rm, rv, mom)
             if head is not None:             # norm + activation + 1x1x1 head: logits, no activation tensor
                 hw, hb = head
                 K = hw.shape[0]
                 lg = torch.empty((N, Do, Ho, Wo, K), dtype=inp.dtype, device=dev)
-                L.call("mi355seg_bn_act_head_fwd_f32", _p(y), Cout, _p(mean), _p(rstd), _p(g), _p(be), act, slope, _p(hw), _p(hb),
+                L.call("mi355seg_bn_act_head_fwd_f32", _p(y), Cout, _p(mean), _p(rstd), _p(gm), _p(be), act, slope, _p(hw), _p(hb),
                        _p(lg), K, rows, Cout, K, _stream())
                 return y, mean, rstd, lg, cfg, (xa, wa, None)
             full = torch.empty((N, Do, Ho, Wo, lp + Cout), dtype=inp.dtype, device=dev)
@@ -1084,31 +1110,27 @@ class _DoubleConvBnAct(Function):
             if pool:                         # norm + activation + MaxPool3d(2, 2): the skip tensor, the pooled tensor and the argmax codes
                 pd = torch.empty((N, Do // 2, Ho // 2, Wo // 2, Cout), dtype=inp.dtype, device=dev)
                 idx = torch.empty((N, Do // 2, Ho // 2, Wo // 2, Cout), dtype=torch.uint8, device=dev)
-                L.call("mi355seg_bn_act_pool_fwd_f32", _p(y), Cout, _p(mean), _p(rstd), _p(g), _p(be), act, slope, a.data_ptr(), lp + Cout,
+                L.call("mi355seg_bn_act_pool_fwd_f32", _p(y), Cout, _p(mean), _p(rstd), _p(gm), _p(be), act, slope, a.data_ptr(), lp + Cout,
                        _p(pd), _p(idx), _p(aa), N, Do, Ho, Wo, Cout, _stream())
                 return y, mean, rstd, (a, pd, idx), cfg, (xa, wa, aa)
-            L.call("mi355seg_norm_act_fwd_ax_f32", _p(y), Cout, _p(mean), _p(rstd), _p(g), _p(be), None, 0,
+            L.call("mi355seg_norm_act_fwd_ax_f32", _p(y), Cout, _p(mean), _p(rstd), _p(gm), _p(be), None, 0,
                    a.data_ptr(), lp + Cout, rows, 1, Cout, act, slope, _p(aa), _stream())
             return y, mean, rstd, a, cfg, (xa, wa, aa)
 
-        w1, w2 = w1.contiguous(), w2.contiguous()
         head = None
         if wh is not None:
             wh = wh.contiguous()
             head = (wh, bh)
         # norm1 + activation as a PROLOGUE of conv2 (its forward and its weight gradient read conv1's raw output): where both run the
         # f16x3 kernels the activation between the two convolutions is never written (mi355seg_conv3d_fwd_pro_ax_f32)
-        C1, k1_, (s1_, p1_) = w1.shape[0], w1.shape[2], geo1
-        e1 = [(e + 2 * p1_ - k1_) // s1_ + 1 for e in x.shape[1:4]]
-        fuse1 = ax and not os.environ.get("MI355SEG_NO_PRO_FUSION") and \
-            L.query("mi355seg_conv3d_pro_supported_f32", N, e1[0], e1[1], e1[2], C1, w2.shape[0], w2.shape[2], geo2[0], geo2[1], act) != 0
-        y1, mean1, rstd1, a1, cfg1, am1 = layer(x, ldx, w1, b1, g1, be1, rm1, rv1, geo1, mom1, eps1, 0, xa_in, fold=fuse1)
+        fuse1 = ax and not os.environ.get("MI355SEG_NO_PRO_FUSION") and L.query("mi355seg_conv3d_pro_supported_f32", *cg2, act) != 0
+        y1, mean1, rstd1, a1, cfg1, am1 = layer(cg1, x, ldx, w1, b1, g1, be1, rm1, rv1, mom1, eps1, 0, xa_in, fold=fuse1)
         pro1 = None
         if fuse1:
             pro1, a1 = a1, None
-            y2, mean2, rstd2, a2, cfg2, am2 = layer(y1, C1, w2, b2, g2, be2, rm2, rv2, geo2, mom2, eps2, left_pad, am1[2], head, pool, pro=pro1)
+            y2, mean2, rstd2, a2, cfg2, am2 = layer(cg2, y1, cg1.Cout, w2, b2, g2, be2, rm2, rv2, mom2, eps2, left_pad, am1[2], head, pool, pro=pro1)
         else:
-            y2, mean2, rstd2, a2, cfg2, am2 = layer(a1, a1.shape[-1], w2, b2, g2, be2, rm2, rv2, geo2, mom2, eps2, left_pad, am1[2], head, pool)
+            y2, mean2, rstd2, a2, cfg2, am2 = layer(cg2, a1, a1.shape[-1], w2, b2, g2, be2, rm2, rv2, mom2, eps2, left_pad, am1[2], head, pool)
         idx = None
         if pool:
             a2, pd, idx = a2
@@ -1127,14 +1149,15 @@ class _DoubleConvBnAct(Function):
     @staticmethod
     def backward(ctx, da2, dskip=None):
         x, w1, y1, mean1, rstd1, g1, be1, a1, w2, y2, mean2, rstd2, g2, be2, wh, idx, al1, bl1 = ctx.saved_tensors
-        cfg1, cfg2, act, slope = ctx.cfg
-        N, D1, H1, W1, Cin1, C1, k1, st1, pd1, ldx, has_b1, rows1 = cfg1
-        _, D2, H2, W2, _, C2, k2, st2, pd2, lda1, has_b2, rows2 = cfg2
+        (cg1, ldx, has_b1), (cg2, lda1, has_b2), act, slope = ctx.cfg
+        N, D1, H1, W1, Cin1, C1 = cg1.args[:6]
+        _, D2, H2, W2, _, C2 = cg2.args[:6]
+        rows1, rows2 = cg1.rows_out, cg2.rows_out
         L = lib()
         dev = x.device
         if da2 is not None:
             da2, ldda2 = cl_view(_like(da2, x), "conv+norm grad")
-        ws = workspace(max(_conv_ws(L, x, N, D1, H1, W1, Cin1, C1, k1, st1, pd1), _conv_ws(L, y1, N, D2, H2, W2, C1, C2, k2, st2, pd2),
+        ws = workspace(max(cg1.ws_bytes(L, x.dtype), cg2.ws_bytes(L, y1.dtype),
                            L.query("mi355seg_norm_ws_bytes", rows1, 1, C1), L.query("mi355seg_norm_ws_bytes", rows2, 1, C2),
                            L.query("mi355seg_bn_act_head_ws_bytes", C2, wh.shape[0]) if wh is not None else 0,
                            L.query("mi355seg_bn_act_pool_ws_bytes", C2) if idx is not None else 0), dev)
@@ -1178,8 +1201,7 @@ class _DoubleConvBnAct(Function):
         da1 = torch.empty((N, D2, H2, W2, C1), dtype=x.dtype, device=dev)
         s12 = torch.empty(2 * C1, **f32)
         dg1, dbe1 = torch.empty(C1, **f32), torch.empty(C1, **f32)
-        L.call("mi355seg_conv3d_dgrad_bnsums_ax_f32", _p(dy2), C2, _p(w2), _p(da1), C1, N, D2, H2, W2, C1, C2, k2, st2, pd2,
-               _p(y1), C1, _p(mean1), _p(rstd1), _p(g1), _p(be1), act, slope, s12.data_ptr(), s12.data_ptr() + 4 * C1, _p(dg1), _p(dbe1),
+        L.call("mi355seg_conv3d_dgrad_bnsums_ax_f32", _p(dy2), C2, _p(w2), _p(da1), C1, *cg2, _p(y1), C1, _p(mean1), _p(rstd1), _p(g1), _p(be1), act, slope, s12.data_ptr(), s12.data_ptr() + 4 * C1, _p(dg1), _p(dbe1),
                _p(dya2), _p(wa2), _p(ws), ws.numel(), _stream())
         dw2 = torch.empty_like(w2)
         if al1 is not None:                  # conv2 read conv1's raw output through the norm + activation prologue: so does its weight gradient
@@ -1187,24 +1209,22 @@ class _DoubleConvBnAct(Function):
             if now != ctx.math:
                 L.call("mi355seg_set_conv_math", ctx.math)
             try:
-                L.call("mi355seg_conv3d_wgrad_pro_ax_f32", _p(dy2), C2, _p(y1), C1, _p(al1), _p(bl1), act, slope, _p(dw2), None,
-                       N, D2, H2, W2, C1, C2, k2, st2, pd2, 0, _p(dya2), _p(xa2), _p(ws), ws.numel(), _stream())
+                L.call("mi355seg_conv3d_wgrad_pro_ax_f32", _p(dy2), C2, _p(y1), C1, _p(al1), _p(bl1), act, slope, _p(dw2), None, *cg2,
+                       0, _p(dya2), _p(xa2), _p(ws), ws.numel(), _stream())
             finally:
                 if now != ctx.math:
                     L.call("mi355seg_set_conv_math", now)
         else:
-            L.call("mi355seg_conv3d_wgrad_ax_f32", _p(dy2), C2, _p(a1), lda1, _p(dw2), None, N, D2, H2, W2, C1, C2, k2, st2, pd2,
-                   0, _p(dya2), _p(xa2), _p(ws), ws.numel(), _stream())
+            _conv_wgrad(L, cg2, dy2, C2, a1, lda1, dw2, None, ws, dya2, xa2)
         del dy2
         # the 1-channel stem whose input needs no gradient (enc1conv1, unet3d.py:80-89): d(conv1 output) has ONE consumer, the stem's weight
         # gradient, which forms it from d(act1) and y1 on the fly -- the apply pass and the 537-MB tensor it writes are gone
-        if not ctx.needs_input_grad[0] and ctx.needs_input_grad[1] and Cin1 == 1 and not os.environ.get("MI355SEG_NO_STEM_FUSION") and \
-                L.query("mi355seg_stem_wgrad_bnbwd_supported_f32", N, D1, H1, W1, Cin1, C1, k1, st1, pd1) != 0:
+        if not ctx.needs_input_grad[0] and ctx.needs_input_grad[1] and Cin1 == 1 and \
+                L.query("mi355seg_stem_wgrad_bnbwd_supported_f32", *cg1) != 0:
             dw1 = torch.empty_like(w1)
             db1 = torch.empty(C1, **f32) if has_b1 else None
             L.call("mi355seg_stem_wgrad_bnbwd_f32", _p(da1), C1, _p(y1), C1, _p(mean1), _p(rstd1), _p(g1), _p(be1), act, slope,
-                   s12.data_ptr(), s12.data_ptr() + 4 * C1, _p(x), ldx, _p(dw1), _p(db1), N, D1, H1, W1, Cin1, C1, k1, st1, pd1,
-                   _p(ws), ws.numel(), _stream())
+                   s12.data_ptr(), s12.data_ptr() + 4 * C1, _p(x), ldx, _p(dw1), _p(db1), *cg1, _p(ws), ws.numel(), _stream())
             return (None, dw1, db1, dg1, dbe1, None, None, dw2, db2, dg2, dbe2, None, None) + (None,) * 9 + (dwh, dbh, None)
         # layer 1: the apply half of the norm backward (+ conv1's bias gradient), then conv1's gradients
         dy1 = torch.empty_like(y1)
@@ -1215,12 +1235,10 @@ class _DoubleConvBnAct(Function):
         dx = dw1 = None
         if ctx.needs_input_grad[0]:
             dx = torch.empty((N, D1, H1, W1, Cin1), dtype=x.dtype, device=dev)
-            L.call("mi355seg_conv3d_dgrad_ax_f32", _p(dy1), C1, _p(w1), _p(dx), Cin1, N, D1, H1, W1, Cin1, C1, k1, st1, pd1,
-                   _p(dya1), _p(wa1), _p(ws), ws.numel(), _stream())
+            _conv_dgrad(L, cg1, dy1, C1, w1, dx, Cin1, ws, dya1, wa1)
         if ctx.needs_input_grad[1]:
             dw1 = torch.empty_like(w1)
-            L.call("mi355seg_conv3d_wgrad_ax_f32", _p(dy1), C1, _p(x), ldx, _p(dw1), None, N, D1, H1, W1, Cin1, C1, k1, st1, pd1,
-                   0, _p(dya1), _p(xa1), _p(ws), ws.numel(), _stream())
+            _conv_wgrad(L, cg1, dy1, C1, x, ldx, dw1, None, ws, dya1, xa1)
         return (dx, dw1, db1, dg1, dbe1, None, None, dw2, db2, dg2, dbe2, None, None) + (None,) * 9 + (dwh, dbh, None)
 
 
@@ -1228,6 +1246,8 @@ def double_conv_bn_act(x, conv1, bn1, conv2, bn2, act=ACT_NONE, slope=0.01, left
     """act(bn2(conv2(act(bn1(conv1(x)))))): training mode on fp32 tensors runs as one autograd node (_DoubleConvBnAct), everything
     else as two conv_bn_act layers.  ``head`` (a layers.Conv3d with kernel_size 1: the output head behind the LAST block,
     unet3d.py:46-48,71): the result is ``head(block(x))``; in the fused node norm2 + activation + head are one kernel."""
+    g1 = _module_geom(x, conv1, "double_conv_bn_act")           # (checked before a counter moves: a refused call changes nothing)
+    g2 = _module_geom(g1.out_shape, conv2, "double_conv_bn_act")
     fused = bn1.training and bn2.training and torch.is_grad_enabled() and compute_dtype() == torch.float32 and x.dtype == torch.float32
     for bn in (bn1, bn2):
         fused = fused and bn.momentum is not None and bn.affine and bn.track_running_stats
@@ -1240,36 +1260,25 @@ def double_conv_bn_act(x, conv1, bn1, conv2, bn2, act=ACT_NONE, slope=0.01, left
         return a if head is None else head(a)
     head_fused = False
     if head is not None:
-        hk = head.kernel_size[0] if isinstance(head.kernel_size, (tuple, list)) else head.kernel_size
-        hs = head.stride[0] if isinstance(head.stride, (tuple, list)) else head.stride
-        hp = head.padding[0] if isinstance(head.padding, (tuple, list)) else head.padding
+        hk, hs, hp = _iso(head.kernel_size, "kernel_size"), _iso(head.stride, "stride"), _iso(head.padding, "padding")
         head_fused = (hk, hs, hp) == (1, 1, 0) and head.groups == 1 and head.weight.dtype == torch.float32 and left_pad == 0 and \
-            head.in_channels == conv2.out_channels and not os.environ.get("MI355SEG_NO_HEAD_FUSION") and \
-            lib().query("mi355seg_bn_act_head_supported_f32", 1, conv2.out_channels, head.out_channels, conv2.out_channels) != 0
-
-    def geo(conv):
-        st = conv.stride[0] if isinstance(conv.stride, (tuple, list)) else conv.stride
-        pd = conv.padding[0] if isinstance(conv.padding, (tuple, list)) else conv.padding
-        return int(st), int(pd)
+            head.in_channels == g2.Cout and \
+            lib().query("mi355seg_bn_act_head_supported_f32", 1, g2.Cout, head.out_channels, g2.Cout) != 0
     bump_counter(bn1)
     bump_counter(bn2)
     args = (x, conv1.weight, conv1.bias, bn1.weight, bn1.bias, bn1.running_mean, bn1.running_var,
             conv2.weight, conv2.bias, bn2.weight, bn2.bias, bn2.running_mean, bn2.running_var,
-            geo(conv1), geo(conv2), float(bn1.momentum), float(bn1.eps), float(bn2.momentum), float(bn2.eps),
+            (g1.stride, g1.pad), (g2.stride, g2.pad), float(bn1.momentum), float(bn1.eps), float(bn2.momentum), float(bn2.eps),
             int(act), float(slope), int(left_pad))
     if head_fused:
         return _DoubleConvBnAct.apply(*args, head.weight, head.bias)
     if pool:
         # ``pool``: (max_pool3d_2x(block(x)), block(x)) -- in the fused node norm2 + activation + pooling are one kernel and the pool's
         # backward rides in the norm backward; geometry the fused kernels do not take (odd extents) pools separately
-        _, D, H, W, _ = x.shape if x.dim() == 5 else (0, 0, 0, 0, 0)
-        k2, (s2_, p2_) = conv2.weight.shape[2], geo(conv2)
-        k1, (s1_, p1_) = conv1.weight.shape[2], geo(conv1)
-        ext = [((e + 2 * p1_ - k1) // s1_ + 1 + 2 * p2_ - k2) // s2_ + 1 for e in (D, H, W)]
         # (the fused kernels address the skip slice -- full[..., left_pad:] -- and its gradient by 16-byte quads: left_pad and the buffer's
         # channel pitch must be multiples of four, else the separate pool node below takes the shape)
-        if not os.environ.get("MI355SEG_NO_POOL_FUSION") and left_pad % 4 == 0 and (left_pad + conv2.out_channels) % 4 == 0 and \
-                lib().query("mi355seg_bn_act_pool_supported_f32", int(x.shape[0]), ext[0], ext[1], ext[2], conv2.out_channels, conv2.out_channels) != 0:
+        if left_pad % 4 == 0 and (left_pad + g2.Cout) % 4 == 0 and \
+                lib().query("mi355seg_bn_act_pool_supported_f32", *g2.out_shape, g2.Cout) != 0:
             return _DoubleConvBnAct.apply(*args, None, None, True)
         return max_pool3d_2x_and_skip(_DoubleConvBnAct.apply(*args))
     a = _DoubleConvBnAct.apply(*args)

@@ -6,16 +6,9 @@ import torch
 import torch.nn as nn
 
 from . import functional as F
+from .functional import _iso
 
 _ACT_OF = {nn.ReLU: (F.ACT_RELU, 0.0), nn.ELU: (F.ACT_ELU, 1.0), nn.LeakyReLU: (F.ACT_LRELU, 0.01)}
-
-
-def _iso(v, what):
-    if isinstance(v, (tuple, list)):
-        if len(set(v)) != 1:
-            raise NotImplementedError(f"{what} must be isotropic, got {v}")
-        return int(v[0])
-    return int(v)
 
 
 class Conv3d(nn.Conv3d):
@@ -23,9 +16,7 @@ class Conv3d(nn.Conv3d):
 
     def forward(self, x, residual=None):
         """residual: conv(x) + residual in one launch where the kernel allows (functional.conv3d)."""
-        if self.groups != 1 or _iso(self.dilation, "dilation") != 1 or self.padding_mode != "zeros":
-            raise NotImplementedError("Conv3d: only groups=1, dilation=1, zero padding are implemented")
-        return F.conv3d(x, self.weight, self.bias, _iso(self.stride, "stride"), _iso(self.padding, "padding"), residual=residual)
+        return F.conv3d(x, self.weight, self.bias, *F._module_stride_pad(self, "Conv3d"), residual=residual)
 
 
 class ConvTranspose3d(nn.ConvTranspose3d):

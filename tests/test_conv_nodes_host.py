@@ -1,0 +1,66 @@
+"""Host logic around the convolution nodes of functional.py (no GPU, the library is never loaded): which Conv3d modules the fused
+entry points refuse, the concat-slot predicate, and the switches that are gone."""
+import os
+import re
+
+import pytest
+import torch
+
+import mi355seg
+from mi355seg import functional as F
+from mi355seg.layers import BatchNorm3d, Conv3d, InstanceNorm3d
+
+UNSUPPORTED = {"stride": dict(stride=(1, 2, 2)), "padding": dict(padding=(0, 1, 1)), "dilation": dict(dilation=2),
+               "groups": dict(groups=2), "padding_mode": dict(padding_mode="reflect")}
+
+
+@pytest.fixture
+def no_library(monkeypatch):
+    def refuse():
+        raise AssertionError("the library was asked for")
+    monkeypatch.setattr(F, "lib", refuse)
+
+
+@pytest.mark.parametrize("entry", ["conv_bn_act", "conv_in_act", "double_conv_bn_act_first", "double_conv_bn_act_second"])
+@pytest.mark.parametrize("what", sorted(UNSUPPORTED))
+def test_fused_entries_refuse_what_conv3d_refuses_before_touching_anything(no_library, entry, what):
+    """layers.Conv3d.forward raises NotImplementedError for these modules; so do the fused entries -- on a CPU tensor, i.e. before any
+    device or library call -- and a refused call leaves num_batches_tracked alone."""
+    bad = Conv3d(4, 4, kernel_size=3, **{"padding": 1, **UNSUPPORTED[what]})
+    good = Conv3d(4, 4, kernel_size=3, padding=1)
+    bn1, bn2 = BatchNorm3d(4).train(), BatchNorm3d(4).train()
+    x = torch.zeros(1, 8, 8, 8, 4)
+    with pytest.raises(NotImplementedError):
+        bad(x)
+    with pytest.raises(NotImplementedError):
+        if entry == "conv_bn_act":
+            F.conv_bn_act(x, bad, bn1, F.ACT_RELU)
+        elif entry == "conv_in_act":
+            F.conv_in_act(x, bad, InstanceNorm3d(4), F.ACT_LRELU)
+        elif entry == "double_conv_bn_act_first":
+            F.double_conv_bn_act(x, bad, bn1, good, bn2, F.ACT_RELU)
+        else:
+            F.double_conv_bn_act(x, good, bn1, bad, bn2, F.ACT_RELU)
+    assert int(bn1.num_batches_tracked) == 0 and int(bn2.num_batches_tracked) == 0
+
+
+def test_concat_base_accepts_only_the_right_slice_of_a_matching_buffer():
+    lead, Cout, Cs = (1, 4, 4, 4), 3, 5
+    buf = torch.zeros(lead + (Cout + Cs,))
+    assert F._concat_base(buf[..., Cout:], Cout, lead, torch.float32) is buf
+    assert F._concat_base(buf[..., :Cs], Cout, lead, torch.float32) is None                                 # a left slice
+    assert F._concat_base(torch.zeros(lead + (Cout + Cs + 1,))[..., Cout + 1:], Cout, lead, torch.float32) is None    # one channel too wide
+    assert F._concat_base(buf[..., Cout:], Cout, lead, torch.bfloat16) is None                              # dtype mismatch
+    assert F._concat_base(buf[..., Cout:], Cout, (1, 4, 4, 2), torch.float32) is None                       # other extents
+    pitch = 2 * (Cout + Cs)
+    wide = torch.empty_strided(lead + (Cout + Cs,), (64 * pitch, 16 * pitch, 4 * pitch, pitch, 1))
+    assert wide._base is None and not wide.is_contiguous()
+    assert F._concat_base(wide[..., Cout:], Cout, lead, torch.float32) is None                              # non-contiguous base
+    assert F._concat_base(torch.zeros(lead + (Cs,)), Cout, lead, torch.float32) is None                     # no base at all
+
+
+def test_unread_fusion_switches_are_gone():
+    src = open(os.path.join(os.path.dirname(os.path.abspath(mi355seg.functional.__file__)), "functional.py")).read()
+    for name in ("RES_EPILOGUE", "CAT_FUSION", "STEM_FUSION", "HEAD_FUSION", "POOL_FUSION"):
+        assert "MI355SEG_NO_" + name not in src
+    assert set(re.findall(r"MI355SEG_NO_\w+", src)) == {"MI355SEG_NO_PREPACK", "MI355SEG_NO_PRO_FUSION", "MI355SEG_NO_MASK_POOL", "MI355SEG_NO_GEMM_PAIRS"}
