@@ -34,55 +34,90 @@ static void cast_rows(const TS* src, int lds, TD* dst, int ldd, long long rows, 
     hipLaunchKernelGGL((cast_rows_kernel<TS, TD>), dim3(grid), dim3(256), 0, st, src, lds, dst, ldd, rows, C);
 }
 
-static int oext(int n, int k, int s, int p) { return (n + 2 * p - k) / s + 1; }
-
-// which native bf16 kernel serves a shape (0 = none: fp32 fallback)
-enum { NB_NONE = 0, NB_IGEMM, NB_GATHER, NB_STEM1K5, NB_PWL, NB_HEADPW, NB_K2S2W, NB_HEAD2, NB_STEM4, NB_STEM, NB_HEAD, NB_LOWP, NB_PW, NB_SMALLCIN, NB_SMALLCOUT, NB_GW, NB_TINY, NB_CONVT };
-static int native_fwd(int N, int D, int H, int W, int Cin, int Cout, int k, int s, int p, int ldx, int ldy) {
-    if (conv_mfma_supported(MATH_B16, N, D, H, W, Cin, Cout, k, s, p, ldx, ldy)) return NB_IGEMM;
-    if (conv_gather_fwd_supported(MATH_B16, N, D, H, W, Cin, Cout, k, s, p, ldx, ldy)) return NB_GATHER;
-    if (head2_lowp_supported(Cin, Cout, k, s, p, ldx, ldy)) return NB_HEAD2;
-    if (stem1k5_lowp_supported(Cin, Cout, k, s, p, ldx, ldy)) return NB_STEM1K5;
-    if (stem4_lowp_supported(Cin, Cout, k, s, p, ldx, ldy)) return NB_STEM4;
-    if (stem_supported(Cin, Cout, k, s, p, ldy)) return NB_STEM;
-    if (headpw_lowp_supported(Cin, Cout, k, s, p, ldx, ldy)) return NB_HEADPW;
-    if (head_supported(Cin, Cout, k, s, p, ldx)) return NB_HEAD;
-    if (tinypw_supported(Cin, Cout, k, s, p)) return NB_TINY;
-    return NB_NONE;
-}
-static int native_dgrad(int N, int D, int H, int W, int Cin, int Cout, int k, int s, int p, int lddy, int lddx) {
-    if (conv_mfma_supported(MATH_B16, N, D, H, W, Cout, Cin, k, s, p, lddy, lddx)) return NB_IGEMM;
-    if (conv_gather_dgrad_supported(MATH_B16, N, D, H, W, Cin, Cout, k, s, p, lddy, lddx)) return NB_GATHER;
-    if (head2_lowp_supported(Cin, Cout, k, s, p, lddx, lddy)) return NB_HEAD2;
-    if (head_supported(Cin, Cout, k, s, p, lddx)) return NB_HEAD;
-    if (tinypw_supported(Cin, Cout, k, s, p)) return NB_TINY;
+// ---- the three bf16 choosers.  Families of native kernels, NB_CAST = the fp32 entry point on fp32 copies staged in the workspace.
+// Unlike the fp32 ladders (conv_generic.hip), the FIRST rung that fits the geometry and pitches owns the call: its kernel runs if `aligned`
+// (the launcher's demands on the addresses modulo 16 -- ax: x or dx, ay: y or dy -- and on accumulate) holds too, else the `demote` rung's if
+// that one fits and is aligned, else the cast fall-back -- never a family further down.
+enum { NB_CAST = 0, NB_IGEMM, NB_GATHER, NB_STEM1K5, NB_PWL, NB_HEADPW, NB_K2S2W, NB_HEAD2, NB_STEM4, NB_STEM, NB_HEAD, NB_LOWP, NB_PW, NB_SMALLCIN, NB_SMALLCOUT, NB_GW, NB_TINY, NB_CONVT };
+static bool k2s2(const ConvGeom& g) { return g.k == 2 && g.stride == 2 && g.pad == 0; }
+static bool k2s2_even(const ConvGeom& g) { return k2s2(g) && g.D % 2 == 0 && g.H % 2 == 0 && g.W % 2 == 0; }
+static bool al16(const ConvKey& k) { return k.ax == 0 && k.ay == 0; }
+static bool al8(const ConvKey& k) { return k.ax % 8 == 0 && k.ay % 8 == 0; }
+static size_t ws_head2(const ConvGeom& g) { return head2_lowp_ws_bytes(g.Cin); }
+static size_t ws_stem1k5(const ConvGeom& g) { return stem1k5_lowp_ws_bytes(g.Cout); }
+static size_t ws_stem4(const ConvGeom& g) { return stem4_lowp_ws_bytes(g.Cout); }
+static size_t ws_headpw(const ConvGeom& g) { return headpw_lowp_ws_bytes(g.Cin, g.Cout); }
+// (rungs without a `ws`: kernels shared with the fp32 ladders, whose terms the bf16 query starts from)
+static const Rung FWD_B16[] = {
+    {NB_IGEMM, RUNG(conv_mfma_supported(MATH_B16, GEOM9(g), k.ldx, k.ldy)), nullptr, nullptr, RUNG(k.ax == 0)},
+    {NB_GATHER, RUNG(conv_gather_fwd_supported(MATH_B16, GEOM9(g), k.ldx, k.ldy)), nullptr, nullptr, RUNG(k.ax == 0)},
+    {NB_HEAD2, RUNG(head2_lowp_supported(SHAPE5(g), k.ldx, k.ldy)), ws_head2, nullptr, RUNG(k.ax == 0 && k.ay % 4 == 0)},
+    {NB_STEM1K5, RUNG(stem1k5_lowp_supported(SHAPE5(g), k.ldx, k.ldy)), ws_stem1k5, nullptr, RUNG(k.ay % 8 == 0)},
+    {NB_STEM4, RUNG(stem4_lowp_supported(SHAPE5(g), k.ldx, k.ldy)), ws_stem4, nullptr, al8, NB_STEM},
+    {NB_STEM, RUNG(stem_supported(SHAPE5(g), k.ldy)), nullptr, nullptr, RUNG(k.ay % 8 == 0)},
+    {NB_HEADPW, RUNG(headpw_lowp_supported(SHAPE5(g), k.ldx, k.ldy)), ws_headpw, nullptr, RUNG(k.ax == 0 && k.ay % (2 * g.Cout) == 0), NB_HEAD},
+    {NB_HEAD, RUNG(head_supported(SHAPE5(g), k.ldx)), nullptr, nullptr, RUNG(k.ax % 8 == 0)},
+    {NB_TINY, RUNG(tinypw_supported(SHAPE5(g)))},
+    {NB_CAST}};
+static const Rung DGRAD_B16[] = {
+    {NB_IGEMM, RUNG(conv_mfma_supported(MATH_B16, GEOM9_T(g), k.ldy, k.ldx)), nullptr, nullptr, RUNG(k.ay == 0)},
+    {NB_GATHER, RUNG(conv_gather_dgrad_supported(MATH_B16, GEOM9(g), k.ldy, k.ldx)), nullptr, nullptr, RUNG(k.ay == 0)},
+    {NB_HEAD2, RUNG(head2_lowp_supported(SHAPE5(g), k.ldx, k.ldy)), ws_head2, nullptr, RUNG(k.ay % 4 == 0 && k.ax % 8 == 0)},
+    {NB_HEAD, RUNG(head_supported(SHAPE5(g), k.ldx)), nullptr, nullptr, RUNG(k.ax % 8 == 0)},
+    {NB_TINY, RUNG(tinypw_supported(SHAPE5(g)))},
     // k2 s2 p0: the input gradient is the forward of ConvTranspose3d k2 s2 with the same weight tensor (conv_generic.hip)
-    if (k == 2 && s == 2 && p == 0 && D % 2 == 0 && H % 2 == 0 && W % 2 == 0 && convt_mfma_supported(MATH_B16, N, D / 2, H / 2, W / 2, Cout, Cin, lddy, lddx))
-        return NB_CONVT;
-    return NB_NONE;
-}
-static int native_wgrad(int N, int D, int H, int W, int Cin, int Cout, int k, int s, int p, int ldx, int lddy) {
-    if (wgrad_lowp_supported(MATH_B16, N, D, H, W, Cin, Cout, k, s, p, ldx, lddy)) return NB_LOWP;
-    // V-Net's two-channel k5 head: the fp32 z-marching kernel (conv_headk.hip) behind the cast fall-back is 8x faster than the
-    // generic small-channel wgrad below (the one-channel k5 stem has its own LDS-tiled kernel inside smallcin_wgrad)
-    if (head2_lowp_supported(Cin, Cout, k, s, p, ldx, lddy)) return NB_HEAD2;
-    if (stem1k5_lowp_supported(Cin, Cout, k, s, p, ldx, lddy)) return NB_STEM1K5;
+    {NB_CONVT, RUNG(k2s2_even(g) && convt_mfma_supported(MATH_B16, g.N, g.D / 2, g.H / 2, g.W / 2, g.Cout, g.Cin, k.ldy, k.ldx)), nullptr, nullptr, RUNG(k.ay == 0)},
+    {NB_CAST}};
+static const Rung WGRAD_B16[] = {
+    {NB_LOWP, RUNG(wgrad_lowp_supported(MATH_B16, GEOM9(g), k.ldx, k.ldy)), nullptr, nullptr, al16},
+    {NB_HEAD2, RUNG(head2_lowp_supported(SHAPE5(g), k.ldx, k.ldy)), ws_head2, nullptr, RUNG(k.ax == 0 && k.ay % 4 == 0)},
+    {NB_STEM1K5, RUNG(stem1k5_lowp_supported(SHAPE5(g), k.ldx, k.ldy)), ws_stem1k5, nullptr, RUNG(k.ay == 0)},
     // k2 s2 down-convolution (V-Net): its weight gradient IS a ConvTranspose k2 s2 weight gradient with the roles swapped
-    // (base voxels = the coarse dy, children = the fine x), and (Cout, Cin, 2, 2, 2) is that kernel's output layout
-    if (k == 2 && s == 2 && p == 0 && D % 2 == 0 && H % 2 == 0 && W % 2 == 0 &&
-        convt_wgrad_lowp_supported((long long)N * (D / 2) * (H / 2) * (W / 2), Cout, Cin, lddy, ldx, 2)) return NB_K2S2W;
-    if (headk_wgrad_supported(Cin, Cout, k, s, p, Cin, Cout)) return NB_NONE;
-    if (tinypw_supported(Cin, Cout, k, s, p)) return NB_TINY;
-    if (k == 1 && s == 1 && p == 0 && pw_wgrad_lowp_supported((long long)N * D * H * W, Cin, Cout, ldx, lddy, 2)) return NB_PWL;
-    if (k == 1 && s == 1 && p == 0 && pw_wgrad_supported((long long)N * D * H * W, Cin, Cout, 1, ldx, lddy)) return NB_PW;
-    if (stem4_lowp_supported(Cin, Cout, k, s, p, ldx, lddy)) return NB_STEM4;
-    if (stem_supported(Cin, Cout, k, s, p, lddy)) return NB_STEM;
-    if (headpw_lowp_supported(Cin, Cout, k, s, p, ldx, lddy)) return NB_HEADPW;
-    if (head_supported(Cin, Cout, k, s, p, ldx)) return NB_HEAD;
-    if (smallcin_wgrad_supported(Cin, Cout, k)) return NB_SMALLCIN;
-    if (smallcout_wgrad_supported(Cin, Cout, k, ldx)) return NB_SMALLCOUT;
-    if (gwgrad_supported(N, D, H, W, Cin, Cout, k, s, p, ldx, lddy)) return NB_GW;
-    return NB_NONE;
+    // (base voxels = the coarse dy, children = the fine x), and (Cout, Cin, 2, 2, 2) is that kernel's output layout; it cannot accumulate.
+    // conservative: counted for every k2 s2 p0 geometry
+    {NB_K2S2W, RUNG(k2s2_even(g) && convt_wgrad_lowp_supported(conv_vin(g) / 8, g.Cout, g.Cin, k.ldy, k.ldx, 2)),
+     WS(convt_wgrad_lowp_ws_bytes((long long)g.N * (g.D / 2) * (g.H / 2) * (g.W / 2), g.Cout, g.Cin)), k2s2, RUNG(al16(k) && !k.accumulate)},
+    // V-Net's two-channel k5 head off the head2 rung: the fp32 z-marching kernel (conv_headk.hip) behind the cast fall-back is 8x faster than
+    // the generic small-channel wgrad below (the one-channel k5 stem has its own LDS-tiled kernel inside smallcin_wgrad)
+    {NB_CAST, RUNG(headk_wgrad_supported(SHAPE5(g), g.Cin, g.Cout))},
+    {NB_TINY, RUNG(tinypw_supported(SHAPE5(g)))},
+    // conservative: counted for every pointwise geometry
+    {NB_PWL, RUNG(pointwise(g) && pw_wgrad_lowp_supported(conv_vin(g), g.Cin, g.Cout, k.ldx, k.ldy, 2)), WS(pw_wgrad_lowp_ws_bytes(conv_vin(g), g.Cin, g.Cout)), pointwise, al16, NB_PW},
+    {NB_PW, RUNG(pointwise(g) && pw_wgrad_supported(conv_vin(g), g.Cin, g.Cout, 1, k.ldx, k.ldy)), nullptr, nullptr, al8},
+    {NB_STEM4, RUNG(stem4_lowp_supported(SHAPE5(g), k.ldx, k.ldy)), ws_stem4, nullptr, al16, NB_STEM},
+    {NB_STEM, RUNG(stem_supported(SHAPE5(g), k.ldy)), nullptr, nullptr, al8},
+    {NB_HEADPW, RUNG(headpw_lowp_supported(SHAPE5(g), k.ldx, k.ldy)), ws_headpw, nullptr, al16, NB_HEAD},
+    {NB_HEAD, RUNG(head_supported(SHAPE5(g), k.ldx)), nullptr, nullptr, al8},
+    {NB_SMALLCIN, RUNG(smallcin_wgrad_supported(g.Cin, g.Cout, g.k)), nullptr, nullptr, al8},
+    {NB_SMALLCOUT, RUNG(smallcout_wgrad_supported(g.Cin, g.Cout, g.k, k.ldx)), nullptr, nullptr, al8},
+    {NB_GW, RUNG(gwgrad_supported(GEOM9(g), k.ldx, k.ldy)), nullptr, nullptr, al8},
+    {NB_CAST}};
+static int choose_b16(const Rung* r, const ConvKey& k) {
+    while (r->fits && !r->fits(k)) ++r;
+    if (!r->aligned || r->aligned(k)) return r->family;
+    for (const Rung* d = r + 1; r->demote && d->fits; ++d)
+        if (d->family == r->demote) return d->fits(k) && d->aligned(k) ? d->family : NB_CAST;
+    return NB_CAST;
+}
+
+// the cast fall-back: fp32 copies of x (or dx) and y (or dy) in the workspace, `run` on them with the rest of it, the written one cast back
+template <typename F>
+static int staged(const ConvCall& c, bool x_in, bool y_in, F run) {
+    const ConvGeom& g = c.g;
+    Carver cv(c.ws);
+    float* xf = cv.take<float>((size_t)c.vin() * g.Cin);
+    float* yf = cv.take<float>((size_t)c.vout() * g.Cout);
+    const size_t used = cv.used();
+    SEG_CHECK_WS(used + mi355seg_conv3d_ws_bytes(GEOM9(g)), c.ws_bytes);
+    if (x_in) cast_rows((const bf16*)c.x, c.ldx, xf, g.Cin, c.vin(), g.Cin, c.st);
+    if (y_in) cast_rows((const bf16*)c.y, c.ldy, yf, g.Cout, c.vout(), g.Cout, c.st);
+    SEG_CHECK_LAUNCH();
+    int rc = run(xf, yf, (char*)c.ws + used, c.ws_bytes - used);
+    if (rc || (x_in && y_in)) return rc;
+    if (x_in) cast_rows(yf, g.Cout, (bf16*)c.y, c.ldy, c.vout(), g.Cout, c.st);
+    else cast_rows(xf, g.Cin, (bf16*)c.x, c.ldx, c.vin(), g.Cin, c.st);
+    SEG_CHECK_LAUNCH();
+    return MI355SEG_OK;
 }
 
 }  // namespace seg
@@ -105,38 +140,38 @@ int mi355seg_set_wgrad_wide(int mode) {
 }
 int mi355seg_get_wgrad_wide(void) { return get_wgrad_wide(); }
 
-// workspace of the three bf16 Conv3d entry points for one layer geometry (contiguous tensors assumed for the fallback test)
+// workspace of the three bf16 Conv3d entry points for one layer geometry: the fp32 query, the rungs of the bf16 ladders the geometry can
+// reach, and the staging copies of the cast fall-back
 size_t mi355seg_conv3d_ws_bytes_bf16(int N, int D, int H, int W, int Cin, int Cout, int k, int stride, int pad) {
     size_t base = mi355seg_conv3d_ws_bytes(N, D, H, W, Cin, Cout, k, stride, pad);
     if (D + 2 * pad < k || H + 2 * pad < k || W + 2 * pad < k) return base;
-    const int Do = oext(D, k, stride, pad), Ho = oext(H, k, stride, pad), Wo = oext(W, k, stride, pad);
-    const bool fb = !native_fwd(N, D, H, W, Cin, Cout, k, stride, pad, Cin, Cout) || !native_dgrad(N, D, H, W, Cin, Cout, k, stride, pad, Cout, Cin) ||
-                    !native_wgrad(N, D, H, W, Cin, Cout, k, stride, pad, Cin, Cout);
-    if (stem4_lowp_supported(Cin, Cout, k, stride, pad, Cin, Cout) && base < stem4_lowp_ws_bytes(Cout)) base = stem4_lowp_ws_bytes(Cout);
-    if (head2_lowp_supported(Cin, Cout, k, stride, pad, Cin, Cout) && base < head2_lowp_ws_bytes(Cin)) base = head2_lowp_ws_bytes(Cin);
-    if (headpw_lowp_supported(Cin, Cout, k, stride, pad, Cin, Cout) && base < headpw_lowp_ws_bytes(Cin, Cout)) base = headpw_lowp_ws_bytes(Cin, Cout);
-    if (stem1k5_lowp_supported(Cin, Cout, k, stride, pad, Cin, Cout) && base < stem1k5_lowp_ws_bytes(Cout)) base = stem1k5_lowp_ws_bytes(Cout);
-    if (k == 1 && stride == 1 && pad == 0 && base < pw_wgrad_lowp_ws_bytes((long long)N * D * H * W, Cin, Cout)) base = pw_wgrad_lowp_ws_bytes((long long)N * D * H * W, Cin, Cout);
-    if (k == 2 && stride == 2 && pad == 0 && base < convt_wgrad_lowp_ws_bytes((long long)N * (D / 2) * (H / 2) * (W / 2), Cout, Cin))
-        base = convt_wgrad_lowp_ws_bytes((long long)N * (D / 2) * (H / 2) * (W / 2), Cout, Cin);
-    // the fp32 staging copies of the fall-back: for shapes without a native kernel, and -- while they stay under 512 MB -- for
-    // every shape, because an entry point also falls back when a POINTER is not 16-byte aligned (a bf16 channel slice at an
-    // 8-byte offset) or a k2 s2 weight gradient is asked not to accumulate, which this query cannot see
-    const size_t stage = align_up((size_t)N * D * H * W * Cin * 4, 256) + align_up((size_t)N * Do * Ho * Wo * Cout * 4, 256) + 512;
+    const ConvGeom g{N, D, H, W, Cin, Cout, k, stride, pad, (D + 2 * pad - k) / stride + 1, (H + 2 * pad - k) / stride + 1, (W + 2 * pad - k) / stride + 1};
+    for (const Rung* ladder : {FWD_B16, DGRAD_B16, WGRAD_B16})
+        if (ladder_ws_bytes(ladder, g) > base) base = ladder_ws_bytes(ladder, g);
+    // the fp32 staging copies of the fall-back: for shapes that take it with contiguous, aligned tensors, and -- while they stay under
+    // 512 MB -- for every shape, because an entry point also falls back when a POINTER is not 16-byte aligned (a bf16 channel slice at an
+    // 8-byte offset) or a k2 s2 weight gradient is asked to accumulate, which this query cannot see
+    const ConvKey d = dense_key(g);
+    const bool fb = !choose_b16(FWD_B16, d) || !choose_b16(DGRAD_B16, d) || !choose_b16(WGRAD_B16, d);
+    const size_t stage = align_up((size_t)N * D * H * W * Cin * 4, 256) + align_up((size_t)N * g.Do * g.Ho * g.Wo * Cout * 4, 256) + 512;
     if (fb || stage <= ((size_t)512 << 20)) base += stage;
     return base;
 }
 
 int mi355seg_conv3d_fused_supported_bf16(int N, int D, int H, int W, int Cin, int Cout, int k, int stride, int pad, int ldx, int ldy) {
-    return native_fwd(N, D, H, W, Cin, Cout, k, stride, pad, ldx, ldy) == NB_IGEMM;
+    return choose_b16(FWD_B16, ConvKey{{N, D, H, W, Cin, Cout, k, stride, pad, 0, 0, 0}, ldx, ldy, 0, 0, 0}) == NB_IGEMM;
 }
 int mi355seg_conv3d_fwd_fused_bf16(const mi355seg_bf16* x, int ldx, const float* w, const float* oscale, const float* oshift, int act, float slope,
                                    mi355seg_bf16* y, int ldy, int N, int D, int H, int W, int Cin, int Cout, int k, int stride, int pad,
                                    void* ws, size_t ws_bytes, void* stream) {
-    SEG_CHECK_ARG(x && w && y && oscale && oshift && N > 0 && D > 0 && H > 0 && W > 0 && Cin > 0 && Cout > 0 && ldx >= Cin && ldy >= Cout, "conv3d_fwd_fused_bf16: bad arguments");
-    SEG_CHECK_ARG(mi355seg_conv3d_fused_supported_bf16(N, D, H, W, Cin, Cout, k, stride, pad, ldx, ldy) && ((uintptr_t)x % 16) == 0,
-                  "conv3d_fwd_fused_bf16: no fused form for this shape / alignment (ask mi355seg_conv3d_fused_supported_bf16)");
-    return conv_fwd_mfma(MATH_B16, x, ldx, w, oshift, y, ldy, N, D, H, W, Cin, Cout, k, /*dgrad=*/0, nullptr, nullptr, ws, ws_bytes, (hipStream_t)stream, oscale, act, slope);
+    ConvCall c;
+    int rc = conv_call(&c, "conv3d_fwd_fused_bf16", x, ldx, w, y, ldy, N, D, H, W, Cin, Cout, k, stride, pad, ws, ws_bytes, stream);
+    if (rc) return rc;
+    SEG_CHECK_ARG(oscale && oshift, "conv3d_fwd_fused_bf16: null pointer or pitch < channels");
+    SEG_CHECK_ARG(choose_b16(FWD_B16, conv_key(c)) == NB_IGEMM, "conv3d_fwd_fused_bf16: no fused form for this shape / alignment (ask mi355seg_conv3d_fused_supported_bf16)");
+    MfmaOpts o;
+    o.oscale = oscale; o.act = act; o.slope = slope;
+    return conv_fwd_mfma(MATH_B16, x, ldx, w, oshift, y, ldy, N, D, H, W, Cin, Cout, k, /*dgrad=*/0, nullptr, nullptr, ws, ws_bytes, c.st, o);
 }
 
 // y = conv(x) + res as the reference's two bf16 operations give it (each rounded to bf16): the sum rides in the convolution's epilogue
@@ -144,117 +179,66 @@ int mi355seg_conv3d_fwd_fused_bf16(const mi355seg_bf16* x, int ldx, const float*
 int mi355seg_conv3d_fwd_res_bf16(const mi355seg_bf16* x, int ldx, const float* w, const float* bias, const mi355seg_bf16* res, int ldres,
                                  mi355seg_bf16* y, int ldy, int N, int D, int H, int W, int Cin, int Cout, int k, int stride, int pad,
                                  void* ws, size_t ws_bytes, void* stream) {
+    ConvCall c;
+    int rc = conv_call(&c, "conv3d_fwd_res_bf16", x, ldx, w, y, ldy, N, D, H, W, Cin, Cout, k, stride, pad, ws, ws_bytes, stream);
+    if (rc) return rc;
     SEG_CHECK_ARG(res && ldres >= Cout, "conv3d_fwd_res_bf16: null residual or pitch < channels");
-    hipStream_t st = (hipStream_t)stream;
-    const int Do = oext(D, k, stride, pad), Ho = oext(H, k, stride, pad), Wo = oext(W, k, stride, pad);
-    if (x && y && native_fwd(N, D, H, W, Cin, Cout, k, stride, pad, ldx, ldy) == NB_IGEMM && ((uintptr_t)x % 16) == 0) {
-        int fused = 0;
-        int rc = conv_fwd_mfma(MATH_B16, x, ldx, w, bias, y, ldy, N, D, H, W, Cin, Cout, k, /*dgrad=*/0, nullptr, nullptr, ws, ws_bytes, st,
-                               nullptr, 0, 0.f, nullptr, nullptr, nullptr, res, ldres, &fused);
-        if (rc || fused) return rc;
+    int fused = 0;
+    if (choose_b16(FWD_B16, conv_key(c)) == NB_IGEMM) {
+        MfmaOpts o;
+        o.res = res; o.ldres = ldres; o.res_fused = &fused;
+        rc = conv_fwd_mfma(MATH_B16, x, ldx, w, bias, y, ldy, N, D, H, W, Cin, Cout, k, /*dgrad=*/0, nullptr, nullptr, ws, ws_bytes, c.st, o);
     } else {
-        int rc = mi355seg_conv3d_fwd_bf16(x, ldx, w, bias, y, ldy, N, D, H, W, Cin, Cout, k, stride, pad, nullptr, nullptr, ws, ws_bytes, stream);
-        if (rc) return rc;
+        rc = mi355seg_conv3d_fwd_bf16(x, ldx, w, bias, y, ldy, N, D, H, W, Cin, Cout, k, stride, pad, nullptr, nullptr, ws, ws_bytes, stream);
     }
-    return mi355seg_act_fwd_bf16(y, ldy, res, ldres, y, ldy, (long long)N * Do * Ho * Wo, Cout, 0, 0.f, stream);
+    if (rc || fused) return rc;
+    return mi355seg_act_fwd_bf16(y, ldy, res, ldres, y, ldy, c.vout(), Cout, 0, 0.f, stream);
 }
 
 int mi355seg_conv3d_fwd_bf16(const mi355seg_bf16* x, int ldx, const float* w, const float* bias, mi355seg_bf16* y, int ldy,
                              int N, int D, int H, int W, int Cin, int Cout, int k, int stride, int pad,
                              double* stats_sum, double* stats_sq, void* ws, size_t ws_bytes, void* stream) {
-    SEG_CHECK_ARG(x && w && y && N > 0 && D > 0 && H > 0 && W > 0 && Cin > 0 && Cout > 0 && ldx >= Cin && ldy >= Cout, "conv3d_fwd_bf16: bad arguments");
-    SEG_CHECK_ARG(k >= 1 && k <= 16 && stride >= 1 && pad >= 0 && D + 2 * pad >= k && H + 2 * pad >= k && W + 2 * pad >= k,
-                  "conv3d_fwd_bf16: bad k/stride/pad %d/%d/%d", k, stride, pad);
-    SEG_CHECK_ARG((stats_sum == nullptr) == (stats_sq == nullptr), "conv3d_fwd_bf16: stats_sum/stats_sq must come together");
-    hipStream_t st = (hipStream_t)stream;
-    const int Do = oext(D, k, stride, pad), Ho = oext(H, k, stride, pad), Wo = oext(W, k, stride, pad);
-    const long long vout = (long long)N * Do * Ho * Wo;
-    const bool al = ((uintptr_t)x % 16) == 0;
-    const int nb = native_fwd(N, D, H, W, Cin, Cout, k, stride, pad, ldx, ldy);
-    if (nb == NB_IGEMM && al)
-        return conv_fwd_mfma(MATH_B16, x, ldx, w, bias, y, ldy, N, D, H, W, Cin, Cout, k, /*dgrad=*/0, stats_sum, stats_sq, ws, ws_bytes, st);
-    if (nb == NB_GATHER && al)
-        return conv_gather_fwd_mfma(MATH_B16, x, ldx, w, bias, y, ldy, N, D, H, W, Cin, Cout, k, stride, pad, stats_sum, stats_sq, ws, ws_bytes, st);
-    if (nb == NB_HEAD2 && al && ((uintptr_t)y % 4) == 0) {
-        int rc = head2_fwd_lowp(x, ldx, w, bias, y, ldy, N, D, H, W, Cin, ws, ws_bytes, st);
-        if (rc || !stats_sum) return rc;
-        return channel_sums(y, ldy, vout, Cout, stats_sum, stats_sq, nullptr, 0, ws, ws_bytes, st);
-    }
-    if (nb == NB_STEM1K5 && ((uintptr_t)y % 8) == 0) {
-        int rc = stem1k5_fwd_lowp(x, w, bias, y, ldy, N, D, H, W, Cout, ws, ws_bytes, st);
-        if (rc || !stats_sum) return rc;
-        return channel_sums(y, ldy, vout, Cout, stats_sum, stats_sq, nullptr, 0, ws, ws_bytes, st);
-    }
-    if (nb == NB_STEM4 && ((uintptr_t)x % 8) == 0 && ((uintptr_t)y % 8) == 0) {
-        int rc = stem4_fwd_lowp(x, w, bias, y, ldy, N, D, H, W, Cout, ws, ws_bytes, st);
-        if (rc || !stats_sum) return rc;
-        return channel_sums(y, ldy, vout, Cout, stats_sum, stats_sq, nullptr, 0, ws, ws_bytes, st);
-    }
-    if ((nb == NB_STEM || nb == NB_STEM4) && ((uintptr_t)y % 8) == 0)
-        return stem_fwd(x, ldx, w, bias, y, ldy, N, D, H, W, Cin, Cout, stats_sum, stats_sq, ws, ws_bytes, st);
-    if (nb == NB_HEADPW && al && ((uintptr_t)y % (2 * Cout)) == 0) {
-        int rc = headpw_fwd_lowp(x, ldx, w, bias, y, ldy, vout, Cin, Cout, st);
-        if (rc || !stats_sum) return rc;
-        return channel_sums(y, ldy, vout, Cout, stats_sum, stats_sq, nullptr, 0, ws, ws_bytes, st);
-    }
-    if ((nb == NB_HEAD || nb == NB_HEADPW) && ((uintptr_t)x % 8) == 0) {
-        int rc = head_fwd(x, ldx, w, bias, y, ldy, N, D, H, W, Cin, Cout, st);
-        if (rc || !stats_sum) return rc;
-        return channel_sums(y, ldy, vout, Cout, stats_sum, stats_sq, nullptr, 0, ws, ws_bytes, st);
-    }
-    if (nb == NB_TINY) {
-        int rc = tinypw_fwd(x, ldx, w, bias, y, ldy, vout, Cin, Cout, st);
-        if (rc || !stats_sum) return rc;
-        return channel_sums(y, ldy, vout, Cout, stats_sum, stats_sq, nullptr, 0, ws, ws_bytes, st);
-    }
-    // fp32 fallback
-    Carver cv(ws);
-    float* xf = cv.take<float>((size_t)N * D * H * W * Cin);
-    float* yf = cv.take<float>((size_t)vout * Cout);
-    const size_t used = cv.used();
-    SEG_CHECK_WS(used + mi355seg_conv3d_ws_bytes(N, D, H, W, Cin, Cout, k, stride, pad), ws_bytes);
-    cast_rows(x, ldx, xf, Cin, (long long)N * D * H * W, Cin, st);
-    SEG_CHECK_LAUNCH();
-    int rc = mi355seg_conv3d_fwd_f32(xf, Cin, w, bias, yf, Cout, N, D, H, W, Cin, Cout, k, stride, pad, stats_sum, stats_sq, (char*)ws + used, ws_bytes - used, stream);
+    ConvCall c;
+    int rc = conv_call(&c, "conv3d_fwd_bf16", x, ldx, w, y, ldy, N, D, H, W, Cin, Cout, k, stride, pad, ws, ws_bytes, stream);
     if (rc) return rc;
-    cast_rows(yf, Cout, y, ldy, vout, Cout, st);
-    SEG_CHECK_LAUNCH();
-    return MI355SEG_OK;
+    SEG_CHECK_ARG((stats_sum == nullptr) == (stats_sq == nullptr), "conv3d_fwd_bf16: stats_sum/stats_sq must come together");
+    hipStream_t st = c.st;
+    switch (choose_b16(FWD_B16, conv_key(c))) {
+    case NB_IGEMM: return conv_fwd_mfma(MATH_B16, x, ldx, w, bias, y, ldy, N, D, H, W, Cin, Cout, k, /*dgrad=*/0, stats_sum, stats_sq, ws, ws_bytes, st);
+    case NB_GATHER: return conv_gather_fwd_mfma(MATH_B16, x, ldx, w, bias, y, ldy, N, D, H, W, Cin, Cout, k, stride, pad, stats_sum, stats_sq, ws, ws_bytes, st);
+    case NB_HEAD2: return conv_stats_tail<bf16>(head2_fwd_lowp(x, ldx, w, bias, y, ldy, N, D, H, W, Cin, ws, ws_bytes, st), c, stats_sum, stats_sq);
+    case NB_STEM1K5: return conv_stats_tail<bf16>(stem1k5_fwd_lowp(x, w, bias, y, ldy, N, D, H, W, Cout, ws, ws_bytes, st), c, stats_sum, stats_sq);
+    case NB_STEM4: return conv_stats_tail<bf16>(stem4_fwd_lowp(x, w, bias, y, ldy, N, D, H, W, Cout, ws, ws_bytes, st), c, stats_sum, stats_sq);
+    case NB_STEM: return stem_fwd(x, ldx, w, bias, y, ldy, N, D, H, W, Cin, Cout, stats_sum, stats_sq, ws, ws_bytes, st);
+    case NB_HEADPW: return conv_stats_tail<bf16>(headpw_fwd_lowp(x, ldx, w, bias, y, ldy, c.vout(), Cin, Cout, st), c, stats_sum, stats_sq);
+    case NB_HEAD: return conv_stats_tail<bf16>(head_fwd(x, ldx, w, bias, y, ldy, N, D, H, W, Cin, Cout, st), c, stats_sum, stats_sq);
+    case NB_TINY: return conv_stats_tail<bf16>(tinypw_fwd(x, ldx, w, bias, y, ldy, c.vout(), Cin, Cout, st), c, stats_sum, stats_sq);
+    default:
+        return staged(c, true, false, [&](float* xf, float* yf, void* rest, size_t rest_bytes) {
+            return mi355seg_conv3d_fwd_f32(xf, Cin, w, bias, yf, Cout, N, D, H, W, Cin, Cout, k, stride, pad, stats_sum, stats_sq, rest, rest_bytes, stream);
+        });
+    }
 }
 
 int mi355seg_conv3d_dgrad_bf16(const mi355seg_bf16* dy, int lddy, const float* w, mi355seg_bf16* dx, int lddx,
                                int N, int D, int H, int W, int Cin, int Cout, int k, int stride, int pad,
                                void* ws, size_t ws_bytes, void* stream) {
-    SEG_CHECK_ARG(dy && w && dx && N > 0 && D > 0 && H > 0 && W > 0 && Cin > 0 && Cout > 0 && lddy >= Cout && lddx >= Cin, "conv3d_dgrad_bf16: bad arguments");
-    SEG_CHECK_ARG(k >= 1 && k <= 16 && stride >= 1 && pad >= 0 && D + 2 * pad >= k && H + 2 * pad >= k && W + 2 * pad >= k,
-                  "conv3d_dgrad_bf16: bad k/stride/pad %d/%d/%d", k, stride, pad);
-    hipStream_t st = (hipStream_t)stream;
-    const int Do = oext(D, k, stride, pad), Ho = oext(H, k, stride, pad), Wo = oext(W, k, stride, pad);
-    const long long vout = (long long)N * Do * Ho * Wo, vin = (long long)N * D * H * W;
-    const bool al = ((uintptr_t)dy % 16) == 0;
-    const int nb = native_dgrad(N, D, H, W, Cin, Cout, k, stride, pad, lddy, lddx);
-    if (nb == NB_IGEMM && al)
-        return conv_fwd_mfma(MATH_B16, dy, lddy, w, nullptr, dx, lddx, N, D, H, W, Cout, Cin, k, /*dgrad=*/1, nullptr, nullptr, ws, ws_bytes, st);
-    if (nb == NB_GATHER && al)
-        return conv_gather_dgrad_mfma(MATH_B16, dy, lddy, w, dx, lddx, N, D, H, W, Cin, Cout, k, stride, pad, ws, ws_bytes, st);
-    if (nb == NB_HEAD2 && ((uintptr_t)dy % 4) == 0 && ((uintptr_t)dx % 8) == 0)
-        return head2_dgrad_lowp(dy, lddy, w, dx, lddx, N, D, H, W, Cin, ws, ws_bytes, st);
-    if (nb == NB_HEAD && ((uintptr_t)dx % 8) == 0)
-        return head_dgrad(dy, lddy, w, dx, lddx, N, D, H, W, Cin, Cout, st);
-    if (nb == NB_TINY) return tinypw_dgrad(dy, lddy, w, dx, lddx, vin, Cin, Cout, st);
-    if (nb == NB_CONVT && al) return convt_fwd_mfma(MATH_B16, dy, lddy, w, nullptr, dx, lddx, N, D / 2, H / 2, W / 2, Cout, Cin, ws, ws_bytes, st);
-    Carver cv(ws);
-    float* dxf = cv.take<float>((size_t)vin * Cin);
-    float* dyf = cv.take<float>((size_t)vout * Cout);
-    const size_t used = cv.used();
-    SEG_CHECK_WS(used + mi355seg_conv3d_ws_bytes(N, D, H, W, Cin, Cout, k, stride, pad), ws_bytes);
-    cast_rows(dy, lddy, dyf, Cout, vout, Cout, st);
-    SEG_CHECK_LAUNCH();
-    int rc = mi355seg_conv3d_dgrad_f32(dyf, Cout, w, dxf, Cin, N, D, H, W, Cin, Cout, k, stride, pad, (char*)ws + used, ws_bytes - used, stream);
+    ConvCall c;
+    int rc = conv_call(&c, "conv3d_dgrad_bf16", dx, lddx, w, dy, lddy, N, D, H, W, Cin, Cout, k, stride, pad, ws, ws_bytes, stream);
     if (rc) return rc;
-    cast_rows(dxf, Cin, dx, lddx, vin, Cin, st);
-    SEG_CHECK_LAUNCH();
-    return MI355SEG_OK;
+    hipStream_t st = c.st;
+    switch (choose_b16(DGRAD_B16, conv_key(c))) {
+    case NB_IGEMM: return conv_fwd_mfma(MATH_B16, dy, lddy, w, nullptr, dx, lddx, N, D, H, W, Cout, Cin, k, /*dgrad=*/1, nullptr, nullptr, ws, ws_bytes, st);
+    case NB_GATHER: return conv_gather_dgrad_mfma(MATH_B16, dy, lddy, w, dx, lddx, N, D, H, W, Cin, Cout, k, stride, pad, ws, ws_bytes, st);
+    case NB_HEAD2: return head2_dgrad_lowp(dy, lddy, w, dx, lddx, N, D, H, W, Cin, ws, ws_bytes, st);
+    case NB_HEAD: return head_dgrad(dy, lddy, w, dx, lddx, N, D, H, W, Cin, Cout, st);
+    case NB_TINY: return tinypw_dgrad(dy, lddy, w, dx, lddx, c.vin(), Cin, Cout, st);
+    case NB_CONVT: return convt_fwd_mfma(MATH_B16, dy, lddy, w, nullptr, dx, lddx, N, D / 2, H / 2, W / 2, Cout, Cin, ws, ws_bytes, st);
+    default:
+        return staged(c, false, true, [&](float* dxf, float* dyf, void* rest, size_t rest_bytes) {
+            return mi355seg_conv3d_dgrad_f32(dyf, Cout, w, dxf, Cin, N, D, H, W, Cin, Cout, k, stride, pad, rest, rest_bytes, stream);
+        });
+    }
 }
 
 // dx = conv3d_dgrad(dy) + res on bf16 tensors, each of the two operations rounded to bf16 (what autograd's sum of the two gradients of a
@@ -263,82 +247,59 @@ int mi355seg_conv3d_dgrad_bf16(const mi355seg_bf16* dy, int lddy, const float* w
 int mi355seg_conv3d_dgrad_res_bf16(const mi355seg_bf16* dy, int lddy, const float* w, const mi355seg_bf16* res, int ldres, mi355seg_bf16* dx, int lddx,
                                    int N, int D, int H, int W, int Cin, int Cout, int k, int stride, int pad,
                                    void* ws, size_t ws_bytes, void* stream) {
-    SEG_CHECK_ARG(dy && w && dx && res && N > 0 && D > 0 && H > 0 && W > 0 && Cin > 0 && Cout > 0 && lddy >= Cout && lddx >= Cin && ldres >= Cin,
-                  "conv3d_dgrad_res_bf16: bad arguments");
-    hipStream_t st = (hipStream_t)stream;
-    if (stride == 1 && 2 * pad == k - 1 && ((uintptr_t)dy % 16) == 0 && native_dgrad(N, D, H, W, Cin, Cout, k, stride, pad, lddy, lddx) == NB_IGEMM) {
-        int fused = 0;
-        int rc = conv_fwd_mfma(MATH_B16, dy, lddy, w, nullptr, dx, lddx, N, D, H, W, Cout, Cin, k, /*dgrad=*/1, nullptr, nullptr, ws, ws_bytes, st,
-                               nullptr, 0, 0.f, nullptr, nullptr, nullptr, res, ldres, &fused);
-        if (rc || fused) return rc;
+    ConvCall c;
+    int rc = conv_call(&c, "conv3d_dgrad_res_bf16", dx, lddx, w, dy, lddy, N, D, H, W, Cin, Cout, k, stride, pad, ws, ws_bytes, stream);
+    if (rc) return rc;
+    SEG_CHECK_ARG(res && ldres >= Cin, "conv3d_dgrad_res_bf16: null residual or pitch < channels");
+    int fused = 0;
+    if (stride == 1 && 2 * pad == k - 1 && choose_b16(DGRAD_B16, conv_key(c)) == NB_IGEMM) {
+        MfmaOpts o;
+        o.res = res; o.ldres = ldres; o.res_fused = &fused;
+        rc = conv_fwd_mfma(MATH_B16, dy, lddy, w, nullptr, dx, lddx, N, D, H, W, Cout, Cin, k, /*dgrad=*/1, nullptr, nullptr, ws, ws_bytes, c.st, o);
     } else {
-        int rc = mi355seg_conv3d_dgrad_bf16(dy, lddy, w, dx, lddx, N, D, H, W, Cin, Cout, k, stride, pad, ws, ws_bytes, stream);
-        if (rc) return rc;
+        rc = mi355seg_conv3d_dgrad_bf16(dy, lddy, w, dx, lddx, N, D, H, W, Cin, Cout, k, stride, pad, ws, ws_bytes, stream);
     }
-    return mi355seg_act_fwd_bf16(dx, lddx, res, ldres, dx, lddx, (long long)N * D * H * W, Cin, 0, 0.f, stream);
+    if (rc || fused) return rc;
+    return mi355seg_act_fwd_bf16(dx, lddx, res, ldres, dx, lddx, c.vin(), Cin, 0, 0.f, stream);
 }
 
 int mi355seg_conv3d_wgrad_bf16(const mi355seg_bf16* dy, int lddy, const mi355seg_bf16* x, int ldx, float* dw, float* db,
                                int N, int D, int H, int W, int Cin, int Cout, int k, int stride, int pad, int accumulate,
                                void* ws, size_t ws_bytes, void* stream) {
-    SEG_CHECK_ARG(dy && x && dw && N > 0 && D > 0 && H > 0 && W > 0 && Cin > 0 && Cout > 0 && lddy >= Cout && ldx >= Cin, "conv3d_wgrad_bf16: bad arguments");
-    SEG_CHECK_ARG(k >= 1 && k <= 16 && stride >= 1 && pad >= 0 && D + 2 * pad >= k && H + 2 * pad >= k && W + 2 * pad >= k,
-                  "conv3d_wgrad_bf16: bad k/stride/pad %d/%d/%d", k, stride, pad);
-    hipStream_t st = (hipStream_t)stream;
-    const int Do = oext(D, k, stride, pad), Ho = oext(H, k, stride, pad), Wo = oext(W, k, stride, pad);
-    const long long vout = (long long)N * Do * Ho * Wo, vin = (long long)N * D * H * W;
+    ConvCall c;
+    int rc = conv_call(&c, "conv3d_wgrad_bf16", x, ldx, dw, dy, lddy, N, D, H, W, Cin, Cout, k, stride, pad, ws, ws_bytes, stream);
+    if (rc) return rc;
+    hipStream_t st = c.st;
     if (db) {
-        int rc = channel_sums(dy, lddy, vout, Cout, nullptr, nullptr, db, accumulate, ws, ws_bytes, st);
+        rc = channel_sums(dy, lddy, c.vout(), Cout, nullptr, nullptr, db, accumulate, ws, ws_bytes, st);
         if (rc) return rc;
     }
-    const bool al16 = ((uintptr_t)x % 16) == 0 && ((uintptr_t)dy % 16) == 0, al8 = ((uintptr_t)x % 8) == 0 && ((uintptr_t)dy % 8) == 0;
-    const int nb = native_wgrad(N, D, H, W, Cin, Cout, k, stride, pad, ldx, lddy);
-    if (nb == NB_K2S2W && al16 && !accumulate) {
-        float* part; int nstrips;
-        int rc = convt_wgrad_lowp(x, ldx, dy, lddy, N, D / 2, H / 2, W / 2, Cout, Cin, &part, &nstrips, ws, ws_bytes, st);
+    float* part; int nstrips;
+    switch (choose_b16(WGRAD_B16, conv_key(c, accumulate))) {
+    case NB_LOWP: return conv_wgrad_lowp(MATH_B16, dy, lddy, x, ldx, dw, N, D, H, W, Cin, Cout, k, stride, accumulate, ws, ws_bytes, st);
+    case NB_HEAD2: return head2_wgrad_lowp(dy, lddy, x, ldx, dw, N, D, H, W, Cin, accumulate, ws, ws_bytes, st);
+    case NB_STEM1K5: return stem1k5_wgrad_lowp(dy, lddy, x, dw, N, D, H, W, Cout, accumulate, ws, ws_bytes, st);
+    case NB_K2S2W:
+        rc = convt_wgrad_lowp(x, ldx, dy, lddy, N, D / 2, H / 2, W / 2, Cout, Cin, &part, &nstrips, ws, ws_bytes, st);
         if (rc) return rc;
         convt_wgrad_reduce(part, dw, nstrips, Cout, Cin, st);
         SEG_CHECK_LAUNCH();
         return MI355SEG_OK;
+    case NB_TINY: return tinypw_wgrad(dy, lddy, x, ldx, dw, c.vin(), Cin, Cout, accumulate, ws, ws_bytes, st);
+    case NB_PWL: return wgrad_strips_tail(pw_wgrad_lowp(dy, lddy, x, ldx, N, D, H, W, Cin, Cout, &part, &nstrips, ws, ws_bytes, st), part, nstrips, c, accumulate);
+    case NB_PW: return wgrad_strips_tail(pw_wgrad_mfma(dy, lddy, x, ldx, N, D, H, W, Cin, Cout, 1, &part, &nstrips, ws, ws_bytes, st), part, nstrips, c, accumulate);
+    case NB_STEM4: return stem4_wgrad_lowp(dy, lddy, x, dw, N, D, H, W, Cout, accumulate, ws, ws_bytes, st);
+    case NB_STEM: return stem_wgrad(dy, lddy, x, ldx, dw, N, D, H, W, Cin, Cout, accumulate, ws, ws_bytes, st);
+    case NB_HEADPW: return headpw_wgrad_lowp(dy, lddy, x, ldx, dw, c.vin(), Cin, Cout, accumulate, ws, ws_bytes, st);
+    case NB_HEAD: return head_wgrad(dy, lddy, x, ldx, dw, N, D, H, W, Cin, Cout, accumulate, ws, ws_bytes, st);
+    case NB_SMALLCIN: return smallcin_wgrad(dy, lddy, x, ldx, dw, N, D, H, W, Cin, Cout, k, stride, pad, accumulate, ws, ws_bytes, st);
+    case NB_SMALLCOUT: return smallcout_wgrad(dy, lddy, x, ldx, dw, N, D, H, W, Cin, Cout, k, stride, pad, accumulate, ws, ws_bytes, st);
+    case NB_GW: return conv_gwgrad(dy, lddy, x, ldx, dw, N, D, H, W, Cin, Cout, k, stride, pad, accumulate, ws, ws_bytes, st);
+    default:
+        return staged(c, true, true, [&](float* xf, float* dyf, void* rest, size_t rest_bytes) {
+            return mi355seg_conv3d_wgrad_f32(dyf, Cout, xf, Cin, dw, nullptr, N, D, H, W, Cin, Cout, k, stride, pad, accumulate, rest, rest_bytes, stream);
+        });
     }
-    if (nb == NB_STEM1K5 && ((uintptr_t)dy % 16) == 0)
-        return stem1k5_wgrad_lowp(dy, lddy, x, dw, N, D, H, W, Cout, accumulate, ws, ws_bytes, st);
-    if (nb == NB_HEAD2 && ((uintptr_t)x % 16) == 0 && ((uintptr_t)dy % 4) == 0)
-        return head2_wgrad_lowp(dy, lddy, x, ldx, dw, N, D, H, W, Cin, accumulate, ws, ws_bytes, st);
-    if (nb == NB_LOWP && al16) return conv_wgrad_lowp(MATH_B16, dy, lddy, x, ldx, dw, N, D, H, W, Cin, Cout, k, stride, accumulate, ws, ws_bytes, st);
-    if (nb == NB_PWL && al16) {
-        float* part; int nstrips;
-        int rc = pw_wgrad_lowp(dy, lddy, x, ldx, N, D, H, W, Cin, Cout, &part, &nstrips, ws, ws_bytes, st);
-        if (rc) return rc;
-        wgrad_reduce(part, dw, nstrips, 1, Cin, Cout, accumulate, st);
-        SEG_CHECK_LAUNCH();
-        return MI355SEG_OK;
-    }
-    if ((nb == NB_PW || (nb == NB_PWL && pw_wgrad_supported((long long)N * D * H * W, Cin, Cout, 1, ldx, lddy))) && al8) {
-        float* part; int nstrips;
-        int rc = pw_wgrad_mfma(dy, lddy, x, ldx, N, D, H, W, Cin, Cout, 1, &part, &nstrips, ws, ws_bytes, st);
-        if (rc) return rc;
-        wgrad_reduce(part, dw, nstrips, 1, Cin, Cout, accumulate, st);
-        SEG_CHECK_LAUNCH();
-        return MI355SEG_OK;
-    }
-    if (nb == NB_TINY) return tinypw_wgrad(dy, lddy, x, ldx, dw, vin, Cin, Cout, accumulate, ws, ws_bytes, st);
-    if (nb == NB_STEM4 && al16) return stem4_wgrad_lowp(dy, lddy, x, dw, N, D, H, W, Cout, accumulate, ws, ws_bytes, st);
-    if ((nb == NB_STEM || nb == NB_STEM4) && al8) return stem_wgrad(dy, lddy, x, ldx, dw, N, D, H, W, Cin, Cout, accumulate, ws, ws_bytes, st);
-    if (nb == NB_HEADPW && al16) return headpw_wgrad_lowp(dy, lddy, x, ldx, dw, vin, Cin, Cout, accumulate, ws, ws_bytes, st);
-    if ((nb == NB_HEAD || nb == NB_HEADPW) && al8) return head_wgrad(dy, lddy, x, ldx, dw, N, D, H, W, Cin, Cout, accumulate, ws, ws_bytes, st);
-    if (nb == NB_SMALLCIN && al8) return smallcin_wgrad(dy, lddy, x, ldx, dw, N, D, H, W, Cin, Cout, k, stride, pad, accumulate, ws, ws_bytes, st);
-    if (nb == NB_SMALLCOUT && al8) return smallcout_wgrad(dy, lddy, x, ldx, dw, N, D, H, W, Cin, Cout, k, stride, pad, accumulate, ws, ws_bytes, st);
-    if (nb == NB_GW && al8) return conv_gwgrad(dy, lddy, x, ldx, dw, N, D, H, W, Cin, Cout, k, stride, pad, accumulate, ws, ws_bytes, st);
-    Carver cv(ws);
-    float* xf = cv.take<float>((size_t)vin * Cin);
-    float* dyf = cv.take<float>((size_t)vout * Cout);
-    const size_t used = cv.used();
-    SEG_CHECK_WS(used + mi355seg_conv3d_ws_bytes(N, D, H, W, Cin, Cout, k, stride, pad), ws_bytes);
-    cast_rows(x, ldx, xf, Cin, vin, Cin, st);
-    cast_rows(dy, lddy, dyf, Cout, vout, Cout, st);
-    SEG_CHECK_LAUNCH();
-    return mi355seg_conv3d_wgrad_f32(dyf, Cout, xf, Cin, dw, nullptr, N, D, H, W, Cin, Cout, k, stride, pad, accumulate, (char*)ws + used, ws_bytes - used, stream);
 }
 
 // dtype casts of [rows, C] matrices with row pitches (autocast boundaries: fp32 <-> bf16 activations)

@@ -46,10 +46,6 @@ void pack_w_dgrad(const float* w, float* wd, int Cout, int Cin, int T, int flip,
     hipLaunchKernelGGL(pack_w_dgrad_kernel, dim3(grid), dim3(256), 0, st, w, wd, Cout, Cin, T, flip);
 }
 
-struct ConvGeom {
-    int N, D, H, W, Cin, Cout, k, stride, pad, Do, Ho, Wo;
-};
-
 // ---------------------------------------------------------------- forward
 // one thread per (output voxel, cout); VOX_PER_THREAD voxels along W share weight loads.
 __global__ __launch_bounds__(256) void conv_fwd_generic_kernel(const float* __restrict__ x, int ldx,
@@ -406,15 +402,33 @@ int conv_wgrad_generic(const float* dy, int lddy, const float* x, int ldx, float
     return MI355SEG_OK;
 }
 
-static int check_geom(ConvGeom* g, const char* who) {
-    SEG_CHECK_ARG(g->N > 0 && g->D > 0 && g->H > 0 && g->W > 0 && g->Cin > 0 && g->Cout > 0, "%s: non-positive extent", who);
-    SEG_CHECK_ARG(g->k >= 1 && g->k <= 16 && g->stride >= 1 && g->pad >= 0, "%s: bad k/stride/pad %d/%d/%d", who, g->k,
-                  g->stride, g->pad);
-    SEG_CHECK_ARG(g->D + 2 * g->pad >= g->k && g->H + 2 * g->pad >= g->k && g->W + 2 * g->pad >= g->k,
-                  "%s: kernel larger than padded input", who);
-    g->Do = (g->D + 2 * g->pad - g->k) / g->stride + 1;
-    g->Ho = (g->H + 2 * g->pad - g->k) / g->stride + 1;
-    g->Wo = (g->W + 2 * g->pad - g->k) / g->stride + 1;
+int conv_call(ConvCall* c, const char* who, const void* x, int ldx, const void* w, const void* y, int ldy, int N, int D, int H, int W,
+              int Cin, int Cout, int k, int stride, int pad, void* ws, size_t ws_bytes, void* stream) {
+    SEG_CHECK_ARG(N > 0 && D > 0 && H > 0 && W > 0 && Cin > 0 && Cout > 0, "%s: non-positive extent", who);
+    SEG_CHECK_ARG(k >= 1 && k <= 16 && stride >= 1 && pad >= 0, "%s: bad k/stride/pad %d/%d/%d", who, k, stride, pad);
+    SEG_CHECK_ARG(D + 2 * pad >= k && H + 2 * pad >= k && W + 2 * pad >= k, "%s: kernel larger than padded input", who);
+    SEG_CHECK_ARG(x && w && y && ldx >= Cin && ldy >= Cout, "%s: null pointer or pitch < channels", who);
+    *c = ConvCall{{N, D, H, W, Cin, Cout, k, stride, pad, (D + 2 * pad - k) / stride + 1, (H + 2 * pad - k) / stride + 1, (W + 2 * pad - k) / stride + 1},
+                  ldx, ldy, x, y, w, ws, ws_bytes, (hipStream_t)stream};
+    return MI355SEG_OK;
+}
+
+size_t ladder_ws_bytes(const Rung* r, const ConvGeom& g) {
+    const ConvKey d = dense_key(g);
+    size_t most = 0;
+    for (;; ++r) {
+        if (r->ws && (r->reach ? r->reach(g) : !r->fits || (r->fits(d) && (!r->aligned || r->aligned(d))))) {
+            const size_t need = r->ws(g);
+            if (need > most) most = need;
+        }
+        if (!r->fits) return most;
+    }
+}
+
+int wgrad_strips_tail(int rc, const float* part, int nstrips, const ConvCall& c, int accumulate) {
+    if (rc) return rc;
+    wgrad_reduce(part, c.dw(), nstrips, 1, c.g.Cin, c.g.Cout, accumulate, c.st);
+    SEG_CHECK_LAUNCH();
     return MI355SEG_OK;
 }
 
@@ -490,6 +504,72 @@ static int patch_embed_matrix(const float* x, int ldx, int N, int D, int H, int 
 }  // namespace seg
 using namespace seg;
 
+// ---- the three fp32 choosers.  A ladder is read top down and the first rung whose test holds serves the call (choose); the test is the
+// whole precondition of the launcher behind the family's switch case -- geometry, pitches, the addresses modulo 16 (ax: x or dx, ay: y or
+// dy), the conv-math policy -- so a call one rung cannot take goes on to the next, down to the generic kernels, which take everything.
+// Where the kernel's own file picks the fine variant (igemm tiles, stem kernels, smallcin, the lowp forms) it records the fine path code.
+enum { F_IGEMM_X3, F_IGEMM_F32, F_PATCH, F_GATHER, F_HEADK, F_STEMK, F_STEM, F_TINYPW, F_HEAD, F_K2S2_CONVT, F_LOWP, F_WGRAD_MFMA, F_PW_LOWP,
+       F_PW_MFMA, F_SMALLCIN, F_SMALLCOUT, F_GWGRAD, F_GENERIC };
+static bool any_geom(const ConvGeom&) { return true; }
+static bool x3() { return f32_conv_policy() != MATH_F32; }
+// conservative: sized for every math, both igemm passes and the stride-1 k3 / k5 / k1 weight-gradient plans, whatever the pitches
+static size_t ws_mfma(const ConvGeom& g) { return conv_mfma_ws_bytes(GEOM9(g)); }
+static size_t ws_gather(const ConvGeom& g) { return conv_gather_ws_bytes(GEOM9(g)); }       // conservative: counted for every geometry its shape test admits
+static size_t ws_patch(const ConvGeom& g) { return patch_embed_ws_bytes(g.N, g.D, g.H, g.W, g.Cin, g.Cout, g.k); }
+static size_t ws_small(const ConvGeom& g) { return small_ws_bytes(g.Cin, g.Cout, g.k); }
+static size_t ws_small_wgrad(const ConvGeom& g) { return small_wgrad_ws_bytes(g.Cin, g.Cout, g.k); }
+static size_t ws_generic(const ConvGeom& g) { return conv_generic_ws_bytes(GEOM9(g)); }
+
+static const Rung FWD_F32[] = {
+    {F_IGEMM_X3, RUNG(x3() && conv_mfma_supported(MATH_X3, GEOM9(g), k.ldx, k.ldy) && k.ax == 0), ws_mfma, any_geom},
+    {F_IGEMM_F32, RUNG(conv_mfma_supported(MATH_F32, GEOM9(g), k.ldx, k.ldy) && k.ax == 0), ws_mfma, any_geom},
+    {F_PATCH, RUNG(patch_embed_supported(g.D, g.H, g.W, g.Cin, g.k, g.stride, g.pad)), ws_patch},
+    {F_GATHER, RUNG(conv_gather_fwd_supported(MATH_F32, GEOM9(g), k.ldx, k.ldy) && k.ax == 0), ws_gather, any_geom},
+    {F_HEADK, RUNG(headk_supported(SHAPE5(g), k.ldx, k.ldy, false) && k.ax == 0 && k.ay % 8 == 0), WS(headk_ws_bytes(g.Cin, g.Cout, g.k))},
+    {F_STEMK, RUNG(stemk_supported(SHAPE5(g), k.ldx, k.ldy) && k.ax % 8 == 0 && k.ay == 0), WS(headk_ws_bytes(g.Cout, g.Cin, g.k))},
+    {F_STEM, RUNG(stem_supported(SHAPE5(g), k.ldy)), ws_small},
+    {F_TINYPW, RUNG(tinypw_supported(SHAPE5(g)))},
+    {F_HEAD, RUNG(head_supported(SHAPE5(g), k.ldx)), ws_small},
+    {F_GENERIC, nullptr, ws_generic}};
+// (k3 s1 p1 and its kin: the input gradient is the same convolution with flipped taps and Cin <-> Cout swapped)
+static const Rung DGRAD_F32[] = {
+    {F_IGEMM_X3, RUNG(x3() && conv_mfma_supported(MATH_X3, GEOM9_T(g), k.ldy, k.ldx) && k.ay == 0), ws_mfma, any_geom},
+    {F_IGEMM_F32, RUNG(conv_mfma_supported(MATH_F32, GEOM9_T(g), k.ldy, k.ldx) && k.ay == 0), ws_mfma, any_geom},
+    {F_GATHER, RUNG(conv_gather_dgrad_supported(MATH_F32, GEOM9(g), k.ldy, k.ldx) && k.ay == 0), ws_gather, any_geom},
+    {F_HEADK, RUNG(headk_supported(SHAPE5(g), k.ldy, k.ldx, true) && k.ay % 8 == 0 && k.ax == 0), WS(headk_ws_bytes(g.Cin, g.Cout, g.k))},
+    {F_HEAD, RUNG(head_supported(SHAPE5(g), k.ldx))},
+    {F_TINYPW, RUNG(tinypw_supported(SHAPE5(g)))},
+    // k2 s2 p0 (V-Net's down-convolutions, vnet3d.py:66): the windows do not overlap, so the input gradient IS the forward of
+    // ConvTranspose3d k2 s2 with the same weight tensor read as (Cin_T = Cout, Cout_T = Cin, 2, 2, 2) -- also for Cin = 16,
+    // which the 32-column tiles of the gather dgrad cannot cut (the transposed conv tiles the flat (child, channel) axis).
+    // Its packed weights are the first part of the gather term, which every k2 s2 geometry carries.
+    {F_K2S2_CONVT, RUNG(g.k == 2 && g.stride == 2 && g.pad == 0 && g.D % 2 == 0 && g.H % 2 == 0 && g.W % 2 == 0 && k.ay == 0 &&
+                        convt_mfma_supported(MATH_F32, g.N, g.D / 2, g.H / 2, g.W / 2, g.Cout, g.Cin, k.ldy, k.ldx)), ws_gather, any_geom},
+    {F_GENERIC, nullptr, ws_generic}};
+static const Rung WGRAD_F32[] = {
+    {F_PATCH, RUNG(patch_embed_supported(g.D, g.H, g.W, g.Cin, g.k, g.stride, g.pad)), ws_patch},
+    // conservative: counted for every geometry and math
+    {F_LOWP, RUNG(x3() && wgrad_lowp_supported(MATH_X3, GEOM9(g), k.ldx, k.ldy) && k.ax == 0 && k.ay == 0), WS(wgrad_lowp_ws_bytes_geom(GEOM9(g))), any_geom},
+    {F_WGRAD_MFMA, RUNG(wgrad_mfma_supported(GEOM9(g), k.ldx, k.ldy) && k.ax == 0 && k.ay == 0), ws_mfma, any_geom},
+    // conservative: counted for every pointwise geometry and math
+    {F_PW_LOWP, RUNG(pointwise(g) && x3() && pw_wgrad_lowp_supported(conv_vin(g), g.Cin, g.Cout, k.ldx, k.ldy, 4) && k.ax == 0 && k.ay == 0),
+     WS(pw_wgrad_lowp_ws_bytes(conv_vin(g), g.Cin, g.Cout)), pointwise},
+    {F_PW_MFMA, RUNG(pointwise(g) && pw_wgrad_supported(conv_vin(g), g.Cin, g.Cout, 1, k.ldx, k.ldy) && k.ax == 0 && k.ay == 0), ws_mfma, any_geom},
+    {F_TINYPW, RUNG(tinypw_supported(SHAPE5(g)))},
+    {F_STEM, RUNG(stem_supported(SHAPE5(g), k.ldy)), ws_small},
+    {F_HEAD, RUNG(head_supported(SHAPE5(g), k.ldx)), ws_small},
+    {F_HEADK, RUNG(headk_wgrad_supported(SHAPE5(g), k.ldx, k.ldy) && k.ax == 0 && k.ay % 8 == 0), WS(headk_wgrad_ws_bytes(g.N, g.D, g.H, g.W, g.Cin, g.k))},
+    {F_SMALLCIN, RUNG(smallcin_wgrad_supported(g.Cin, g.Cout, g.k)), ws_small_wgrad},
+    {F_SMALLCOUT, RUNG(smallcout_wgrad_supported(g.Cin, g.Cout, g.k, k.ldx) && k.ax == 0), ws_small_wgrad},
+    // conservative: counted for every geometry its plan admits, whatever the pitches
+    {F_GWGRAD, RUNG(gwgrad_supported(GEOM9(g), k.ldx, k.ldy) && k.ax == 0 && k.ay == 0), WS(gwgrad_ws_bytes(GEOM9(g))), any_geom},
+    {F_GENERIC, nullptr, ws_generic}};
+static int choose(const Rung* r, const ConvKey& k) {
+    while (r->fits && !r->fits(k)) ++r;
+    return r->family;
+}
+static bool is_igemm(int family) { return family == F_IGEMM_X3 || family == F_IGEMM_F32; }
+
 extern "C" {
 
 int mi355seg_set_conv_math(int mode) {
@@ -506,24 +586,11 @@ int mi355seg_set_x3_shape(int shape) {
 int mi355seg_get_x3_shape(void) { return g_x3_shape; }
 int mi355seg_last_conv_path(void) { return g_conv_path; }
 
+// the most any rung that the geometry can reach, under some pitch, alignment and math, takes from the workspace
 size_t mi355seg_conv3d_ws_bytes(int N, int D, int H, int W, int Cin, int Cout, int k, int stride, int pad) {
-    size_t a = conv_generic_ws_bytes(N, D, H, W, Cin, Cout, k, stride, pad);
-    size_t b = conv_mfma_ws_bytes(N, D, H, W, Cin, Cout, k, stride, pad);
-    size_t c = (stem_supported(Cin, Cout, k, stride, pad, 4) || head_supported(Cin, Cout, k, stride, pad, 4)) ? small_ws_bytes(Cin, Cout, k) : 0;
-    size_t d = gwgrad_ws_bytes(N, D, H, W, Cin, Cout, k, stride, pad);
-    if ((smallcin_wgrad_supported(Cin, Cout, k) || smallcout_wgrad_supported(Cin, Cout, k, 4)) && small_wgrad_ws_bytes(Cin, Cout, k) > d)
-        d = small_wgrad_ws_bytes(Cin, Cout, k);
-    size_t e = conv_gather_ws_bytes(N, D, H, W, Cin, Cout, k, stride, pad);
-    if (wgrad_lowp_ws_bytes_geom(N, D, H, W, Cin, Cout, k, stride, pad) > e) e = wgrad_lowp_ws_bytes_geom(N, D, H, W, Cin, Cout, k, stride, pad);
-    if (b > a) a = b;
-    if (d > a) a = d;
-    if (e > a) a = e;
-    if (headk_supported(Cin, Cout, k, stride, pad, 4, 4, true) && headk_ws_bytes(Cin, Cout, k) > a) a = headk_ws_bytes(Cin, Cout, k);
-    if (patch_embed_supported(D, H, W, Cin, k, stride, pad) && patch_embed_ws_bytes(N, D, H, W, Cin, Cout, k) > a) a = patch_embed_ws_bytes(N, D, H, W, Cin, Cout, k);
-    if (stemk_supported(Cin, Cout, k, stride, pad, 2, 4) && headk_ws_bytes(Cout, Cin, k) > a) a = headk_ws_bytes(Cout, Cin, k);
-    if (headk_wgrad_supported(Cin, Cout, k, stride, pad, 4, 2) && headk_wgrad_ws_bytes(N, D, H, W, Cin, k) > a) a = headk_wgrad_ws_bytes(N, D, H, W, Cin, k);
-    if (k == 1 && stride == 1 && pad == 0 && pw_wgrad_lowp_ws_bytes((long long)N * D * H * W, Cin, Cout) > a) a = pw_wgrad_lowp_ws_bytes((long long)N * D * H * W, Cin, Cout);
-    return a > c ? a : c;
+    const ConvGeom g{N, D, H, W, Cin, Cout, k, stride, pad, 0, 0, 0};
+    const size_t f = ladder_ws_bytes(FWD_F32, g), d = ladder_ws_bytes(DGRAD_F32, g), w = ladder_ws_bytes(WGRAD_F32, g);
+    return f > d ? (f > w ? f : w) : (d > w ? d : w);
 }
 
 // ---- inference forward with eval-mode BatchNorm and the activation folded in (predict.py:79-81,133: model.eval() forward):
@@ -531,21 +598,20 @@ size_t mi355seg_conv3d_ws_bytes(int N, int D, int H, int W, int Cin, int Cout, i
 // activation runs in the MFMA kernel's epilogue -- no normalise pass.  Only the matrix-core layers have this form; the caller
 // asks first and keeps the two-pass form (convolution, then norm_act_fwd with the running statistics) for the rest.
 int mi355seg_conv3d_fused_supported_f32(int N, int D, int H, int W, int Cin, int Cout, int k, int stride, int pad, int ldx, int ldy) {
-    const int pol = f32_conv_policy();
-    return (pol != MATH_F32 && conv_mfma_supported(pol, N, D, H, W, Cin, Cout, k, stride, pad, ldx, ldy)) ||
-           conv_mfma_supported(MATH_F32, N, D, H, W, Cin, Cout, k, stride, pad, ldx, ldy);
+    return is_igemm(choose(FWD_F32, ConvKey{{N, D, H, W, Cin, Cout, k, stride, pad, 0, 0, 0}, ldx, ldy, 0, 0, 0}));
 }
 int mi355seg_conv3d_fwd_fused_f32(const float* x, int ldx, const float* w, const float* oscale, const float* oshift, int act, float slope,
                                   float* y, int ldy, int N, int D, int H, int W, int Cin, int Cout, int k, int stride, int pad,
                                   void* ws, size_t ws_bytes, void* stream) {
-    ConvGeom g{N, D, H, W, Cin, Cout, k, stride, pad, 0, 0, 0};
-    int rc = check_geom(&g, "conv3d_fwd_fused");
+    ConvCall c;
+    int rc = conv_call(&c, "conv3d_fwd_fused", x, ldx, w, y, ldy, N, D, H, W, Cin, Cout, k, stride, pad, ws, ws_bytes, stream);
     if (rc) return rc;
-    SEG_CHECK_ARG(x && w && y && oscale && oshift && ldx >= Cin && ldy >= Cout, "conv3d_fwd_fused: null pointer or pitch < channels");
-    SEG_CHECK_ARG(mi355seg_conv3d_fused_supported_f32(N, D, H, W, Cin, Cout, k, stride, pad, ldx, ldy), "conv3d_fwd_fused: no fused form for this shape (ask mi355seg_conv3d_fused_supported_f32)");
-    const int pol = f32_conv_policy();
-    const int math = (pol != MATH_F32 && conv_mfma_supported(pol, N, D, H, W, Cin, Cout, k, stride, pad, ldx, ldy)) ? pol : MATH_F32;
-    return conv_fwd_mfma(math, x, ldx, w, oshift, y, ldy, N, D, H, W, Cin, Cout, k, /*dgrad=*/0, nullptr, nullptr, ws, ws_bytes, (hipStream_t)stream, oscale, act, slope);
+    SEG_CHECK_ARG(oscale && oshift, "conv3d_fwd_fused: null pointer or pitch < channels");
+    const int family = choose(FWD_F32, conv_key(c));           // (only the igemm rungs have the fused form: a misaligned x stays refused)
+    SEG_CHECK_ARG(is_igemm(family), "conv3d_fwd_fused: no fused form for this shape or alignment (ask mi355seg_conv3d_fused_supported_f32)");
+    MfmaOpts o;
+    o.oscale = oscale; o.act = act; o.slope = slope;
+    return conv_fwd_mfma(family == F_IGEMM_X3 ? MATH_X3 : MATH_F32, x, ldx, w, oshift, y, ldy, N, D, H, W, Cin, Cout, k, /*dgrad=*/0, nullptr, nullptr, ws, ws_bytes, c.st, o);
 }
 
 int mi355seg_conv3d_fwd_f32(const float* x, int ldx, const float* w, const float* bias,
@@ -579,68 +645,85 @@ int mi355seg_conv3d_amax_use_f32(int N, int D, int H, int W, int Cin, int Cout, 
 
 // y_amax (may be NULL): max |y| max-combined into a zeroed device scalar by the paths that can do it inside their kernel; *amax_done says
 // whether the path that ran did
-static int conv3d_fwd_impl(const float* x, int ldx, const float* w, const float* bias,
-                            float* y, int ldy, int N, int D, int H, int W, int Cin, int Cout,
-                            int k, int stride, int pad, double* stats_sum, double* stats_sq, const float* x_amax, const float* w_amax,
-                            void* ws, size_t ws_bytes, void* stream, float* y_amax, bool* amax_done) {
-    ConvGeom g{N, D, H, W, Cin, Cout, k, stride, pad, 0, 0, 0};
-    int rc = check_geom(&g, "conv3d_fwd");
-    if (rc) return rc;
-    SEG_CHECK_ARG(x && w && y && ldx >= Cin && ldy >= Cout, "conv3d_fwd: null pointer or pitch < channels");
+static int conv3d_fwd_impl(const ConvCall& c, const float* bias, double* stats_sum, double* stats_sq, const float* x_amax, const float* w_amax,
+                           float* y_amax, bool* amax_done) {
     SEG_CHECK_ARG((stats_sum == nullptr) == (stats_sq == nullptr), "conv3d_fwd: stats_sum/stats_sq must come together");
-    hipStream_t st = (hipStream_t)stream;
-    const int pol = f32_conv_policy();
-    // (the matrix-core branches are recorded inside conv_fwd_mfma: MI355SEG_PATH_FWD_MFMA_X3S / _X3 / _F32)
-    if (pol != MATH_F32 && conv_mfma_supported(pol, N, D, H, W, Cin, Cout, k, stride, pad, ldx, ldy)) {
+    const ConvGeom& g = c.g;
+    const float* x = (const float*)c.x; const float* w = (const float*)c.w; float* y = (float*)c.y;
+    const int ldx = c.ldx, ldy = c.ldy;
+    switch (choose(FWD_F32, conv_key(c))) {
+    case F_IGEMM_X3: {            // (the matrix-core branches are recorded inside conv_fwd_mfma: MI355SEG_PATH_FWD_MFMA_X3S / _X3 / _F32)
+        MfmaOpts o;
+        o.x_amax = x_amax; o.w_amax = w_amax; o.y_amax = y_amax;
         if (y_amax) *amax_done = true;
-        return conv_fwd_mfma(pol, x, ldx, w, bias, y, ldy, N, D, H, W, Cin, Cout, k, /*dgrad=*/0, stats_sum, stats_sq, ws, ws_bytes, st,
-                             nullptr, 0, 0.f, nullptr, x_amax, w_amax, nullptr, 0, nullptr, nullptr, y_amax);
+        return conv_fwd_mfma(MATH_X3, x, ldx, w, bias, y, ldy, g.N, g.D, g.H, g.W, g.Cin, g.Cout, g.k, /*dgrad=*/0, stats_sum, stats_sq, c.ws, c.ws_bytes, c.st, o);
     }
-    if (conv_mfma_supported(MATH_F32, N, D, H, W, Cin, Cout, k, stride, pad, ldx, ldy)) {
-        return conv_fwd_mfma(MATH_F32, x, ldx, w, bias, y, ldy, N, D, H, W, Cin, Cout, k, /*dgrad=*/0, stats_sum, stats_sq, ws, ws_bytes, st);
-    }
-    if (patch_embed_supported(D, H, W, Cin, k, stride, pad)) {
+    case F_IGEMM_F32:
+        return conv_fwd_mfma(MATH_F32, x, ldx, w, bias, y, ldy, g.N, g.D, g.H, g.W, g.Cin, g.Cout, g.k, /*dgrad=*/0, stats_sum, stats_sq, c.ws, c.ws_bytes, c.st);
+    case F_PATCH: {
         float* A; void* rest; size_t rest_bytes;
         note_conv_path(MI355SEG_PATH_FWD_PATCH_EMBED);
-        rc = patch_embed_matrix(x, ldx, N, D, H, W, Cin, k, ws, ws_bytes, &A, &rest, &rest_bytes, st);
+        int rc = patch_embed_matrix(x, ldx, g.N, g.D, g.H, g.W, g.Cin, g.k, c.ws, c.ws_bytes, &A, &rest, &rest_bytes, c.st);
         if (rc) return rc;
-        const int M = N * (D / k) * (H / k) * (W / k), K = Cin * k * k * k;
-        rc = mi355seg_gemm_f32(A, K, 1, 0, 0, w, 1, K, 0, 0, y, ldy, 0, 0, bias, M, Cout, K, 1, 1, 1.f, 0, 0, rest, rest_bytes, stream);
-        if (rc || !stats_sum) return rc;
-        return channel_sums(y, ldy, M, Cout, stats_sum, stats_sq, nullptr, 0, ws, ws_bytes, st);
+        const int M = (int)c.vout(), K = g.Cin * g.k * g.k * g.k;
+        rc = mi355seg_gemm_f32(A, K, 1, 0, 0, w, 1, K, 0, 0, y, ldy, 0, 0, bias, M, g.Cout, K, 1, 1, 1.f, 0, 0, rest, rest_bytes, c.st);
+        return conv_stats_tail<float>(rc, c, stats_sum, stats_sq);
     }
-    if (conv_gather_fwd_supported(MATH_F32, N, D, H, W, Cin, Cout, k, stride, pad, ldx, ldy) && ((uintptr_t)x % 16) == 0) {
+    case F_GATHER:
         note_conv_path(MI355SEG_PATH_FWD_GATHER);
-        return conv_gather_fwd_mfma(MATH_F32, x, ldx, w, bias, y, ldy, N, D, H, W, Cin, Cout, k, stride, pad, stats_sum, stats_sq, ws, ws_bytes, st);
-    }
-    if (headk_supported(Cin, Cout, k, stride, pad, ldx, ldy, false) && ((uintptr_t)x % 16) == 0 && ((uintptr_t)y % 8) == 0) {
+        return conv_gather_fwd_mfma(MATH_F32, x, ldx, w, bias, y, ldy, GEOM9(g), stats_sum, stats_sq, c.ws, c.ws_bytes, c.st);
+    case F_HEADK:
         note_conv_path(MI355SEG_PATH_FWD_HEADK);
-        rc = headk_conv(false, x, ldx, w, bias, y, ldy, N, D, H, W, Cin, k, ws, ws_bytes, st);
-        if (rc || !stats_sum) return rc;
-        return channel_sums(y, ldy, (long long)N * D * H * W, Cout, stats_sum, stats_sq, nullptr, 0, ws, ws_bytes, st);
-    }
-    if (stemk_supported(Cin, Cout, k, stride, pad, ldx, ldy) && ((uintptr_t)x % 8) == 0 && ((uintptr_t)y % 16) == 0) {
+        return conv_stats_tail<float>(headk_conv(false, x, ldx, w, bias, y, ldy, g.N, g.D, g.H, g.W, g.Cin, g.k, c.ws, c.ws_bytes, c.st), c, stats_sum, stats_sq);
+    case F_STEMK:
         note_conv_path(MI355SEG_PATH_FWD_STEMK);
-        rc = stemk_fwd(x, ldx, w, bias, y, ldy, N, D, H, W, Cin, Cout, ws, ws_bytes, st);
-        if (rc || !stats_sum) return rc;
-        return channel_sums(y, ldy, (long long)N * D * H * W, Cout, stats_sum, stats_sq, nullptr, 0, ws, ws_bytes, st);
-    }
-    if (stem_supported(Cin, Cout, k, stride, pad, ldy))          // (stem_fwd records which of its kernels: MI355SEG_PATH_FWD_STEM_*)
-        return stem_fwd(x, ldx, w, bias, y, ldy, N, D, H, W, Cin, Cout, stats_sum, stats_sq, ws, ws_bytes, st, y_amax, amax_done);
-    if (tinypw_supported(Cin, Cout, k, stride, pad)) {
+        return conv_stats_tail<float>(stemk_fwd(x, ldx, w, bias, y, ldy, g.N, g.D, g.H, g.W, g.Cin, g.Cout, c.ws, c.ws_bytes, c.st), c, stats_sum, stats_sq);
+    case F_STEM:                  // (stem_fwd records which of its kernels: MI355SEG_PATH_FWD_STEM_*)
+        return stem_fwd(x, ldx, w, bias, y, ldy, g.N, g.D, g.H, g.W, g.Cin, g.Cout, stats_sum, stats_sq, c.ws, c.ws_bytes, c.st, y_amax, amax_done);
+    case F_TINYPW:
         note_conv_path(MI355SEG_PATH_FWD_TINYPW);
-        rc = tinypw_fwd(x, ldx, w, bias, y, ldy, (long long)N * D * H * W, Cin, Cout, st);
-        if (rc || !stats_sum) return rc;
-        return channel_sums(y, ldy, (long long)N * D * H * W, Cout, stats_sum, stats_sq, nullptr, 0, ws, ws_bytes, st);
-    }
-    if (head_supported(Cin, Cout, k, stride, pad, ldx)) {
+        return conv_stats_tail<float>(tinypw_fwd(x, ldx, w, bias, y, ldy, c.vin(), g.Cin, g.Cout, c.st), c, stats_sum, stats_sq);
+    case F_HEAD:
         note_conv_path(MI355SEG_PATH_FWD_HEAD);
-        rc = head_fwd(x, ldx, w, bias, y, ldy, N, D, H, W, Cin, Cout, st);
-        if (rc || !stats_sum) return rc;
-        return channel_sums(y, ldy, (long long)N * D * H * W, Cout, stats_sum, stats_sq, nullptr, 0, ws, ws_bytes, st);
+        return conv_stats_tail<float>(head_fwd(x, ldx, w, bias, y, ldy, g.N, g.D, g.H, g.W, g.Cin, g.Cout, c.st), c, stats_sum, stats_sq);
+    default:
+        note_conv_path(MI355SEG_PATH_FWD_GENERIC);
+        return conv_fwd_generic(x, ldx, w, bias, y, ldy, g, stats_sum, stats_sq, c.ws, c.ws_bytes, c.st);
     }
-    note_conv_path(MI355SEG_PATH_FWD_GENERIC);
-    return conv_fwd_generic(x, ldx, w, bias, y, ldy, g, stats_sum, stats_sq, ws, ws_bytes, st);
+}
+
+// bne (may be NULL): the norm backward's column sums of the layer in front, taken from the epilogue where the split igemm rung serves the call
+static int conv3d_dgrad_impl(const ConvCall& c, const float* dy_amax, const float* w_amax, BnBwdEpi* bne) {
+    const ConvGeom& g = c.g;
+    const float* dy = (const float*)c.y; const float* w = (const float*)c.w; float* dx = (float*)c.x;
+    const int lddy = c.ldy, lddx = c.ldx;
+    switch (choose(DGRAD_F32, conv_key(c))) {
+    case F_IGEMM_X3: {
+        MfmaOpts o;
+        o.bne = bne; o.x_amax = dy_amax; o.w_amax = w_amax;
+        return conv_fwd_mfma(MATH_X3, dy, lddy, w, nullptr, dx, lddx, g.N, g.D, g.H, g.W, g.Cout, g.Cin, g.k, /*dgrad=*/1, nullptr, nullptr, c.ws, c.ws_bytes, c.st, o);
+    }
+    case F_IGEMM_F32:
+        return conv_fwd_mfma(MATH_F32, dy, lddy, w, nullptr, dx, lddx, g.N, g.D, g.H, g.W, g.Cout, g.Cin, g.k, /*dgrad=*/1, nullptr, nullptr, c.ws, c.ws_bytes, c.st);
+    case F_GATHER:
+        note_conv_path(MI355SEG_PATH_DGRAD_GATHER);
+        return conv_gather_dgrad_mfma(MATH_F32, dy, lddy, w, dx, lddx, GEOM9(g), c.ws, c.ws_bytes, c.st);
+    case F_HEADK:
+        note_conv_path(MI355SEG_PATH_DGRAD_HEADK);
+        return headk_conv(true, dy, lddy, w, nullptr, dx, lddx, g.N, g.D, g.H, g.W, g.Cin, g.k, c.ws, c.ws_bytes, c.st);
+    case F_HEAD:
+        note_conv_path(MI355SEG_PATH_DGRAD_HEAD);
+        return head_dgrad(dy, lddy, w, dx, lddx, g.N, g.D, g.H, g.W, g.Cin, g.Cout, c.st);
+    case F_TINYPW:
+        note_conv_path(MI355SEG_PATH_DGRAD_TINYPW);
+        return tinypw_dgrad(dy, lddy, w, dx, lddx, c.vin(), g.Cin, g.Cout, c.st);
+    case F_K2S2_CONVT:
+        note_conv_path(MI355SEG_PATH_DGRAD_K2S2_CONVT);
+        return convt_fwd_mfma(MATH_F32, dy, lddy, w, nullptr, dx, lddx, g.N, g.D / 2, g.H / 2, g.W / 2, g.Cout, g.Cin, c.ws, c.ws_bytes, c.st);
+    default:
+        note_conv_path(MI355SEG_PATH_DGRAD_GENERIC);
+        return conv_dgrad_generic(dy, lddy, w, dx, lddx, g, c.ws, c.ws_bytes, c.st);
+    }
 }
 
 extern "C" {
@@ -649,7 +732,9 @@ int mi355seg_conv3d_fwd_ax_f32(const float* x, int ldx, const float* w, const fl
                             float* y, int ldy, int N, int D, int H, int W, int Cin, int Cout,
                             int k, int stride, int pad, double* stats_sum, double* stats_sq, const float* x_amax, const float* w_amax,
                             void* ws, size_t ws_bytes, void* stream) {
-    return conv3d_fwd_impl(x, ldx, w, bias, y, ldy, N, D, H, W, Cin, Cout, k, stride, pad, stats_sum, stats_sq, x_amax, w_amax, ws, ws_bytes, stream, nullptr, nullptr);
+    ConvCall c;
+    int rc = conv_call(&c, "conv3d_fwd", x, ldx, w, y, ldy, N, D, H, W, Cin, Cout, k, stride, pad, ws, ws_bytes, stream);
+    return rc ? rc : conv3d_fwd_impl(c, bias, stats_sum, stats_sq, x_amax, w_amax, nullptr, nullptr);
 }
 
 // ---- conv2 of a double-conv block reading conv1's RAW output (r5): the norm + activation between them is a prologue of conv2's staging
@@ -667,13 +752,12 @@ int mi355seg_conv3d_fwd_yamax_ax_f32(const float* x, int ldx, const float* w, co
                                      int k, int stride, int pad, double* stats_sum, double* stats_sq, const float* x_amax, const float* w_amax,
                                      float* y_amax, void* ws, size_t ws_bytes, void* stream) {
     SEG_CHECK_ARG(y_amax, "conv3d_fwd_yamax: y_amax is null");
+    ConvCall c;
     bool done = false;
-    int rc = conv3d_fwd_impl(x, ldx, w, bias, y, ldy, N, D, H, W, Cin, Cout, k, stride, pad, stats_sum, stats_sq, x_amax, w_amax, ws, ws_bytes, stream, y_amax, &done);
+    int rc = conv_call(&c, "conv3d_fwd_yamax", x, ldx, w, y, ldy, N, D, H, W, Cin, Cout, k, stride, pad, ws, ws_bytes, stream);
+    if (!rc) rc = conv3d_fwd_impl(c, bias, stats_sum, stats_sq, x_amax, w_amax, y_amax, &done);
     if (rc || done) return rc;
-    ConvGeom g{N, D, H, W, Cin, Cout, k, stride, pad, 0, 0, 0};
-    rc = check_geom(&g, "conv3d_fwd_yamax");
-    if (rc) return rc;
-    tensor_amax(y, ldy, (long long)N * g.Do * g.Ho * g.Wo, Cout, nullptr, y_amax, (hipStream_t)stream);
+    tensor_amax(y, ldy, c.vout(), Cout, nullptr, y_amax, c.st);
     SEG_CHECK_LAUNCH();
     return MI355SEG_OK;
 }
@@ -684,16 +768,18 @@ int mi355seg_conv3d_fwd_pro_ax_f32(const float* x, int ldx, const float* pro_al,
                                    const float* w, const float* bias, float* y, int ldy, int N, int D, int H, int W, int Cin, int Cout,
                                    int k, int stride, int pad, double* stats_sum, double* stats_sq, const float* x_amax, const float* w_amax,
                                    void* ws, size_t ws_bytes, void* stream) {
-    ConvGeom g{N, D, H, W, Cin, Cout, k, stride, pad, 0, 0, 0};
-    int rc = check_geom(&g, "conv3d_fwd_pro");
+    ConvCall c;
+    int rc = conv_call(&c, "conv3d_fwd_pro", x, ldx, w, y, ldy, N, D, H, W, Cin, Cout, k, stride, pad, ws, ws_bytes, stream);
     if (rc) return rc;
-    SEG_CHECK_ARG(x && w && y && pro_al && pro_be && x_amax && ldx >= Cin && ldy >= Cout, "conv3d_fwd_pro: null pointer or pitch < channels");
+    SEG_CHECK_ARG(pro_al && pro_be && x_amax, "conv3d_fwd_pro: null pointer or pitch < channels");
     SEG_CHECK_ARG((stats_sum == nullptr) == (stats_sq == nullptr), "conv3d_fwd_pro: stats_sum/stats_sq must come together");
-    SEG_CHECK_ARG(mi355seg_conv3d_pro_supported_f32(N, D, H, W, Cin, Cout, k, stride, pad, pro_act) && conv_mfma_supported(MATH_X3, N, D, H, W, Cin, Cout, k, stride, pad, ldx, ldy),
+    // (only the split igemm rung has the prologue form: a misaligned x stays refused)
+    SEG_CHECK_ARG(mi355seg_conv3d_pro_supported_f32(N, D, H, W, Cin, Cout, k, stride, pad, pro_act) && choose(FWD_F32, conv_key(c)) == F_IGEMM_X3,
                   "conv3d_fwd_pro: no prologue form for this layer under the selected conv math (ask mi355seg_conv3d_pro_supported_f32)");
     ConvPro pro{pro_al, pro_be, pro_act, pro_slope};
-    return conv_fwd_mfma(MATH_X3, x, ldx, w, bias, y, ldy, N, D, H, W, Cin, Cout, k, /*dgrad=*/0, stats_sum, stats_sq, ws, ws_bytes, (hipStream_t)stream,
-                         nullptr, 0, 0.f, nullptr, x_amax, w_amax, nullptr, 0, nullptr, &pro, nullptr);
+    MfmaOpts o;
+    o.x_amax = x_amax; o.w_amax = w_amax; o.pro = &pro;
+    return conv_fwd_mfma(MATH_X3, x, ldx, w, bias, y, ldy, N, D, H, W, Cin, Cout, k, /*dgrad=*/0, stats_sum, stats_sq, ws, ws_bytes, c.st, o);
 }
 
 // dw (+ db) of that convolution: the same prologue on the x operand of the weight-gradient kernels
@@ -701,20 +787,18 @@ int mi355seg_conv3d_wgrad_pro_ax_f32(const float* dy, int lddy, const float* x, 
                                      float* dw, float* db, int N, int D, int H, int W, int Cin, int Cout,
                                      int k, int stride, int pad, int accumulate, const float* dy_amax, const float* x_amax,
                                      void* ws, size_t ws_bytes, void* stream) {
-    ConvGeom g{N, D, H, W, Cin, Cout, k, stride, pad, 0, 0, 0};
-    int rc = check_geom(&g, "conv3d_wgrad_pro");
+    ConvCall c;
+    int rc = conv_call(&c, "conv3d_wgrad_pro", x, ldx, dw, dy, lddy, N, D, H, W, Cin, Cout, k, stride, pad, ws, ws_bytes, stream);
     if (rc) return rc;
-    SEG_CHECK_ARG(dy && x && dw && pro_al && pro_be && x_amax && lddy >= Cout && ldx >= Cin, "conv3d_wgrad_pro: null pointer or pitch < channels");
-    SEG_CHECK_ARG(mi355seg_conv3d_pro_supported_f32(N, D, H, W, Cin, Cout, k, stride, pad, pro_act) && wgrad_lowp_supported(MATH_X3, N, D, H, W, Cin, Cout, k, stride, pad, ldx, lddy) &&
-                  ((uintptr_t)x % 16) == 0 && ((uintptr_t)dy % 16) == 0,
+    SEG_CHECK_ARG(pro_al && pro_be && x_amax, "conv3d_wgrad_pro: null pointer or pitch < channels");
+    SEG_CHECK_ARG(mi355seg_conv3d_pro_supported_f32(N, D, H, W, Cin, Cout, k, stride, pad, pro_act) && choose(WGRAD_F32, conv_key(c, accumulate)) == F_LOWP,
                   "conv3d_wgrad_pro: no prologue form for this layer under the selected conv math (ask mi355seg_conv3d_pro_supported_f32)");
-    hipStream_t st = (hipStream_t)stream;
     if (db) {
-        rc = channel_sums(dy, lddy, (long long)N * g.Do * g.Ho * g.Wo, Cout, nullptr, nullptr, db, accumulate, ws, ws_bytes, st);
+        rc = channel_sums(dy, lddy, c.vout(), Cout, nullptr, nullptr, db, accumulate, ws, ws_bytes, c.st);
         if (rc) return rc;
     }
     ConvPro pro{pro_al, pro_be, pro_act, pro_slope};
-    return conv_wgrad_lowp(MATH_X3, dy, lddy, x, ldx, dw, N, D, H, W, Cin, Cout, k, stride, accumulate, ws, ws_bytes, st, x_amax, dy_amax, &pro);
+    return conv_wgrad_lowp(MATH_X3, dy, lddy, x, ldx, dw, N, D, H, W, Cin, Cout, k, stride, accumulate, ws, ws_bytes, c.st, x_amax, dy_amax, &pro);
 }
 
 // The 1-channel stem behind a BatchNorm + activation (unet3d.py:80-89) when the stem's input needs no gradient: dw (+ db) of the stem
@@ -741,46 +825,9 @@ int mi355seg_conv3d_dgrad_f32(const float* dy, int lddy, const float* w, float* 
 int mi355seg_conv3d_dgrad_ax_f32(const float* dy, int lddy, const float* w, float* dx, int lddx,
                               int N, int D, int H, int W, int Cin, int Cout,
                               int k, int stride, int pad, const float* dy_amax, const float* w_amax, void* ws, size_t ws_bytes, void* stream) {
-    ConvGeom g{N, D, H, W, Cin, Cout, k, stride, pad, 0, 0, 0};
-    int rc = check_geom(&g, "conv3d_dgrad");
-    if (rc) return rc;
-    SEG_CHECK_ARG(dy && w && dx && lddy >= Cout && lddx >= Cin, "conv3d_dgrad: null pointer or pitch < channels");
-    hipStream_t st = (hipStream_t)stream;
-    // k3 s1 p1: dgrad is the same convolution with flipped taps and Cin<->Cout swapped
-    const int pol = f32_conv_policy();
-    if (pol != MATH_F32 && conv_mfma_supported(pol, N, D, H, W, Cout, Cin, k, stride, pad, lddy, lddx)) {
-        return conv_fwd_mfma(pol, dy, lddy, w, nullptr, dx, lddx, N, D, H, W, Cout, Cin, k, /*dgrad=*/1, nullptr, nullptr, ws, ws_bytes, st,
-                             nullptr, 0, 0.f, nullptr, dy_amax, w_amax);
-    }
-    if (conv_mfma_supported(MATH_F32, N, D, H, W, Cout, Cin, k, stride, pad, lddy, lddx)) {
-        return conv_fwd_mfma(MATH_F32, dy, lddy, w, nullptr, dx, lddx, N, D, H, W, Cout, Cin, k, /*dgrad=*/1, nullptr, nullptr, ws, ws_bytes, st);
-    }
-    if (conv_gather_dgrad_supported(MATH_F32, N, D, H, W, Cin, Cout, k, stride, pad, lddy, lddx) && ((uintptr_t)dy % 16) == 0) {
-        note_conv_path(MI355SEG_PATH_DGRAD_GATHER);
-        return conv_gather_dgrad_mfma(MATH_F32, dy, lddy, w, dx, lddx, N, D, H, W, Cin, Cout, k, stride, pad, ws, ws_bytes, st);
-    }
-    if (headk_supported(Cin, Cout, k, stride, pad, lddy, lddx, true) && ((uintptr_t)dy % 8) == 0 && ((uintptr_t)dx % 16) == 0) {
-        note_conv_path(MI355SEG_PATH_DGRAD_HEADK);
-        return headk_conv(true, dy, lddy, w, nullptr, dx, lddx, N, D, H, W, Cin, k, ws, ws_bytes, st);
-    }
-    if (head_supported(Cin, Cout, k, stride, pad, lddx)) {
-        note_conv_path(MI355SEG_PATH_DGRAD_HEAD);
-        return head_dgrad(dy, lddy, w, dx, lddx, N, D, H, W, Cin, Cout, st);
-    }
-    if (tinypw_supported(Cin, Cout, k, stride, pad)) {
-        note_conv_path(MI355SEG_PATH_DGRAD_TINYPW);
-        return tinypw_dgrad(dy, lddy, w, dx, lddx, (long long)N * D * H * W, Cin, Cout, st);
-    }
-    // k2 s2 p0 (V-Net's down-convolutions, vnet3d.py:66): the windows do not overlap, so the input gradient IS the forward of
-    // ConvTranspose3d k2 s2 with the same weight tensor read as (Cin_T = Cout, Cout_T = Cin, 2, 2, 2) -- also for Cin = 16,
-    // which the 32-column tiles of the gather dgrad cannot cut (the transposed conv tiles the flat (child, channel) axis)
-    if (k == 2 && stride == 2 && pad == 0 && D % 2 == 0 && H % 2 == 0 && W % 2 == 0 && ((uintptr_t)dy % 16) == 0 &&
-        convt_mfma_supported(MATH_F32, N, D / 2, H / 2, W / 2, Cout, Cin, lddy, lddx)) {
-        note_conv_path(MI355SEG_PATH_DGRAD_K2S2_CONVT);
-        return convt_fwd_mfma(MATH_F32, dy, lddy, w, nullptr, dx, lddx, N, D / 2, H / 2, W / 2, Cout, Cin, ws, ws_bytes, st);
-    }
-    note_conv_path(MI355SEG_PATH_DGRAD_GENERIC);
-    return conv_dgrad_generic(dy, lddy, w, dx, lddx, g, ws, ws_bytes, st);
+    ConvCall c;
+    int rc = conv_call(&c, "conv3d_dgrad", dx, lddx, w, dy, lddy, N, D, H, W, Cin, Cout, k, stride, pad, ws, ws_bytes, stream);
+    return rc ? rc : conv3d_dgrad_impl(c, dy_amax, w_amax, nullptr);
 }
 
 // Input gradient of a convolution whose INPUT was act(norm(bn_x)) of the layer in front, together with the two column sums that
@@ -801,25 +848,16 @@ int mi355seg_conv3d_dgrad_bnsums_ax_f32(const float* dy, int lddy, const float* 
                                      const float* bn_x, int ld_bnx, const float* mean, const float* rstd, const float* gamma, const float* beta,
                                      int act, float slope, float* s1, float* s2, float* dgamma, float* dbeta, const float* dy_amax, const float* w_amax,
                                      void* ws, size_t ws_bytes, void* stream) {
-    ConvGeom g{N, D, H, W, Cin, Cout, k, stride, pad, 0, 0, 0};
-    int rc = check_geom(&g, "conv3d_dgrad_bnsums");
+    ConvCall c;
+    int rc = conv_call(&c, "conv3d_dgrad_bnsums", dx, lddx, w, dy, lddy, N, D, H, W, Cin, Cout, k, stride, pad, ws, ws_bytes, stream);
     if (rc) return rc;
-    SEG_CHECK_ARG(dy && w && dx && lddy >= Cout && lddx >= Cin, "conv3d_dgrad_bnsums: null pointer or pitch < channels");
     SEG_CHECK_ARG(bn_x && mean && rstd && gamma && beta && s1 && s2 && ld_bnx >= Cin, "conv3d_dgrad_bnsums: the norm in front needs x, mean, rstd, gamma, beta");
     SEG_CHECK_ARG((dgamma == nullptr) == (dbeta == nullptr), "conv3d_dgrad_bnsums: dgamma/dbeta must come together");
-    hipStream_t st = (hipStream_t)stream;
-    const int pol = f32_conv_policy();
-    if (pol == MATH_X3 && conv_mfma_supported(pol, N, D, H, W, Cout, Cin, k, stride, pad, lddy, lddx)) {
-        BnBwdEpi e{bn_x, ld_bnx, mean, rstd, gamma, beta, act, slope, s1, s2, dgamma, dbeta, 0};
-        rc = conv_fwd_mfma(pol, dy, lddy, w, nullptr, dx, lddx, N, D, H, W, Cout, Cin, k, /*dgrad=*/1, nullptr, nullptr, ws, ws_bytes, st, nullptr, 0, 0.f, &e,
-                           dy_amax, w_amax);
-        if (rc || e.done) return rc;
-    } else {                 // (the plain dispatcher: it records its own branch)
-        rc = mi355seg_conv3d_dgrad_ax_f32(dy, lddy, w, dx, lddx, N, D, H, W, Cin, Cout, k, stride, pad, dy_amax, w_amax, ws, ws_bytes, stream);
-        if (rc) return rc;
-    }
+    BnBwdEpi e{bn_x, ld_bnx, mean, rstd, gamma, beta, act, slope, s1, s2, dgamma, dbeta, 0};
+    rc = conv3d_dgrad_impl(c, dy_amax, w_amax, &e);
+    if (rc || e.done) return rc;
     return mi355seg_norm_act_bwd_sums_f32(dx, lddx, bn_x, ld_bnx, mean, rstd, gamma, beta, nullptr, 0, s1, s2, dgamma, dbeta,
-                                          (long long)N * D * H * W, 1, Cin, act, slope, ws, ws_bytes, stream);
+                                          c.vin(), 1, Cin, act, slope, ws, ws_bytes, stream);
 }
 
 int mi355seg_conv3d_wgrad_f32(const float* dy, int lddy, const float* x, int ldx,
@@ -832,75 +870,59 @@ int mi355seg_conv3d_wgrad_ax_f32(const float* dy, int lddy, const float* x, int 
                               float* dw, float* db, int N, int D, int H, int W, int Cin, int Cout,
                               int k, int stride, int pad, int accumulate, const float* dy_amax, const float* x_amax,
                               void* ws, size_t ws_bytes, void* stream) {
-    ConvGeom g{N, D, H, W, Cin, Cout, k, stride, pad, 0, 0, 0};
-    int rc = check_geom(&g, "conv3d_wgrad");
+    ConvCall c;
+    int rc = conv_call(&c, "conv3d_wgrad", x, ldx, dw, dy, lddy, N, D, H, W, Cin, Cout, k, stride, pad, ws, ws_bytes, stream);
     if (rc) return rc;
-    SEG_CHECK_ARG(dy && x && dw && lddy >= Cout && ldx >= Cin, "conv3d_wgrad: null pointer or pitch < channels");
-    hipStream_t st = (hipStream_t)stream;
+    const ConvGeom& g = c.g;
+    hipStream_t st = c.st;
     if (db) {
-        rc = channel_sums(dy, lddy, (long long)N * g.Do * g.Ho * g.Wo, Cout, nullptr, nullptr, db, accumulate, ws, ws_bytes, st);
+        rc = channel_sums(dy, lddy, c.vout(), Cout, nullptr, nullptr, db, accumulate, ws, ws_bytes, st);
         if (rc) return rc;
     }
-    if (patch_embed_supported(D, H, W, Cin, k, stride, pad)) {          // dW[co][(ci, tap)] = sum_tokens dy[token][co] * patch[token][(ci, tap)]
+    float* part; int nstrips;
+    switch (choose(WGRAD_F32, conv_key(c, accumulate))) {
+    case F_PATCH: {               // dW[co][(ci, tap)] = sum_tokens dy[token][co] * patch[token][(ci, tap)]
         float* A; void* rest; size_t rest_bytes;
         note_conv_path(MI355SEG_PATH_WGRAD_PATCH_EMBED);
         rc = patch_embed_matrix(x, ldx, N, D, H, W, Cin, k, ws, ws_bytes, &A, &rest, &rest_bytes, st);
         if (rc) return rc;
-        const int M = N * (D / k) * (H / k) * (W / k), K = Cin * k * k * k;
+        const int M = (int)c.vout(), K = Cin * k * k * k;
         return mi355seg_gemm_f32(dy, 1, lddy, 0, 0, A, K, 1, 0, 0, dw, K, 0, 0, nullptr, Cout, K, M, 1, 1, 1.f, 0, accumulate, rest, rest_bytes, stream);
     }
-    if (f32_conv_policy() == MATH_X3 && wgrad_lowp_supported(MATH_X3, N, D, H, W, Cin, Cout, k, stride, pad, ldx, lddy) &&
-        ((uintptr_t)x % 16) == 0 && ((uintptr_t)dy % 16) == 0)
+    case F_LOWP:                  // (conv_wgrad_lowp records which of its forms: MI355SEG_PATH_WGRAD_LOWP_*)
         return conv_wgrad_lowp(MATH_X3, dy, lddy, x, ldx, dw, N, D, H, W, Cin, Cout, k, stride, accumulate, ws, ws_bytes, st, x_amax, dy_amax);
-    if (wgrad_mfma_supported(N, D, H, W, Cin, Cout, k, stride, pad, ldx, lddy) && ((uintptr_t)x % 16) == 0 && ((uintptr_t)dy % 16) == 0) {
+    case F_WGRAD_MFMA:
         note_conv_path(MI355SEG_PATH_WGRAD_MFMA);
         return conv_wgrad_mfma(dy, lddy, x, ldx, dw, N, D, H, W, Cin, Cout, k, accumulate, ws, ws_bytes, st);
-    }
-    if (k == 1 && stride == 1 && pad == 0 && f32_conv_policy() == MATH_X3 && pw_wgrad_lowp_supported((long long)N * D * H * W, Cin, Cout, ldx, lddy, 4) &&
-        ((uintptr_t)x % 16) == 0 && ((uintptr_t)dy % 16) == 0) {
-        float* part; int nstrips;
+    case F_PW_LOWP:
         note_conv_path(MI355SEG_PATH_WGRAD_PW_LOWP);
-        rc = pw_wgrad_lowp(dy, lddy, x, ldx, N, D, H, W, Cin, Cout, &part, &nstrips, ws, ws_bytes, st);
-        if (rc) return rc;
-        wgrad_reduce(part, dw, nstrips, 1, Cin, Cout, accumulate, st);
-        SEG_CHECK_LAUNCH();
-        return MI355SEG_OK;
-    }
-    if (k == 1 && stride == 1 && pad == 0 && pw_wgrad_supported((long long)N * D * H * W, Cin, Cout, 1, ldx, lddy)) {
-        float* part; int nstrips;
+        return wgrad_strips_tail(pw_wgrad_lowp(dy, lddy, x, ldx, N, D, H, W, Cin, Cout, &part, &nstrips, ws, ws_bytes, st), part, nstrips, c, accumulate);
+    case F_PW_MFMA:
         note_conv_path(MI355SEG_PATH_WGRAD_PW_MFMA);
-        rc = pw_wgrad_mfma(dy, lddy, x, ldx, N, D, H, W, Cin, Cout, 1, &part, &nstrips, ws, ws_bytes, st);
-        if (rc) return rc;
-        wgrad_reduce(part, dw, nstrips, 1, Cin, Cout, accumulate, st);
-        SEG_CHECK_LAUNCH();
-        return MI355SEG_OK;
-    }
-    if (tinypw_supported(Cin, Cout, k, stride, pad)) {
+        return wgrad_strips_tail(pw_wgrad_mfma(dy, lddy, x, ldx, N, D, H, W, Cin, Cout, 1, &part, &nstrips, ws, ws_bytes, st), part, nstrips, c, accumulate);
+    case F_TINYPW:
         note_conv_path(MI355SEG_PATH_WGRAD_TINYPW);
-        return tinypw_wgrad(dy, lddy, x, ldx, dw, (long long)N * D * H * W, Cin, Cout, accumulate, ws, ws_bytes, st);
-    }
-    if (stem_supported(Cin, Cout, k, stride, pad, lddy))         // (stem_wgrad records which of its kernels: MI355SEG_PATH_WGRAD_STEM*)
+        return tinypw_wgrad(dy, lddy, x, ldx, dw, c.vin(), Cin, Cout, accumulate, ws, ws_bytes, st);
+    case F_STEM:                  // (stem_wgrad records which of its kernels: MI355SEG_PATH_WGRAD_STEM*)
         return stem_wgrad(dy, lddy, x, ldx, dw, N, D, H, W, Cin, Cout, accumulate, ws, ws_bytes, st);
-    if (head_supported(Cin, Cout, k, stride, pad, ldx)) {
+    case F_HEAD:
         note_conv_path(MI355SEG_PATH_WGRAD_HEAD);
         return head_wgrad(dy, lddy, x, ldx, dw, N, D, H, W, Cin, Cout, accumulate, ws, ws_bytes, st);
-    }
-    if (headk_wgrad_supported(Cin, Cout, k, stride, pad, ldx, lddy) && ((uintptr_t)x % 16) == 0 && ((uintptr_t)dy % 8) == 0) {
+    case F_HEADK:
         note_conv_path(MI355SEG_PATH_WGRAD_HEADK);
         return headk_wgrad(dy, lddy, x, ldx, dw, N, D, H, W, Cin, k, accumulate, ws, ws_bytes, st);
-    }
-    if (smallcin_wgrad_supported(Cin, Cout, k))                  // (smallcin_wgrad records MI355SEG_PATH_WGRAD_SMALLCIN[_K5_TILED])
+    case F_SMALLCIN:              // (smallcin_wgrad records MI355SEG_PATH_WGRAD_SMALLCIN[_K5_TILED])
         return smallcin_wgrad(dy, lddy, x, ldx, dw, N, D, H, W, Cin, Cout, k, stride, pad, accumulate, ws, ws_bytes, st);
-    if (smallcout_wgrad_supported(Cin, Cout, k, ldx) && ((uintptr_t)x % 16) == 0) {
+    case F_SMALLCOUT:
         note_conv_path(MI355SEG_PATH_WGRAD_SMALLCOUT);
         return smallcout_wgrad(dy, lddy, x, ldx, dw, N, D, H, W, Cin, Cout, k, stride, pad, accumulate, ws, ws_bytes, st);
-    }
-    if (gwgrad_supported(N, D, H, W, Cin, Cout, k, stride, pad, ldx, lddy) && ((uintptr_t)x % 16) == 0 && ((uintptr_t)dy % 16) == 0) {
+    case F_GWGRAD:
         note_conv_path(MI355SEG_PATH_WGRAD_GWGRAD);
         return conv_gwgrad(dy, lddy, x, ldx, dw, N, D, H, W, Cin, Cout, k, stride, pad, accumulate, ws, ws_bytes, st);
+    default:
+        note_conv_path(MI355SEG_PATH_WGRAD_GENERIC);
+        return conv_wgrad_generic(dy, lddy, x, ldx, dw, g, accumulate, ws, ws_bytes, st);
     }
-    note_conv_path(MI355SEG_PATH_WGRAD_GENERIC);
-    return conv_wgrad_generic(dy, lddy, x, ldx, dw, g, accumulate, ws, ws_bytes, st);
 }
 
 }  // extern "C"

@@ -441,9 +441,10 @@ static double matrix_bytes(int math, double act_elems, double w_elems) { return 
 // oscale / act / slope (inference): y = act(conv(x, w * oscale[co]) + bias[co]) -- eval-mode BatchNorm folded into the packed weights
 // and the bias vector, the activation applied in the epilogue (or in the split-K reduce), no normalise pass
 int conv_fwd_mfma(int math, const void* x, int ldx, const float* w, const float* bias, void* y, int ldy, int N, int D, int H, int W,
-                  int Cin, int Cout, int k, int dgrad, double* ssum, double* ssq, void* ws, size_t ws_bytes, hipStream_t st,
-                  const float* oscale, int act, float slope, BnBwdEpi* bne, const float* x_amax, const float* w_amax, const void* res, int ldres,
-                  int* res_fused, const ConvPro* pro, float* y_amax) {
+                  int Cin, int Cout, int k, int dgrad, double* ssum, double* ssq, void* ws, size_t ws_bytes, hipStream_t st, const MfmaOpts& o) {
+    const float* oscale = o.oscale; const int act = o.act; const float slope = o.slope; BnBwdEpi* bne = o.bne;
+    const float* x_amax = o.x_amax; const float* w_amax = o.w_amax; const void* res = o.res; const int ldres = o.ldres; int* res_fused = o.res_fused;
+    const ConvPro* pro = o.pro; float* y_amax = o.y_amax;
     IgemmPlan p;
     if (res_fused) *res_fused = 0;
     SEG_CHECK_ARG(igemm_plan(math, k, N, D, H, W, Cin, Cout, 1, &p), "conv_fwd_mfma: unsupported shape");

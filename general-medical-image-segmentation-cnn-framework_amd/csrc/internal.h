@@ -86,7 +86,51 @@ int headk_wgrad(const float* dy, int lddy, const float* x, int ldx, float* dw, i
 template <typename T> int head_wgrad(const T* dy, int lddy, const T* x, int ldx, float* dw, int N, int D, int H, int W, int Cin, int Cout,
                int accumulate, void* ws, size_t ws_bytes, hipStream_t st);
 
-// conv_generic.hip
+// conv_generic.hip -- one Conv3d call as every entry point of conv_generic.hip / conv_bf16_api.hip sees it
+struct ConvGeom {
+    int N, D, H, W, Cin, Cout, k, stride, pad, Do, Ho, Wo;
+};
+#define GEOM9(g) (g).N, (g).D, (g).H, (g).W, (g).Cin, (g).Cout, (g).k, (g).stride, (g).pad      // as the predicates and size queries take it
+#define GEOM9_T(g) (g).N, (g).D, (g).H, (g).W, (g).Cout, (g).Cin, (g).k, (g).stride, (g).pad    // the input gradient as a convolution Cout -> Cin
+#define SHAPE5(g) (g).Cin, (g).Cout, (g).k, (g).stride, (g).pad
+inline long long conv_vin(const ConvGeom& g) { return (long long)g.N * g.D * g.H * g.W; }
+inline bool pointwise(const ConvGeom& g) { return g.k == 1 && g.stride == 1 && g.pad == 0; }
+// the checked call: geometry with its output extents, the operands by their role in the FORWARD pass (x: the input-side tensor, x or dx;
+// y: the output-side one, y or dy; w: w or dw) with the two pitches, workspace and stream
+struct ConvCall {
+    ConvGeom g; int ldx, ldy; const void* x; const void* y; const void* w; void* ws; size_t ws_bytes; hipStream_t st;
+    long long vin() const { return conv_vin(g); }
+    long long vout() const { return (long long)g.N * g.Do * g.Ho * g.Wo; }
+    float* dw() const { return (float*)w; }      // (weight gradient: the one operand of the three that is written)
+};
+// fills *c; extents, k / stride / pad, null operands and pitches below the channel count are refused under the entry point's name `who`
+int conv_call(ConvCall* c, const char* who, const void* x, int ldx, const void* w, const void* y, int ldy, int N, int D, int H, int W,
+              int Cin, int Cout, int k, int stride, int pad, void* ws, size_t ws_bytes, void* stream);
+// all a chooser sees of a call: geometry, pitches, the operand addresses modulo 16, accumulate (weight gradient); the conv-math policy
+// is the library's setting.  dense_key: contiguous tensors at aligned addresses, accumulate = 0 -- what the workspace queries probe with
+struct ConvKey { ConvGeom g; int ldx, ldy; unsigned ax, ay; int accumulate; };
+inline ConvKey conv_key(const ConvCall& c, int accumulate = 0) { return {c.g, c.ldx, c.ldy, (unsigned)((uintptr_t)c.x % 16), (unsigned)((uintptr_t)c.y % 16), accumulate}; }
+inline ConvKey dense_key(const ConvGeom& g) { return {g, g.Cin, g.Cout, 0, 0, 0}; }
+// One rung of a chooser's ladder.  THE RULE: `fits` (and `aligned`) is the precondition of the launcher the family's switch case calls,
+// nothing weaker; `ws` is what that launcher carves from the workspace, and the size queries are the maximum of `ws` over the rungs a
+// geometry can reach: fits / aligned of dense_key(g), or `reach` where the query has always counted the term more widely than that.
+struct Rung {
+    int family;
+    bool (*fits)(const ConvKey&);
+    size_t (*ws)(const ConvGeom&);              // null: nothing beyond what the always-reached generic rung takes
+    bool (*reach)(const ConvGeom&);
+    bool (*aligned)(const ConvKey&);            // bf16 ladders (conv_bf16_api.hip): see choose_b16
+    int demote;
+};
+#define RUNG(...) [](const ConvKey& k) -> bool { const ConvGeom& g = k.g; return __VA_ARGS__; }        // a test over the key k and its geometry g
+#define WS(...) [](const ConvGeom& g) -> size_t { return __VA_ARGS__; }
+size_t ladder_ws_bytes(const Rung* ladder, const ConvGeom& g);      // (a ladder ends at the rung without a `fits`, which takes every call)
+// the tails the launchers share: batch statistics of y by channel_sums where asked for, the strips of a weight gradient summed into dw
+template <typename T> inline int conv_stats_tail(int rc, const ConvCall& c, double* stats_sum, double* stats_sq) {
+    if (rc || !stats_sum) return rc;
+    return channel_sums((const T*)c.y, c.ldy, c.vout(), c.g.Cout, stats_sum, stats_sq, nullptr, 0, c.ws, c.ws_bytes, c.st);
+}
+int wgrad_strips_tail(int rc, const float* part, int nstrips, const ConvCall& c, int accumulate);      // (k1 slabs: [strip][Cin][Cout])
 int f32_conv_policy();     // MATH_X3 when the bf16x6 conv math is selected, else MATH_F32
 int x3_shape();            // 16 | 32: MFMA shape of the bf16x6 forward / dgrad kernels (mi355seg_set_x3_shape)
 void note_conv_path(int code);      // MI355SEG_PATH_*: the branch an fp32 convolution dispatcher took (mi355seg_last_conv_path)
@@ -125,11 +169,17 @@ bool tile_stats_finalize2(const float* spart, int nM, int C, double* sum, double
 // over -- the folded BatchNorm of the layer in front (al = rstd gamma, be = beta - mean al) -- formed while the tiles are staged
 struct ConvPro { const float* al; const float* be; int act; float slope; };
 bool conv_pro_act_ok(int act);
+// what a conv_fwd_mfma call adds to the plain convolution; every field defaults to "absent" and a caller names the ones it sets
+struct MfmaOpts {
+    const float* oscale = nullptr; int act = 0; float slope = 0.f;      // inference: y = act(conv(x, w * oscale[co]) + bias[co])
+    BnBwdEpi* bne = nullptr;                                            // input gradient: the norm backward's column sums from the epilogue
+    const float* x_amax = nullptr; const float* w_amax = nullptr;       // f16x3: operand maxima the caller already holds
+    const void* res = nullptr; int ldres = 0; int* res_fused = nullptr;
+    const ConvPro* pro = nullptr;
+    float* y_amax = nullptr;
+};
 int conv_fwd_mfma(int math, const void* x, int ldx, const float* w, const float* bias, void* y, int ldy, int N, int D, int H, int W,
-                  int Cin, int Cout, int k, int dgrad, double* ssum, double* ssq, void* ws, size_t ws_bytes, hipStream_t st,
-                  const float* oscale = nullptr, int act = 0, float slope = 0.f, BnBwdEpi* bne = nullptr,
-                  const float* x_amax = nullptr, const float* w_amax = nullptr, const void* res = nullptr, int ldres = 0, int* res_fused = nullptr,
-                  const ConvPro* pro = nullptr, float* y_amax = nullptr);
+                  int Cin, int Cout, int k, int dgrad, double* ssum, double* ssq, void* ws, size_t ws_bytes, hipStream_t st, const MfmaOpts& o = {});
 // (pro: fp32 tensors under f16x3 on the conv_x3s kernels only -- ask conv_fwd_takes_amax; x_amax must then bound the prologue's OUTPUT.
 //  y_amax: max |y| max-combined into this zeroed device scalar: from the kernel's epilogue on whole-K conv_x3s launches, by a pass over y otherwise)
 // (res: a tensor of y's geometry to add to the result; *res_fused = 1 when the launch took it into its epilogue -- bf16 16x16x32 tiles,

@@ -455,6 +455,48 @@ def test_conv_transpose3d_k2s2_branch_against_fp64_in_every_math(seg, case):
     G.spread("dw", errs["dw"], pw_)
 
 
+SLICE_CASE = ((1, 5, 7, 9, 32, 32, 3, 1, 1), 4, 4)        # the igemm case of CONV_CASES, its operand read at channel offset 1 of the pitch-36 rows
+
+
+@gpu
+@pytest.mark.parametrize("which, want", [("fwd", "FWD_GENERIC"), ("dgrad", "DGRAD_GENERIC")])
+def test_conv3d_misaligned_channel_slice_falls_through(seg, which, want):
+    """An fp32 channel slice that starts at channel 1: x (forward) / dy (input gradient) sits 4 bytes off a 16-byte boundary at a pitch
+    that is a multiple of 4.  The igemm rungs ask for the 16-byte alignment their launcher demands, so the call goes down the ladder --
+    gather, headk, stems and heads do not fit a 32 -> 32 k3 layer -- to the generic kernel instead of being refused, in every math, within
+    bound (a), inside its rows x channels and inside the queried workspace."""
+    geom, ex, ey = SLICE_CASE
+    N, D, H, W, Cin, Cout, k, s, p = geom
+    L = seg.lib()
+    ref = conv_reference(geom, ex, ey)
+    G = Grader(ref, f"slice-{which}-" + case_id(SLICE_CASE))
+    ldx, ldy = ref.ldx, ref.ldy
+    rows_in, rows_out = N * D * H * W, ref.y.numel() // Cout
+    src, C, ld = (ref.x, Cin, ldx) if which == "fwd" else (ref.g, Cout, ldy)
+    buf = torch.full((src.numel() // ld + 1, ld), SENTINEL, device="cuda")
+    buf[:-1, 1:1 + C] = src.reshape(-1, ld)[:, :C].cuda()
+    ptr = buf.data_ptr() + 4
+    assert ptr % 16 == 4 and ld % 4 == 0
+    w, b = ref.w.cuda(), ref.b.cuda()
+    ws = Workspace(L.query("mi355seg_conv3d_ws_bytes", *geom))
+    try:
+        for key in MATHS:
+            seg.set_conv_math(key[0])
+            seg.set_x3_shape(key[1])
+            if which == "fwd":
+                out = Rows(rows_out, ldy, Cout)
+                L.call("mi355seg_conv3d_fwd_ax_f32", ptr, ldx, w.data_ptr(), b.data_ptr(), out.ptr, ldy, *geom, None, None, None, None, ws.ptr, ws.n, stream())
+            else:
+                out = Rows(rows_in, ldx, Cin)
+                L.call("mi355seg_conv3d_dgrad_ax_f32", ptr, ldy, w.data_ptr(), out.ptr, ldx, *geom, None, None, ws.ptr, ws.n, stream())
+            expect_path(L, want, which, key)
+            ws.check(which)
+            G.grade("y" if which == "fwd" else "dx", out.check(which), key)
+    finally:
+        seg.set_conv_math(DEFAULT_MATH)
+        seg.set_x3_shape(16)
+
+
 def _amax_rules(run, what):
     """(c): ``run(slot)`` writes y and max-combines max |y| into the device scalar; returns y.  The scalar equals max |y| of the tensor
     the call wrote bit for bit; a larger value already in the slot stays, a smaller one is raised."""
