@@ -78,7 +78,7 @@ def train_step(model, optimizer, x, gt, criterion=None, sync_metric=True, grad_h
             with F.autocast(dtype or F.compute_dtype()), F.counters_batched(bns):
                 if getattr(model, "takes_frequency_bands", False):      # the IS network, train.py:198-201: second output discarded
                     from .models.three_d.IS import frequency_bands
-                    low_x, high_x = frequency_bands(x)
+                    low_x, high_x = frequency_bands(x, impl=getattr(model, "band_split", "fft"))
                     pred, _ = _forward(model, _leaves, x, low_x, high_x)
                 else:
                     pred = _forward(model, _leaves, x)

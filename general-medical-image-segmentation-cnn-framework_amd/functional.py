@@ -1824,6 +1824,76 @@ def augment_sample(patches, patch_size):
     return xb, yb
 
 
+_BAND_BASIS = {}                # (n, limit, device) -> (float32 [q, n] on the device, r, q)
+
+
+def band_basis(n, limit=0.04):
+    """Orthonormal real Fourier basis of the modes of a length-``n`` axis that the IS band split (train.py:76-88) does not let into
+    its high band: ``(E float64 [q, n], r)``; the first ``r`` rows span the low band (``|f| < limit``), all ``q`` rows the modes that
+    are not ``> limit``.  Membership is the reference's own comparison -- ``torch.fft.fftfreq(n).abs()`` against ``limit`` in
+    float32 on the CPU -- so a mode exactly at the limit (n = 25, 50, 100 at 0.04) sits in neither band.  Per kept mode k:
+    ``1/sqrt(n)`` for k = 0, ``(-1)^j/sqrt(n)`` for 2k = n, else the pair ``sqrt(2/n) cos(2 pi k j / n)``, ``sqrt(2/n) sin(...)``."""
+    n = int(n)
+    f = torch.fft.fftfreq(n).abs()
+    below, above = (f < limit).tolist(), (f > limit).tolist()
+
+    def rows(k):
+        if k == 0:
+            return [np.full(n, 1.0 / np.sqrt(n))]
+        if 2 * k == n:
+            return [np.where(np.arange(n) % 2 == 0, 1.0, -1.0) / np.sqrt(n)]
+        w = 2.0 * np.pi * ((k * np.arange(n)) % n) / n
+        return [np.sqrt(2.0 / n) * np.cos(w), np.sqrt(2.0 / n) * np.sin(w)]
+
+    low, edge = [], []
+    for k in range(n // 2 + 1):
+        if below[k]:
+            low += rows(k)
+        elif not above[k]:
+            edge += rows(k)
+    basis = np.stack(low + edge) if low or edge else np.zeros((0, n))
+    return basis, len(low)
+
+
+def _band_basis_device(n, limit, device):
+    key = (int(n), float(limit), device)
+    hit = _BAND_BASIS.get(key)
+    if hit is None:
+        basis, r = band_basis(n, limit)
+        hit = (torch.from_numpy(np.ascontiguousarray(basis, dtype=np.float32)).to(device), r, basis.shape[0])
+        _BAND_BASIS[key] = hit
+    return hit
+
+
+def frequency_bands(x, limit=0.04):
+    """The IS network's input split (train.py:76-88,198-201: low_pass_torch / high_pass_torch) of ``x`` [B,C,D,H,W] as ONE launch:
+    ``(low, high)`` with ``low = P_H X P_W`` and ``high = (I - E_H) X (I - E_W)`` per [H,W] slice (definitions in
+    include/mi355seg.h; ``high`` is not ``x - low``).  The per-axis bases come from ``band_basis`` and are uploaded once per
+    (n, limit, device): the first eager call warms that cache, after which a call copies nothing and may be captured.  B and C
+    may be 1 or 2 (for 2 the slices filter x0 + x1 and x0 - x1, the reference's all-axes forward transform)."""
+    if x.requires_grad:
+        raise NotImplementedError("frequency_bands: the bands are inputs of the network; no gradient flows through the split")
+    _require_cuda(x, "frequency_bands input")
+    if x.dim() != 5:
+        raise Mi355SegError(f"frequency_bands: expected [B,C,D,H,W], got {tuple(x.shape)}")
+    B, C, D, H, W = x.shape
+    L = lib()
+    if not (1 <= H <= 256 and 1 <= W <= 256 and D >= 1):
+        raise Mi355SegError(f"frequency_bands: unsupported shape {tuple(x.shape)}: the device split filters axes of 1 .. 256 elements")
+    if B not in (1, 2) or C not in (1, 2):
+        raise Mi355SegError(f"frequency_bands: unsupported shape {tuple(x.shape)}: B and C must be 1 or 2 -- the reference's forward "
+                            "transform also covers the batch and channel axes and is never inverted there (the upstream "
+                            "all-axes-transform quirk), which is defined for lengths 1 and 2 only")
+    (eh, rh, qh), (ew, rw, qw) = _band_basis_device(H, limit, x.device), _band_basis_device(W, limit, x.device)
+    if not L.query("mi355seg_band_split_supported", B, C, D, H, W, rh, qh, rw, qw):
+        raise Mi355SegError(f"frequency_bands: unsupported shape {tuple(x.shape)} at limit {limit}: an axis may keep at most 32 modes "
+                            f"(H keeps {qh}, W keeps {qw})")
+    x = x.contiguous()
+    low, high = torch.empty_like(x), torch.empty_like(x)
+    L.call("mi355seg_band_split_f32", _p(x), B, C, D, H, W, _p(eh), rh, qh, _p(ew), rw, qw, _p(low), _p(high), _stream())
+    return low, high
+
+
 def dice_sums(x, t, apply_sigmoid=False):
     """(sum a*b, sum a, sum b, sum a*a, sum b*b) as float64[5], a = sigmoid(x) if asked."""
     _require_cuda(x, "dice_sums input")

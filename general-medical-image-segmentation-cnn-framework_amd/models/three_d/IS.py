@@ -9,9 +9,11 @@ constructor, same state_dict keys, same call pattern (so the shared encoder's Ba
 three times per forward, as upstream), with every op a kernel of libmi355seg.so.
 
 ``frequency_bands`` is the caller-side split of train.py:76-88,198-201 (``low_pass_torch`` / ``high_pass_torch`` at
-limit 0.04): an FFT mask on the last two axes.  It is data preparation in front of the hot path and runs on rocFFT
-through ``torch.fft``; including the upstream quirk that the forward transform covers all five axes while the inverse
-covers only the last three (exact for batch = channel = 1).
+limit 0.04): an FFT mask on the last two axes, including the upstream quirk that the forward transform covers all five
+axes while the inverse covers only the last three (exact for batch = channel = 1).  ``impl="fft"`` (the default) runs it
+on rocFFT through ``torch.fft``; ``impl="device"`` is the same operation as one launch of the library
+(``functional.frequency_bands``, csrc/band.hip).  The model's ``band_split`` attribute (``config.band_split``) chooses
+for ``engine.train_step`` and ``predict.sliding_window_predict``.
 """
 import torch
 import torch.nn as nn
@@ -24,8 +26,25 @@ _SETS = ("", "_", "__")
 _LEVELS = (1, 2, 3, 4)
 
 
-def frequency_bands(x, limit=0.04):
+BAND_SPLITS = ("fft", "device")
+
+
+def set_band_split(model, config):
+    """``config.band_split`` (when the key is present) -> ``model.band_split`` of a network that takes frequency bands."""
+    value = config.get("band_split") if hasattr(config, "get") else getattr(config, "band_split", None)
+    if value is None or not getattr(model, "takes_frequency_bands", False):
+        return
+    if str(value) not in BAND_SPLITS:
+        raise ValueError(f"config.band_split must be one of {BAND_SPLITS}, got {value!r}")
+    model.band_split = str(value)
+
+
+def frequency_bands(x, limit=0.04, impl="fft"):
     """-> (low_x, high_x) as train.py:198-200 computes them for the IS network."""
+    if impl == "device":
+        return F.frequency_bands(x, limit)
+    if impl != "fft":
+        raise ValueError(f"frequency_bands: impl must be one of {BAND_SPLITS}, got {impl!r}")
     fx = torch.fft.rfftn(x)
     f_last = torch.fft.rfftfreq(x.shape[-1]).abs()
     f_prev = torch.fft.fftfreq(x.shape[-2]).abs()
@@ -57,6 +76,7 @@ class UNet3D(nn.Module):
         self.conv_ = Conv3d(in_channels=f, out_channels=out_channels, kernel_size=1)
 
     takes_frequency_bands = True                           # engine.train_step / predict feed (x, low_x, high_x)
+    band_split = "fft"                                     # which frequency_bands(impl=...) they feed it from (config.band_split)
 
     def _branch(self, volume, tag):
         """Shared encoder + bottleneck, then decoder set ``tag`` (IS.py:133-150 / 152-169 / 171-188)."""

@@ -24,6 +24,7 @@ from . import functional as F
 from .config import compose, parse_patch_size
 from .engine import mixed_precision_dtype
 from .registry import build_model
+from .models.three_d.IS import set_band_split
 from .utils.metric import metric_from_counts, metric_with_spacing
 
 
@@ -106,7 +107,7 @@ def sliding_window_predict(model, volume, patch_size, overlap=(4, 4, 36), batch_
         with F.autocast(dtype or F.compute_dtype()):
             if getattr(model, "takes_frequency_bands", False):           # predict.py:128-131 (IS: first output only)
                 from .models.three_d.IS import frequency_bands
-                logits, _ = model(x, *frequency_bands(x))
+                logits, _ = model(x, *frequency_bands(x, impl=getattr(model, "band_split", "fft")))
             else:
                 logits = model(x)
         labels = F.argmax_channels(logits)                               # predict.py:133,139
@@ -201,6 +202,7 @@ def main(argv=None, conf_dir=None):
     config = compose(conf_dir, argv, job_name="predict")
     parse_patch_size(config)
     model = build_model(config)
+    set_band_split(model, config)                        # config.band_split (IS only): fft | device
     return config, predict(config, model)
 
 

@@ -19,6 +19,7 @@ from .data import make_loader
 from .utils.metric import metric_from_counts
 from .engine import GraphedTrainStep, make_adam, mixed_precision_dtype, train_step, weights_init_normal
 from .registry import build_model
+from .models.three_d.IS import set_band_split
 
 
 class AverageMeter:
@@ -137,6 +138,7 @@ def main(argv=None, conf_dir=None):
             raise SystemExit(rc)
         return config, None
     model = build_model(config)                          # train.py:324-373
+    set_band_split(model, config)                        # config.band_split (IS only): fft | device
     model.apply(weights_init_normal(config.init_type))   # train.py:374
     logger = get_logger(config)
     logger.info("\nParameter Settings:\n" + "".join(f"{k}: {v}\n" for k, v in config.items()))

@@ -707,6 +707,26 @@ int mi355seg_augment_stats_f32(const float* x, int C, int D, int H, int W, const
 int mi355seg_augment_sample_f32(const int* table, int count, int C, int Cy, int pd, int ph, int pw, float* out_x, float* out_y,
                                 void* stream);
 
+/* ------------------------------------------------------------------ Frequency-band split of the IS network (train.py:76-88,198-201)
+ * low_pass_torch / high_pass_torch at `limit`: the reference masks the spectrum of x [B,C,D,H,W] on its last two axes with the outer
+ * product of (|fftfreq(H)| < limit, |rfftfreq(W)| < limit) for the low band and of the two `> limit` masks for the high band.  Per
+ * [H,W] slice X that is
+ *   low = P_H X P_W          high = (I - E_H) X (I - E_W)          (high is NOT x - low: the cross terms are dropped, as upstream)
+ * with P_n the orthogonal projector onto the real Fourier modes of length n with |f| < limit and E_n the one onto the modes that are
+ * not > limit (the low modes plus any mode exactly at the limit; membership is the reference's own float32 comparison, which the
+ * CALLER evaluates).  The caller passes orthonormal basis rows basis_h [qH,H] and basis_w [qW,W] whose first rH / rW rows span P:
+ * per kept mode k, 1/sqrt(n) for k = 0, (-1)^j/sqrt(n) for 2k = n, else the pair sqrt(2/n) cos(2 pi k j / n), sqrt(2/n) sin(2 pi k j / n).
+ * With U = X Ew^T, V = Eh X, A = Eh U:  low = Eh[:r]^T A[:r,:r] Ew[:r],  high = X - Eh^T V - U Ew + Eh^T A Ew.
+ * Upstream quirk, kept: the forward transform also covers the batch and channel axes and is never inverted there, so for B = 2
+ * (C = 2 likewise, independently) slice 0 filters x0 + x1 and slice 1 filters x0 - x1; longer axes are backend-defined upstream and
+ * refused here.  Supported: B, C in {1, 2}, D >= 1, 1 <= H, W <= 256, 0 <= r <= q <= min(n, 32).
+ * One launch, one workgroup per output slice, fixed-order fp32 sums and no atomics (bitwise reproducible); neither allocates nor
+ * synchronises.  mi355seg_band_split_supported: 0 for an unsupported shape, else the number of row chunks a slice is staged in
+ * (1: the slice stays in LDS between the two passes; more: the second pass re-reads it). */
+int mi355seg_band_split_supported(int B, int C, int D, int H, int W, int rH, int qH, int rW, int qW);
+int mi355seg_band_split_f32(const float* x, int B, int C, int D, int H, int W, const float* basis_h, int rH, int qH,
+                            const float* basis_w, int rW, int qW, float* low, float* high, void* stream);
+
 /* ------------------------------------------------------------------ Layout helpers */
 int mi355seg_ncdhw_to_ndhwc_f32(const float* src, float* dst, int lddst, long long N, int C, long long S, void* stream);
 int mi355seg_ndhwc_to_ncdhw_f32(const float* src, int ldsrc, float* dst, long long N, int C, long long S, void* stream);

@@ -25,12 +25,19 @@ from oracle.fill import fill_module_, make_input, make_labels  # noqa: E402
 BF16 = torch.bfloat16
 
 
+def _with(module, **attrs):
+    for k, v in attrs.items():
+        setattr(module, k, v)
+    return module
+
+
 def _model(name):
     from mi355seg.models.three_d import unet3d, vnet3d, residual_unet3d, csrnet, RE_net, ER_net, IS, unetr
     return {"unet": lambda: unet3d.UNet3D(1, 2, 16), "vnet": lambda: vnet3d.VNet(in_channels=1, classes=2),
             "resunet": lambda: residual_unet3d.UNet(4, 2, 16), "csrnet": lambda: csrnet.CSRNet(in_channels=1, out_channels=2, init_features=4),
             "renet": lambda: RE_net.RE_Net(), "ernet": lambda: ER_net.ER_Net(classes=2, channels=1),
             "isnet": lambda: IS.UNet3D(in_channels=1, out_channels=2, init_features=4),
+            "isnet_device_bands": lambda: _with(IS.UNet3D(in_channels=1, out_channels=2, init_features=4), band_split="device"),
             "unetr": lambda: unetr.UNETR(img_shape=(32, 32, 32), input_dim=1, output_dim=2, embed_dim=96, patch_size=16, num_heads=4, dropout=0.0),
             "torch_ops": lambda: unet3d.UNet3D(1, 2, 8)}[name]()
 
@@ -51,6 +58,7 @@ CONFIGS.update({
     "renet": ("renet", (1, 1, 32, 32, 32), None, None, "train"),
     "ernet": ("ernet", (1, 1, 32, 32, 32), None, None, "train"),
     "isnet": ("isnet", (1, 1, 32, 32, 32), None, None, "train"),
+    "isnet-bands-device": ("isnet_device_bands", (1, 1, 32, 32, 32), None, None, "train"),     # config.band_split=device (csrc/band.hip)
     "unetr": ("unetr", (2, 1, 32, 32, 32), None, None, "train"),
     "torch_ops": ("torch_ops", (2, 1, 32, 32, 32), None, None, "ops"),
 })
