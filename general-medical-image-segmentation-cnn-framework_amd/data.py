@@ -3,7 +3,9 @@
 of scope, so this module yields the same dict shape from (a) a device-resident synthetic generator or (b) a
 device-resident patch queue over a directory of ``.npy`` volumes (Queue / UniformSampler / ZNormalization semantics of
 dataloader.py:52-67,94).  With ``config.aug`` both apply the reference's training augmentation (dataloader.py:69-86) on the
-device: parameters drawn on the host per subject visit (``AugmentParams``), one resampling launch per batch."""
+device: parameters drawn on the host per subject visit (``AugmentParams``), one resampling launch per batch.  With
+``config.sampler=label`` the queue places its patches as tio.LabelSampler does (imported beside UniformSampler, dataloader.py:19):
+picks drawn on the host from per-class counts (``draw_label_picks``), resolved to origins by one select launch per visit."""
 import glob
 import os
 
@@ -11,11 +13,83 @@ import numpy as np
 import torch
 
 
-def _require_device(device, what):
+def _require_device(device, what, option="aug=True resamples with the HIP kernels of csrc/augment.hip"):
     if torch.device(device).type != "cuda":
         from ._lib import Mi355SegError
-        raise Mi355SegError(f"{what}: aug=True resamples with the HIP kernels of csrc/augment.hip and needs an MI355X (cuda/HIP) "
+        raise Mi355SegError(f"{what}: {option} and needs an MI355X (cuda/HIP) "
                             f"device, got {device}; there is no CPU fallback in this package")
+
+
+N_LABEL_CLASSES = 16            # classes 0 .. 15 of a label index; counts[16] is the `bad` bin (include/mi355seg.h)
+
+
+def parse_label_probabilities(value):
+    """``config.label_probabilities`` -> ``None`` or ``{label: weight}``: ``None`` / ``""`` / ``"None"`` give ``None`` (sample in
+    proportion to ``label > 0``, torchio's default), a dict passes through (keys and weights converted), the command-line form
+    ``"0:0.2,1:0.8"`` is parsed (a trailing comma is allowed: YAML reads a single ``1:1`` as the base-60 number 61, so a single pair is
+    written ``1:1,`` or ``{1: 1}``).  A negative or non-finite weight, a label outside 0 .. 15 or an all-zero dict raise ``ValueError``."""
+    if value is None or (isinstance(value, str) and value.strip() in ("", "None")):
+        return None
+    if isinstance(value, dict):
+        items = list(value.items())
+    elif isinstance(value, str):
+        items = []
+        for part in value.split(","):
+            if not part.strip() and items:                  # a trailing comma: "1:1," (what keeps a single pair a string in YAML)
+                continue
+            k, sep, w = part.partition(":")
+            if not sep or not k.strip() or not w.strip():
+                raise ValueError(f"label_probabilities: '{part}' in '{value}' is not label:weight (expected e.g. 0:0.2,1:0.8)")
+            items.append((k.strip(), w.strip()))
+    else:
+        raise ValueError(f"label_probabilities: expected None, a dict or a string 'label:weight,...' such as 0:0.2,1:0.8, got {value!r} "
+                         f"(YAML reads a single pair such as 1:1 as a base-60 number: write it with a trailing comma, 1:1, or as {{1: 1}})")
+    out = {}
+    for k, w in items:
+        try:
+            kf, wf = float(k), float(w)
+        except (TypeError, ValueError):
+            raise ValueError(f"label_probabilities: '{k}:{w}' is not label:weight with an integer label and a number") from None
+        if kf != int(kf) or not 0 <= int(kf) < N_LABEL_CLASSES:
+            raise ValueError(f"label_probabilities: label {k} is outside 0 .. {N_LABEL_CLASSES - 1}")
+        if not (wf >= 0.0 and np.isfinite(wf)):
+            raise ValueError(f"label_probabilities: the weight {w} of label {k} must be a finite number >= 0")
+        if int(kf) in out:
+            raise ValueError(f"label_probabilities: label {int(kf)} is given twice")
+        out[int(kf)] = wf
+    if not any(w > 0.0 for w in out.values()):
+        raise ValueError(f"label_probabilities: every weight of {value!r} is zero")
+    return out
+
+
+def draw_label_picks(rng, counts, label_probabilities, n):
+    """``n`` picks of tio.LabelSampler from the per-class voxel counts of a subject's region of valid patch centres (UNPINNED, the
+    definitions of include/mi355seg.h): ``(classes, ranks)`` as ``np.int64[n]``.  Pure host, needs no GPU and no library.
+    Class masses: without ``label_probabilities`` ``M[l] = counts[l]`` for l >= 1 and ``M[0] = 0`` (torchio: probability
+    proportional to ``label > 0``); with a dict ``{l: w_l}`` ``M[l] = w_l`` where ``counts[l] > 0`` and 0 elsewhere -- a label
+    absent from the region drops out and the rest renormalise, as torchio's cdf normalisation does.  ``sum M == 0`` raises
+    ``RuntimeError`` (torchio: empty probability map).  One sample draws ``u = rng.random()`` -- the class is the first whose
+    cumulative ``M / sum M`` exceeds u -- and then ``r = rng.integers(0, counts[class])``, in that order and nothing else."""
+    counts = np.asarray(counts, dtype=np.int64)[:N_LABEL_CLASSES]
+    mass = np.zeros(N_LABEL_CLASSES, dtype=np.float64)
+    if label_probabilities is None:
+        mass[1:counts.size] = counts[1:]
+    else:
+        for l, w in label_probabilities.items():
+            if 0 <= int(l) < counts.size and counts[int(l)] > 0:
+                mass[int(l)] = float(w)
+    cum = np.cumsum(mass)
+    if not cum[-1] > 0.0:
+        raise RuntimeError(f"empty probability map: no voxel of the region of valid patch centres carries a label with a positive "
+                           f"probability (label_probabilities={label_probabilities}, region counts {counts.tolist()})")
+    cdf = cum / cum[-1]                                     # ends in exactly 1.0 > u
+    classes, ranks = np.empty(n, dtype=np.int64), np.empty(n, dtype=np.int64)
+    for i in range(n):
+        u = rng.random()
+        l = int(np.searchsorted(cdf, u, side="right"))      # the first class with cdf > u; a class of mass 0 never is
+        classes[i] = l
+        ranks[i] = int(rng.integers(0, counts[l]))
+    return classes, ranks
 
 
 class AugmentParams:
@@ -137,11 +211,29 @@ class DevicePatchQueue:
     subject visit draws one ``AugmentParams`` from the queue's generator (after which its ``samples_per_volume`` origins are drawn as
     before) and has its statistics computed on the device (``functional.augment_stats``), the queue holds patch descriptors instead
     of views, and a batch is one small table upload and one resampling launch (``functional.augment_sample``); ``last_patches`` keeps
-    the descriptors of the batch yielded last.  With ``aug=False`` nothing changes."""
+    the descriptors of the batch yielded last.  With ``aug=False`` nothing changes.
+
+    ``sampler="label"`` (tio.LabelSampler(patch_size, label_probabilities) in the place of the UniformSampler; UNPINNED, the
+    definitions of include/mi355seg.h): a subject's label index is built on the device once (``functional.label_index``, kept in
+    ``label_indices`` for subjects that are themselves cached), every visit draws its ``samples_per_volume`` picks on the host
+    (``draw_label_picks``: per patch ``u`` then ``r``, nothing else), one select launch turns them into origins
+    (``functional.label_pick``), which are copied to the host once and cut as before.  ``label_probabilities``: ``None`` or
+    ``{label: weight}`` (``parse_label_probabilities``).  Labels must have one channel and hold integers 0 .. 15 inside the region of
+    valid patch centres.  With ``sampler="uniform"`` (the default) nothing changes."""
 
     def __init__(self, data_path, gt_path, patch_size, batch_size, iters, device, seed=1234, queue_length=10,
-                 samples_per_volume=10, cache_gb=200.0, aug=False):
+                 samples_per_volume=10, cache_gb=200.0, aug=False, sampler="uniform", label_probabilities=None):
         self.aug = bool(aug)
+        if sampler not in ("uniform", "label"):
+            raise ValueError(f"DevicePatchQueue: unknown sampler='{sampler}' (expected 'uniform' or 'label')")
+        self.sampler = sampler
+        self.label_probabilities = parse_label_probabilities(label_probabilities)
+        self.label_indices = {}
+        if sampler == "label":
+            if self.aug:
+                raise NotImplementedError("DevicePatchQueue: sampler='label' with aug=True is not implemented: an augmented visit would "
+                                          "have to sample from the RESAMPLED labels; use sampler='uniform' with aug=True")
+            _require_device(device, "DevicePatchQueue", "sampler='label' selects patch centres with the HIP kernels of csrc/sampler.hip")
         if self.aug:
             _require_device(device, "DevicePatchQueue")
         self.last_patches = None
@@ -184,11 +276,40 @@ class DevicePatchQueue:
             self.cache_bytes += nbytes
         return x, y
 
+    def _label_index(self, idx, y):
+        """the label index of subject ``idx`` (labels ``y``); kept while the subject itself is cached"""
+        hit = self.label_indices.get(idx)
+        if hit is not None:
+            return hit
+        from . import functional as F
+        from ._lib import Mi355SegError
+        if y.shape[0] != 1:
+            raise Mi355SegError(f"{self.files[idx]}: sampler='label' needs ONE label channel, got labels {tuple(y.shape)}")
+        index = F.label_index(y, self.ps)
+        if index.counts[N_LABEL_CLASSES] != 0:
+            raise ValueError(f"{self.files[idx]}: sampler='label': {int(index.counts[N_LABEL_CLASSES])} label voxels inside the region of "
+                             f"valid patch centres are not integers in 0 .. {N_LABEL_CLASSES - 1}")
+        if idx in self.cache:
+            self.label_indices[idx] = index
+        return index
+
     def _refill(self):
         while len(self._queue) < self.queue_length:
             if not self._order:
                 self._order = list(self.rng.permutation(len(self.files)))
-            x, y = self._subject(int(self._order.pop()))
+            idx = int(self._order.pop())
+            x, y = self._subject(idx)
+            if self.sampler == "label":
+                from . import functional as F
+                index = self._label_index(idx, y)
+                try:
+                    classes, ranks = draw_label_picks(self.rng, index.counts, self.label_probabilities, self.spv)
+                except RuntimeError as e:
+                    raise RuntimeError(f"{self.files[idx]}: {e}") from None
+                for o in F.label_pick(index, classes, ranks).cpu().numpy():     # the visit's one device-to-host copy
+                    sl = (slice(None),) + tuple(slice(int(a), int(a) + p) for a, p in zip(o, self.ps))
+                    self._queue.append((x[sl], y[sl]))
+                continue
             if self.aug:
                 from . import functional as F
                 prm = AugmentParams.draw(self.rng, x.shape[1:])
@@ -238,8 +359,14 @@ NpyPatches = DevicePatchQueue
 def make_loader(config, device, in_channels, seed=1234):
     iters = int(getattr(config, "iters_per_epoch", 4))
     aug = bool(getattr(config, "aug", False))             # conf/config.yaml:27; dataloader.py:69
+    sampler = str(getattr(config, "sampler", "uniform"))
+    label_probabilities = parse_label_probabilities(getattr(config, "label_probabilities", None))
     if str(config.data_path) == "synthetic":
+        if sampler != "uniform":
+            raise ValueError(f"config.sampler={sampler} needs volumes to sample from: with data_path=synthetic every sample is its own "
+                             f"volume (use config.sampler=uniform)")
         return SyntheticPatches(config.patch_size, in_channels, config.batch_size, iters, device, seed, aug=aug)
     return DevicePatchQueue(config.data_path, config.gt_path, config.patch_size, config.batch_size, iters, device, seed,
                             queue_length=int(getattr(config, "queue_length", 10)),
-                            samples_per_volume=int(getattr(config, "samples_per_volume", 10)), aug=aug)
+                            samples_per_volume=int(getattr(config, "samples_per_volume", 10)), aug=aug, sampler=sampler,
+                            label_probabilities=label_probabilities)

@@ -1824,6 +1824,74 @@ def augment_sample(patches, patch_size):
     return xb, yb
 
 
+LABEL_CHUNK = 1024              # MI355SEG_LABEL_CHUNK: region-linear voxels per chunk of a label index
+LABEL_BINS = 17                 # MI355SEG_LABEL_BINS: classes 0 .. 15 and the `bad` bin
+
+
+class LabelIndex:
+    """What ``label_index`` built for one (label volume, patch size) pair and ``label_pick`` selects from:
+    ``labels`` the contiguous device volume [D,H,W] the index belongs to (kept alive here: a select re-reads one chunk of it),
+    ``shape`` = (D, H, W), ``patch`` = (pd, ph, pw), ``region`` = (m_d, m_h, m_w) the extents of the box of valid patch centres,
+    ``index`` the device int64 [17, chunks] of exclusive per-class chunk prefixes, ``counts`` a HOST ``np.int64[17]``: the number of
+    region voxels of classes 0 .. 15, then ``bad`` (values that are no integer in [0, 16))."""
+
+    def __init__(self, labels, patch, index, counts):
+        self.labels, self.patch, self.index, self.counts = labels, patch, index, counts
+        self.shape = tuple(int(s) for s in labels.shape)
+        self.region = tuple(n - p + 1 for n, p in zip(self.shape, patch))
+
+
+def label_index(y, patch_size):
+    """The sampling index of tio.LabelSampler(patch_size) over the label volume ``y`` ([1,D,H,W] or [D,H,W], float32 holding integers):
+    per-class counts of the region of valid patch centres and their per-chunk prefixes, built in two launches
+    (mi355seg_label_index_build_f32) -> ``LabelIndex``.  One device-to-host copy of the 17 totals, the only synchronisation.
+    UNPINNED (torchio is absent): the definitions in include/mi355seg.h are the specification."""
+    _require_cuda(y, "label_index labels")
+    if y.dim() == 4 and y.shape[0] != 1:
+        raise Mi355SegError(f"label_index: expected ONE label channel, got {tuple(y.shape)} (multi-channel label maps are not sampled)")
+    v = y[0] if y.dim() == 4 else y
+    ps = tuple(int(p) for p in ((patch_size,) * 3 if isinstance(patch_size, int) else patch_size))
+    if v.dim() != 3 or len(ps) != 3 or v.numel() >= 1 << 31 or any(p < 1 or p > n for p, n in zip(ps, v.shape)):
+        raise Mi355SegError(f"label_index: expected labels [1,D,H,W] or [D,H,W] with D*H*W < 2^31 and a patch 1 <= p <= n per axis, "
+                            f"got {tuple(y.shape)} and patch {ps}")
+    v = v.contiguous()
+    D, H, W = v.shape
+    L = lib()
+    nbytes = L.query("mi355seg_label_index_bytes", D, H, W, *ps)
+    index = torch.empty((LABEL_BINS, nbytes // (8 * LABEL_BINS)), dtype=torch.int64, device=v.device)
+    counts = torch.empty(LABEL_BINS, dtype=torch.int64, device=v.device)
+    L.call("mi355seg_label_index_build_f32", _p(v), D, H, W, *ps, _p(index), nbytes, _p(counts), _stream())
+    return LabelIndex(v, ps, index, counts.cpu().numpy())
+
+
+def label_pick(index, classes, ranks):
+    """Patch origins of the picks ``(classes[i], ranks[i])`` -- the voxel of that class with that rank in region-linear order, see
+    include/mi355seg.h -- from a ``LabelIndex``: int32 [n, 3] (z, y, x) on the device, one small table upload and one launch
+    (mi355seg_label_index_select), no synchronisation.  ``classes`` / ``ranks``: host integer arrays, validated against
+    ``index.counts`` here because the kernel trusts them: class in 0 .. 15 and 0 <= rank < counts[class], else ``Mi355SegError``
+    before any launch."""
+    if not isinstance(index, LabelIndex):
+        raise Mi355SegError(f"label_pick: expected the LabelIndex of label_index, got {type(index).__name__}")
+    cl, rk = np.asarray(classes), np.asarray(ranks)
+    if cl.ndim != 1 or cl.shape != rk.shape or cl.size < 1 or cl.dtype.kind not in "iu" or rk.dtype.kind not in "iu":
+        raise Mi355SegError(f"label_pick: expected two equally long 1-D integer arrays of at least one pick, got {cl.dtype}{cl.shape} "
+                            f"and {rk.dtype}{rk.shape}")
+    cl, rk = cl.astype(np.int64), rk.astype(np.int64)
+    if ((cl < 0) | (cl >= LABEL_BINS - 1)).any():
+        raise Mi355SegError(f"label_pick: class {int(cl[(cl < 0) | (cl >= LABEL_BINS - 1)][0])} is outside 0 .. 15")
+    bad = (rk < 0) | (rk >= index.counts[cl])
+    if bad.any():
+        i = int(np.flatnonzero(bad)[0])
+        raise Mi355SegError(f"label_pick: pick {i}: rank {int(rk[i])} is outside the {int(index.counts[cl[i]])} region voxels of class "
+                            f"{int(cl[i])}")
+    v = index.labels
+    picks = torch.from_numpy(np.ascontiguousarray(np.stack([cl, rk], axis=1))).to(v.device)
+    origins = torch.empty((cl.size, 3), dtype=torch.int32, device=v.device)
+    D, H, W = index.shape
+    lib().call("mi355seg_label_index_select", _p(v), D, H, W, *index.patch, _p(index.index), _p(picks), int(cl.size), _p(origins), _stream())
+    return origins
+
+
 _BAND_BASIS = {}                # (n, limit, device) -> (float32 [q, n] on the device, r, q)
 
 

@@ -707,6 +707,39 @@ int mi355seg_augment_stats_f32(const float* x, int C, int D, int H, int W, const
 int mi355seg_augment_sample_f32(const int* table, int count, int C, int Cy, int pd, int ph, int pw, float* out_x, float* out_y,
                                 void* stream);
 
+/* ------------------------------------------------------------------ Label-balanced patch sampling (tio.LabelSampler, dataloader.py:19)
+ * config.sampler=label: where the queue cuts its patches is drawn from the label map instead of uniformly.  UNPINNED (torchio is
+ * absent and the reference holds no fixture of its data pipeline): the definitions here are the specification.
+ *   labels  y [1,D,H,W] = [D,H,W], fp32 holding integers (as the queue caches them); n = (D, H, W); patch p = (pd, ph, pw), p_d <= n_d
+ *   origin  o is valid when 0 <= o_d <= n_d - p_d; its centre is c = o + p // 2 (torchio: crop_ini = p // 2, crop_fin = (p - 1) // 2,
+ *           index_ini = centre - p // 2)
+ *   region  R, the box of valid centres: extents m_d = n_d - p_d + 1, start p_d // 2.  The region-linear index of a voxel of R is
+ *           e = (z * m_h + y) * m_w + x with (z, y, x) relative to R's start; the origin of the patch centred there is exactly (z, y, x)
+ *   classes the integers 0 .. 15; count[l] = the number of voxels of R with label l; a voxel of R whose value is not an integer in
+ *           [0, 16) (NaN and the infinities included) is counted in a 17th bin, bad = count[16].  Voxels outside R are never read.
+ *   pick    (class l, rank r), 0 <= r < count[l]: the voxel of class l with rank r in region-linear order
+ * The host turns two random draws into a pick from count[] (class masses: count[l] for l >= 1 and 0 for l = 0 without
+ * label_probabilities; else w_l where count[l] > 0, renormalised); everything on the device is integer arithmetic, so a result is
+ * exact, and without atomics equal inputs give bitwise equal outputs.
+ * R is cut into chunks of MI355SEG_LABEL_CHUNK consecutive region-linear voxels (the last one ragged).
+ * mi355seg_label_index_bytes: the size of the index of one (volume, patch) pair, chunks * 17 * 8 bytes (0 for bad arguments).
+ * mi355seg_label_index_build_f32, once per (subject, patch size), two launches: one workgroup per chunk counts its 17 bins (wave
+ * ballots), then one workgroup per bin turns the per-chunk counts into exclusive prefixes.  index: int64 [17][chunks] on the device,
+ * index[l][k] = the number of voxels of class l in chunks 0 .. k-1; counts17: int64 [17] on the DEVICE, the totals count[0..15], bad.
+ * mi355seg_label_index_select, one launch, one workgroup per pick: picks = int64 [n][2] (class, rank) on the device; binary search of
+ * the rank in the class's prefixes, one re-read of that chunk, ballot prefix count; writes origins int32 [n][3] = (z, y, x).  The
+ * select trusts class < 16 and rank < count[class] -- the caller holds the counts; for a pick outside that the origin is left
+ * unwritten (no access leaves the index or the volume).  labels, geometry and index must be the ones of the build.
+ * Bad arguments (null pointers, p_d > n_d, D*H*W >= 2^31, too small an index_bytes, n < 1) return an error code with
+ * mi355seg_last_error.  Neither entry point allocates or synchronises. */
+#define MI355SEG_LABEL_CHUNK 1024
+#define MI355SEG_LABEL_BINS 17
+size_t mi355seg_label_index_bytes(int D, int H, int W, int pd, int ph, int pw);
+int mi355seg_label_index_build_f32(const float* labels, int D, int H, int W, int pd, int ph, int pw,
+                                   void* index, size_t index_bytes, long long* counts17, void* stream);
+int mi355seg_label_index_select(const float* labels, int D, int H, int W, int pd, int ph, int pw, const void* index,
+                                const long long* picks, int n, int* origins, void* stream);
+
 /* ------------------------------------------------------------------ Frequency-band split of the IS network (train.py:76-88,198-201)
  * low_pass_torch / high_pass_torch at `limit`: the reference masks the spectrum of x [B,C,D,H,W] on its last two axes with the outer
  * product of (|fftfreq(H)| < limit, |rfftfreq(W)| < limit) for the low band and of the two `> limit` masks for the high band.  Per
