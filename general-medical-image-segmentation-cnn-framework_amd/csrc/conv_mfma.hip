@@ -179,6 +179,7 @@ static PackDesc lowp_desc(int np, const float* w, void* wq, int K, int Nn, int T
     PackDesc d{};
     d.kind = PD_LOWP; d.np = np; d.w = w; d.dst = wq; d.oscale = oscale;
     d.K = K; d.Nn = Nn; d.T = T; d.P = NT; d.mode = mode; d.aux = aux; d.CK = CK; d.TW = TW; d.taps = taps;
+    d.layout = (long long)K * Nn * T < 0x7F000000LL ? 0 : 1;          // (1: 64-bit element indices)
     return d;
 }
 
@@ -186,19 +187,19 @@ static int pack_grid(long long total) { return (int)((total + 255) / 256 > 2048 
 // MATH_X3: sized for the 28-tap layout of conv_x3s.hip (27 taps + one zero tap), which is the larger of its two packings
 // MATH_B16 likewise for conv_b16s.hip (taps paired: one zero tap when the tap count is odd)
 static size_t wq_bytes(int math, size_t nelem) { return math == MATH_F32 ? nelem * 4 : (math == MATH_X3 ? (nelem + nelem / 27 + 64) * 6 : (nelem + nelem / 27 + 64) * 2); }
-// the generic layouts; the low-precision ones with fewer than 2^31 elements through a descriptor (*desc, when asked for, tells the caller
-// what was launched so that a recorded step can replay it: kind 0 = not replayable)
+// the generic layouts, packed into wq by a launch of their own: the exact-fp32 one, or a low-precision one by its descriptor
 static void launch_pack(int math, const float* w, void* wq, int K, int Nn, int T, int NT, int mode, int aux, int CK, int TW, const TapList& taps,
-                        hipStream_t st, const float* oscale = nullptr, PackDesc* desc = nullptr) {
-    const int grid = pack_grid((long long)K * Nn * T);
-    if (desc) desc->kind = 0;
-    if (math == MATH_F32) hipLaunchKernelGGL(pack_wq_kernel, dim3(grid), dim3(256), 0, st, w, (float*)wq, K, Nn, T, NT, mode, aux, CK, TW, taps, oscale);
-    else {
-        PackDesc d = lowp_desc(math == MATH_X3 ? 3 : 1, w, wq, K, Nn, T, NT, mode, aux, CK, TW, taps, oscale);
-        d.layout = (long long)K * Nn * T < 0x7F000000LL ? 0 : 1;          // (1: 64-bit element indices)
-        pack_launch(d, st);
-        if (desc) *desc = d;
-    }
+                        hipStream_t st, const float* oscale = nullptr) {
+    if (math == MATH_F32) hipLaunchKernelGGL(pack_wq_kernel, dim3(pack_grid((long long)K * Nn * T)), dim3(256), 0, st, w, (float*)wq, K, Nn, T, NT, mode, aux, CK, TW, taps, oscale);
+    else pack_launch(lowp_desc(math == MATH_X3 ? 3 : 1, w, wq, K, Nn, T, NT, mode, aux, CK, TW, taps, oscale), st);
+}
+// the same as a pack site of a training step (pack.h, prepack_use): the packing to read -- wq (`bytes` of the workspace), or the copy the
+// step's plan holds under `key`.  The exact-fp32 layout is no part of any plan.
+static void* step_pack(const PackKey& key, size_t bytes, int math, const float* w, void* wq, int K, int Nn, int T, int NT, int mode, int aux, int CK, int TW,
+                       const TapList& taps, hipStream_t st) {
+    if (math != MATH_F32) return prepack_use(key, bytes, lowp_desc(math == MATH_X3 ? 3 : 1, w, wq, K, Nn, T, NT, mode, aux, CK, TW, taps, nullptr), st);
+    launch_pack(math, w, wq, K, Nn, T, NT, mode, aux, CK, TW, taps, st);
+    return wq;
 }
 
 // y[r][c] = bias[c] + sum_k part[k][r][c]   (split-K second stage; fixed order)
@@ -460,7 +461,8 @@ int conv_fwd_mfma(int math, const void* x, int ldx, const float* w, const float*
     // fp32 tensors under f16x3: the large layers run conv_x3w's 8 x 4 x 16 tiles (fewer, larger M-tiles: decided before anything is sized by nM)
     const bool x3w = math == MATH_X3 && x3s_enabled() && x3_f16() && x3s_plan_ok(p, x, ldx, y, ldy, (long long)D * H * W) && x3w_plan(p, N, D, H, W, Cin, Cout, ksplit);
     Carver cv(ws);
-    void* wq = cv.take<char>(wq_bytes(math, (size_t)T * Cin * Cout));
+    const size_t wq_size = wq_bytes(math, (size_t)T * Cin * Cout);
+    void* wq = cv.take<char>(wq_size);
     float* spart = (ssum && ksplit == 1) ? cv.take<float>((size_t)p.nM * Cout * 3) : nullptr;
     float* slabs = ksplit > 1 ? cv.take<float>((size_t)ksplit * nvox * Cout) : nullptr;
     // fp32 tensors, bf16x6, 16-wide tiles: the 16x16x32-MFMA kernel (conv_x3s.hip) with its own weight packing
@@ -499,18 +501,19 @@ int conv_fwd_mfma(int math, const void* x, int ldx, const float* w, const float*
         }
     }
     if (!pk_hit) {
-        PackDesc pd{};
         const int dg = dgrad ? 1 : 0;
-        if (pk_form == 1) pd = tiled_desc(2, w, wq, Cin, Cout, 27, p.NBW, dg, oscale, w_amax);
-        else if (pk_form == 3) pd = tiled_desc(0, w, wq, Cin, Cout, T, bp.NT, dg, oscale, nullptr);
-        else if (pk_form == 5) pd = tiled_desc(1, w, wq, Cin, Cout, 27, p.NBW, dg, oscale, nullptr);
-        if (pd.kind) pack_launch(pd, st);
-        else if (pk_form == 2) hipLaunchKernelGGL(pack_wq_x3s_f16_kernel, dim3(pack_grid((long long)28 * Cin * Cout)), dim3(256), 0, st, w, (_Float16*)wq, Cin, Cout, p.NBW, dg, oscale, w_amax);
+        // the forms no plan replays: the per-element kernels for a w that is not 16-byte aligned, the exact-fp32 layout
+        if (pk_form == 2) hipLaunchKernelGGL(pack_wq_x3s_f16_kernel, dim3(pack_grid((long long)28 * Cin * Cout)), dim3(256), 0, st, w, (_Float16*)wq, Cin, Cout, p.NBW, dg, oscale, w_amax);
         else if (pk_form == 4) hipLaunchKernelGGL(pack_wq_b16s_kernel, dim3(pack_grid((long long)(T + 1) * Cin * Cout)), dim3(256), 0, st, w, (bf16*)wq, Cin, Cout, T, bp.NT, dg, oscale);
         else if (pk_form == 6) hipLaunchKernelGGL(pack_wq_x3s_kernel, dim3(pack_grid((long long)28 * Cin * Cout)), dim3(256), 0, st, w, (bf16*)wq, Cin, Cout, p.NBW, dg, oscale);
-        else launch_pack(math, w, wq, Cin, Cout, T, p.NT, dg, 0, p.CK, T, TapList{}, st, oscale, &pd);
+        else if (math == MATH_F32) launch_pack(math, w, wq, Cin, Cout, T, p.NT, dg, 0, p.CK, T, TapList{}, st, oscale);
+        // the replayable ones, noted while the step is being recorded
+        else pack_and_note(pkey, wq_size,
+                           pk_form == 1 ? tiled_desc(2, w, wq, Cin, Cout, 27, p.NBW, dg, oscale, w_amax)
+                           : pk_form == 3 ? tiled_desc(0, w, wq, Cin, Cout, T, bp.NT, dg, oscale, nullptr)
+                           : pk_form == 5 ? tiled_desc(1, w, wq, Cin, Cout, 27, p.NBW, dg, oscale, nullptr)
+                                          : lowp_desc(math == MATH_X3 ? 3 : 1, w, wq, Cin, Cout, T, p.NT, dg, 0, p.CK, T, TapList{}, oscale), st);
         SEG_CHECK_LAUNCH();
-        if (pd.kind) prepack_note(pkey, wq_bytes(math, (size_t)T * Cin * Cout), pd);
     }
     IgemmArgs a{x, wq, ksplit > 1 ? nullptr : bias, ksplit > 1 ? (void*)slabs : y, spart, ldx, ksplit > 1 ? Cout : ldy, N, D, H, W, Cout,
                 p.ntx, p.nty, p.ntz, p.nN, nchunks, nchunks, p.nN, 1, 1, p.nM, ksplit, nchunks / ksplit, nvox * Cout, dbg_flags()};
@@ -579,17 +582,11 @@ int convt_fwd_mfma(int math, const void* x, int ldx, const float* w, const float
     IgemmPlan p;
     SEG_CHECK_ARG(igemm_plan(math, 1, N, D, H, W, Cin, Cout, 8, &p), "convt_fwd_mfma: unsupported shape");
     Carver cv(ws);
-    void* wq = cv.take<char>(wq_bytes(math, (size_t)8 * Cin * Cout));
+    const size_t wq_size = wq_bytes(math, (size_t)8 * Cin * Cout);
+    void* wq = cv.take<char>(wq_size);
     SEG_CHECK_WS(cv.used(), ws_bytes);
-    {
-        const PackKey pkey = make_pack_key(w, PK_CONVT_FWD, math, Cin, Cout, p.NT, p.CK);
-        if (!prepack_find(pkey, &wq, nullptr)) {
-            PackDesc pd{};
-            launch_pack(math, w, wq, Cin, 8 * Cout, 1, p.NT, 2, Cout, p.CK, 8, TapList{}, st, nullptr, &pd);
-            SEG_CHECK_LAUNCH();
-            if (pd.kind) prepack_note(pkey, wq_bytes(math, (size_t)8 * Cin * Cout), pd);
-        }
-    }
+    wq = step_pack(make_pack_key(w, PK_CONVT_FWD, math, Cin, Cout, p.NT, p.CK), wq_size, math, w, wq, Cin, 8 * Cout, 1, p.NT, 2, Cout, p.CK, 8, TapList{}, st);
+    SEG_CHECK_LAUNCH();
     IgemmArgs a{x, wq, bias, y, nullptr, ldx, ldy, N, D, H, W, Cout, p.ntx, p.nty, p.ntz, p.nN, Cin / p.CK, Cin / p.CK,
                 p.flat ? p.nN : p.nN / 8, 1, 2, p.nM, 1, Cin / p.CK, 0, 0};
     a.Di = D; a.Hi = H; a.Wi = W; a.Do = 2 * D; a.Ho = 2 * H; a.Wo = 2 * W; a.flatn = p.flat;
@@ -606,17 +603,11 @@ int convt_dgrad_mfma(int math, const void* dy, int lddy, const float* w, void* d
     IgemmPlan p;
     SEG_CHECK_ARG(igemm_plan(math, 1, N, D, H, W, Cout, Cin, 1, &p), "convt_dgrad_mfma: unsupported shape");
     Carver cv(ws);
-    void* wq = cv.take<char>(wq_bytes(math, (size_t)8 * Cin * Cout));
+    const size_t wq_size = wq_bytes(math, (size_t)8 * Cin * Cout);
+    void* wq = cv.take<char>(wq_size);
     SEG_CHECK_WS(cv.used(), ws_bytes);
-    {
-        const PackKey pkey = make_pack_key(w, PK_CONVT_DGRAD, math, Cin, Cout, p.NT, p.CK);
-        if (!prepack_find(pkey, &wq, nullptr)) {
-            PackDesc pd{};
-            launch_pack(math, w, wq, 8 * Cout, Cin, 1, p.NT, 3, Cout, p.CK, 8, TapList{}, st, nullptr, &pd);
-            SEG_CHECK_LAUNCH();
-            if (pd.kind) prepack_note(pkey, wq_bytes(math, (size_t)8 * Cin * Cout), pd);
-        }
-    }
+    wq = step_pack(make_pack_key(w, PK_CONVT_DGRAD, math, Cin, Cout, p.NT, p.CK), wq_size, math, w, wq, 8 * Cout, Cin, 1, p.NT, 3, Cout, p.CK, 8, TapList{}, st);
+    SEG_CHECK_LAUNCH();
     IgemmArgs a{dy, wq, nullptr, dx, nullptr, lddy, lddx, N, D, H, W, Cin, p.ntx, p.nty, p.ntz, p.nN, 8 * Cout / p.CK, Cout / p.CK, p.nN, 2, 1,
                 p.nM, 1, 8 * Cout / p.CK, 0, 0};
     a.Di = 2 * D; a.Hi = 2 * H; a.Wi = 2 * W; a.Do = D; a.Ho = H; a.Wo = W;
@@ -678,20 +669,14 @@ int conv_gather_fwd_mfma(int math, const void* x, int ldx, const float* w, const
     const int ksplit = (ldy % 4 == 0) ? pick_ksplit(p.nM * p.nN, nchunks) : 1;
     const long long nvo = (long long)N * Do * Ho * Wo;
     Carver cv(ws);
-    void* wq = cv.take<char>(wq_bytes(math, (size_t)T * Cin * Cout));
+    const size_t wq_size = wq_bytes(math, (size_t)T * Cin * Cout);
+    void* wq = cv.take<char>(wq_size);
     float* spart = (ssum && ksplit == 1) ? cv.take<float>((size_t)p.nM * Cout * 3) : nullptr;
     float* slabs = ksplit > 1 ? cv.take<float>((size_t)ksplit * nvo * Cout) : nullptr;
     const size_t tail = cv.used();
     SEG_CHECK_WS(tail + ((ssum && ksplit > 1) ? colsum_ws_bytes(Cout) : 0), ws_bytes);
-    {
-        const PackKey pkey = make_pack_key(w, PK_GATHER_FWD, math, Cin, Cout, T, p.NT, p.CK);
-        if (!prepack_find(pkey, &wq, nullptr)) {
-            PackDesc pd{};
-            launch_pack(math, w, wq, T * Cin, Cout, 1, p.NT, 5, Cin, p.CK, T, TapList{}, st, nullptr, &pd);
-            SEG_CHECK_LAUNCH();
-            if (pd.kind) prepack_note(pkey, wq_bytes(math, (size_t)T * Cin * Cout), pd);
-        }
-    }
+    wq = step_pack(make_pack_key(w, PK_GATHER_FWD, math, Cin, Cout, T, p.NT, p.CK), wq_size, math, w, wq, T * Cin, Cout, 1, p.NT, 5, Cin, p.CK, T, TapList{}, st);
+    SEG_CHECK_LAUNCH();
     IgemmArgs a{x, wq, ksplit > 1 ? nullptr : bias, ksplit > 1 ? (void*)slabs : y, spart, ldx, ksplit > 1 ? Cout : ldy, N, Do, Ho, Wo, Cout, p.ntx, p.nty, p.ntz, p.nN, nchunks, cpt, p.nN, stride, 1,
                 p.nM, ksplit, nchunks / ksplit, nvo * Cout, 0};
     a.Di = D; a.Hi = H; a.Wi = W; a.Do = Do; a.Ho = Ho; a.Wo = Wo;
@@ -731,7 +716,8 @@ int conv_gather_dgrad_mfma(int math, const void* dy, int lddy, const float* w, v
     SEG_CHECK_ARG(((uintptr_t)dy % 16) == 0, "conv_gather_dgrad_mfma: gradient pointer must be 16-byte aligned");
     const int T = k * k * k;
     Carver cv(ws);
-    char* wq_all = cv.take<char>(wq_bytes(math, (size_t)T * Cin * Cout));
+    const size_t wq_size = wq_bytes(math, (size_t)T * Cin * Cout);
+    char* const wq_all = cv.take<char>(wq_size);
     SEG_CHECK_WS(cv.used(), ws_bytes);
     ProfScope ps(PF_IGEMM, 2.0 * (double)N * Do * Ho * Wo * T * Cin * Cout,
                  matrix_bytes(math, (double)N * D * H * W * Cin + (double)N * Do * Ho * Wo * Cout, (double)T * Cin * Cout), st);
@@ -776,23 +762,27 @@ int conv_gather_dgrad_mfma(int math, const void* dy, int lddy, const float* w, v
         multi = phs[i].nt <= 8 && p.KS == p0.KS && p.CK == p0.CK && p.BX == p0.BX && p.MB == p0.MB && p.NBW == p0.NBW && p.WN == 1 && p.nN == p0.nN && !p.flat;
         taps_total += phs[i].nt;
     }
-    multi = multi && taps_total == T;
+    // (decided before any packing is looked up or launched: the per-phase launches below pack eight separately padded pieces, into the workspace only)
+    multi = multi && taps_total == T && igemm_phases_lowp_has(math, phs[0].p);
     if (multi) {
         const IgemmPlan& p0 = phs[0].p;
         const int cpt = Cout / p0.CK;
         const size_t chunk_bytes = (size_t)p0.CK * p0.NT * esize(math);          // one (N-tile, chunk) of the packing (bf16: one plane)
+        TapList tl{};
+        for (int i = 0, slot = 0; i < nph; ++i)
+            for (int sl = 0; sl < phs[i].nt; ++sl) tl.t[slot++] = phs[i].tl.t[sl];
+        const char* wq = (const char*)step_pack(make_pack_key(w, PK_GATHER_DGRAD, math, Cin, Cout, k * 256 + stride * 16 + pad, p0.NT, p0.CK), wq_size,
+                                                math, w, wq_all, T * Cout, Cin, 1, p0.NT, 6, Cout, p0.CK, T, tl, st);
+        SEG_CHECK_LAUNCH();
         IgemmArgs a = phs[0].a;
         IgemmPhases pt{};
-        TapList tl{};
         int slot0 = 0, first = 0;
         for (int i = 0; i < nph; ++i) {
             const Phase& q = phs[i];
-            for (int sl = 0; sl < q.nt; ++sl) {
-                tl.t[slot0 + sl] = q.tl.t[sl];
+            for (int sl = 0; sl < q.nt; ++sl)
                 for (int c = 0; c < 4; ++c) a.toff[8 * i + sl][c] = q.a.toff[sl][c];
-            }
             IgemmPhase& f = pt.ph[i];
-            f.wq = wq_all + (size_t)slot0 * cpt * chunk_bytes;
+            f.wq = wq + (size_t)slot0 * cpt * chunk_bytes;
             f.D = q.a.D; f.H = q.a.H; f.W = q.a.W; f.ntx = q.p.ntx; f.nty = q.p.nty; f.ntz = q.p.ntz;
             f.by = tile_block(f.nty); f.bz = f.ntz >= 4 ? 4 : tile_block(f.ntz);
             f.nchunks = q.nt * cpt; f.wstride = T * cpt; f.cz = q.a.cz; f.cy = q.a.cy; f.cx = q.a.cx; f.first = first;
@@ -800,24 +790,10 @@ int conv_gather_dgrad_mfma(int math, const void* dy, int lddy, const float* w, v
             slot0 += q.nt;
         }
         pt.n = nph;
-        {
-            const PackKey pkey = make_pack_key(w, PK_GATHER_DGRAD, math, Cin, Cout, k * 256 + stride * 16 + pad, p0.NT, p0.CK);
-            void* hit = nullptr;
-            if (prepack_find(pkey, &hit, nullptr)) {
-                for (int i = 0; i < nph; ++i) pt.ph[i].wq = (const char*)hit + ((const char*)pt.ph[i].wq - wq_all);
-                wq_all = (char*)hit;
-            } else {
-                PackDesc pd{};
-                launch_pack(math, w, wq_all, T * Cout, Cin, 1, p0.NT, 6, Cout, p0.CK, T, tl, st, nullptr, &pd);
-                SEG_CHECK_LAUNCH();
-                if (pd.kind) prepack_note(pkey, wq_bytes(math, (size_t)T * Cin * Cout), pd);
-            }
-        }
-        a.wq = wq_all; a.total = first;
-        if (dispatch_igemm_phases_lowp(math, p0, a, pt, first, st)) {
-            SEG_CHECK_LAUNCH();
-            return MI355SEG_OK;
-        }
+        a.wq = wq; a.total = first;
+        SEG_CHECK_ARG(dispatch_igemm_phases_lowp(math, p0, a, pt, first, st), "conv_gather_dgrad_mfma: internal: no one-launch instantiation for a plan igemm_phases_lowp_has accepted");
+        SEG_CHECK_LAUNCH();
+        return MI355SEG_OK;
     }
     size_t wq_used = 0;
     for (int i = 0; i < nph; ++i) {

@@ -500,21 +500,12 @@ int convt_direct(bool gather, const TT* x, int ldx, const float* w, const float*
     CtPlan p;
     SEG_CHECK_ARG(ct_plan((int)sizeof(TT), gather, (long long)N * D * H * W, Cin, Cout, &p), "convt_direct: unsupported shape");
     Carver cv(ws);
-    bf16x8_t* wq = reinterpret_cast<bf16x8_t*>(cv.take<char>((size_t)p.K * p.Nc * 2 * NP));
+    const size_t wq_size = (size_t)p.K * p.Nc * 2 * NP;
+    PackDesc pd{};
+    pd.kind = PD_CONVT; pd.np = NP; pd.w = w; pd.dst = cv.take<char>(wq_size); pd.K = Cin; pd.Nn = Cout; pd.mode = gather ? 1 : 0; pd.P = p.BN; pd.aux = p.K; pd.TW = p.Nc;
     SEG_CHECK_WS(cv.used(), ws_bytes);
-    const long long slots = (long long)p.K * p.Nc / 8;
-    {
-        const PackKey pkey = make_pack_key(w, PK_CONVT_DIRECT, NP, Cin, Cout, gather ? 1 : 0, p.BN, p.K, p.Nc);
-        void* hit = nullptr;
-        if (prepack_find(pkey, &hit, nullptr)) wq = reinterpret_cast<bf16x8_t*>(hit);
-        else {
-            PackDesc pd{};
-            pd.kind = PD_CONVT; pd.np = NP; pd.w = w; pd.dst = wq; pd.K = Cin; pd.Nn = Cout; pd.mode = gather ? 1 : 0; pd.P = p.BN; pd.aux = p.K; pd.TW = p.Nc;
-            pack_launch(pd, st);
-            SEG_CHECK_LAUNCH();
-            prepack_note(pkey, (size_t)p.K * p.Nc * 2 * NP, pd);
-        }
-    }
+    const bf16x8_t* wq = reinterpret_cast<const bf16x8_t*>(prepack_use(make_pack_key(w, PK_CONVT_DIRECT, NP, Cin, Cout, gather ? 1 : 0, p.BN, p.K, p.Nc), wq_size, pd, st));
+    SEG_CHECK_LAUNCH();
     CtArgs a{x, wq, gather ? nullptr : bias, y, ldx, ldy, D, H, W, Cout, (long long)N * D * H * W, p.K / 64, p.Nc / p.BN, gather ? nullptr : reinterpret_cast<unsigned*>(y_amax),
              1, p.K / 64, 0};
     const double vox = (double)a.nvox;

@@ -773,7 +773,8 @@ int get_b16_tiles();
 
 // conv_igemm_lowp.hip: the MATH_X3 / MATH_B16 instantiations (their own translation unit: they compile in parallel)
 void dispatch_igemm_lowp(int math, const IgemmPlan& p, const IgemmArgs& a, int nwg, hipStream_t st);
-bool dispatch_igemm_phases_lowp(int math, const IgemmPlan& p, const IgemmArgs& a, const IgemmPhases& pt, int nwg, hipStream_t st);     // false: no such instantiation
+bool dispatch_igemm_phases_lowp(int math, const IgemmPlan& p, const IgemmArgs& a, const IgemmPhases& pt, int nwg, hipStream_t st);     // false: no such instantiation (igemm_phases_lowp_has)
 bool igemm_lowp_has(int math, int KS, int CK, int BX, int MB);
+bool igemm_phases_lowp_has(int math, const IgemmPlan& p);
 
 }  // namespace seg

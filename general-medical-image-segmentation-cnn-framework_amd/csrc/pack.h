@@ -33,15 +33,19 @@ struct PackDesc {
 };
 size_t pack_lds_bytes(const PackDesc& d);
 int pack_blocks(const PackDesc& d);
+long long pack_src_elems(const PackDesc& d);      // the fp32 elements of `w` the packing reads: [w, w + that)
 void pack_launch(const PackDesc& d, hipStream_t st);
 
-// a recorded step's packings (mi355seg_prepack_*): a pack site builds its key (weight pointer, site, the integers that fix the layout) and
-// asks prepack_find -- on a hit `*wq` is the arena copy and `*w_amax`, for a packing that scales by max |w|, the scalar it was scaled
-// with -- and otherwise packs in place (pack_launch) and hands the descriptor to prepack_note (kept only while a plan is being recorded)
+// a recorded step's packings (mi355seg_prepack_*).  A pack site builds its key (weight pointer, site, the integers that fix the layout) and the
+// descriptor of the packing into its workspace (d.dst, the `bytes` the site carved), and reads what prepack_use returns: the arena copy when the step's
+// plan holds the key (`*w_amax`, if asked for, is then the scalar a packing that scales by max |w| was scaled with), else d.dst, packed by a launch of its
+// own (pack_launch; the caller checks it) and noted while a plan is being recorded.  conv_fwd_mfma, which measures max |w| between the lookup and the
+// packing, calls the two halves itself: prepack_find, then pack_and_note.  A packing with an oscale never enters or leaves a plan.
 struct PackKey { const void* w; int kind; int p[7]; };
 PackKey make_pack_key(const void* w, int kind, int a = 0, int b = 0, int c = 0, int d = 0, int e = 0, int f = 0, int g = 0);
+void* prepack_use(const PackKey& key, size_t bytes, const PackDesc& d, hipStream_t st, const float** w_amax = nullptr);
 bool prepack_find(const PackKey& key, void** wq, const float** w_amax);
-void prepack_note(const PackKey& key, size_t bytes, const PackDesc& d);
+void* pack_and_note(const PackKey& key, size_t bytes, const PackDesc& d, hipStream_t st);
 enum { PK_CONV = 1, PK_CONVT_FWD, PK_CONVT_DGRAD, PK_GATHER_FWD, PK_GATHER_DGRAD, PK_CONVT_DIRECT };
 
 }  // namespace seg

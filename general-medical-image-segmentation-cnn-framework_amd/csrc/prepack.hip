@@ -5,19 +5,22 @@
 // to build into the workspace right in front of the launch: 44 launches of 4-9 us per cfg-2 step, ~50 per UNETR step, each on the
 // stream's critical path (a kernel starts when its predecessor has drained) although it depends on nothing but the weights.  Here
 // every such packing is described by a PackDesc (what pack_launch runs), and a train step can have ALL of them formed at once:
-//   * the first step of a model at a shape RECORDS the descriptors its convolutions pack with (key = weight pointer + kind + layout);
+//   * the first step of a model at a shape RECORDS the descriptors its convolutions pack parameter storage with (key = weight pointer + kind + layout);
 //   * every later step starts with mi355seg_prepack_run: one memset + one launch measuring max |w| of the f16x3-scaled weights + ONE
 //     launch (pack_all_kernel: block -> job by a table in the arena) that writes every packing into a caller-owned arena, on the
 //     step's own stream; a convolution that finds its key reads the arena copy and launches nothing.
 // (r6 first tried the same replay on a SIDE stream beside the step's first kernels: 0.1-0.5 ms slower on every workload,
 //  profiles/r06_prepack_side_stream_REVERTED.log -- small kernels on a second queue delay the main queue's launches.)
 // A key that is not found (another shape, another model, inference, a misaligned weight tensor) packs in place as before.
+// The pack sites (conv_mfma.hip, convt_direct.hip) see one call of this protocol: prepack_use (pack.h).
 #include "common.h"
 #include "internal.h"
 #include "igemm_kernel.h"
 #include "pack.h"
-#include <vector>
+#include <algorithm>
 #include <cstring>
+#include <mutex>
+#include <vector>
 
 namespace seg {
 
@@ -219,14 +222,28 @@ struct PackPlan {
     size_t arena_bytes = 0, amax_off = 0, tab_off = 0, lds = 0;
     int namax = 0, nblocks = 0, amax_blocks = 0;
     const void* uploaded_to = nullptr;
-    bool sealed = false;
 };
 
-std::vector<PackPlan*> g_plans;      // index = plan id - 1 (nullptr once freed)
-PackPlan* g_rec = nullptr;           // being recorded
-PackPlan* g_act = nullptr;           // replayed for the running step
-char* g_arena = nullptr;
-int g_cursor = 0;
+// The step state: ONE bracket per process at a time -- a recording (record_begin .. record_end) or a replay (prepack_run .. prepack_done).
+// Per process, not per thread: a step's backward runs on autograd's device thread, not on the thread that opened the bracket.  Read and
+// written under g_mu only, by the entry points and by the pack sites' lookup / note (about a hundred uncontended locks per step).
+struct StepState {
+    std::vector<PackPlan*> plans;    // index = plan id - 1 (nullptr once freed)
+    PackPlan* rec = nullptr;         // being recorded
+    PackPlan* act = nullptr;         // replayed for the running step (plan id act_id), out of `arena`
+    char* arena = nullptr;
+    int act_id = 0, cursor = 0;
+    PackPlan* plan_of(int id) const { return (id >= 1 && id <= (int)plans.size()) ? plans[id - 1] : nullptr; }
+} g_step;
+std::mutex g_mu;
+using Lock = std::lock_guard<std::mutex>;
+
+// the refusal of a second bracket, naming the open one (which stays as it is); false when none is open
+bool bracket_open(const char* who) {
+    if (g_step.rec) set_error("%s: a recording is open (record_begin without record_end); one bracket per process at a time", who);
+    else if (g_step.act) set_error("%s: plan %d is being replayed (prepack_run without prepack_done); one bracket per process at a time", who, g_step.act_id);
+    return g_step.rec || g_step.act;
+}
 
 bool key_eq(const PackKey& a, const PackKey& b) { return std::memcmp(&a, &b, sizeof(PackKey)) == 0; }
 
@@ -237,15 +254,15 @@ int find_job(const PackPlan& p, const PackKey& k, int hint) {
     return -1;
 }
 
-PackPlan* plan_of(int id) { return (id >= 1 && id <= (int)g_plans.size()) ? g_plans[id - 1] : nullptr; }
-
 }  // namespace
 
 size_t pack_lds_bytes(const PackDesc& d) { return d.kind == PD_TILED ? (size_t)16 * d.nb * d.T * sizeof(float) : 0; }
 
+long long pack_src_elems(const PackDesc& d) { return (long long)d.K * d.Nn * (d.kind == PD_CONVT ? 8 : d.T); }      // (ConvT: w is (Cin, Cout, 8))
+
 int pack_blocks(const PackDesc& d) {
     if (d.kind == PD_TILED) return (d.Nn / d.nb) * (d.K / 16);
-    long long total = d.kind == PD_LOWP ? (long long)d.K * d.Nn * d.T : (long long)d.aux * d.TW / 8;      // (ConvT: K * Ncols / 8 slots)
+    long long total = d.kind == PD_LOWP ? pack_src_elems(d) : (long long)d.aux * d.TW / 8;      // (ConvT: K * Ncols / 8 slots)
     long long g = (total + 255) / 256;
     return (int)(g > 2048 ? 2048 : (g < 1 ? 1 : g));
 }
@@ -265,20 +282,30 @@ PackKey make_pack_key(const void* w, int kind, int a, int b, int c, int d, int e
 }
 
 bool prepack_find(const PackKey& key, void** wq, const float** w_amax) {
-    if (!g_act) return false;
-    const int i = find_job(*g_act, key, g_cursor);
+    Lock lk(g_mu);
+    StepState& s = g_step;
+    if (!s.act) return false;
+    const int i = find_job(*s.act, key, s.cursor);
     if (i < 0) return false;
-    const PackJob& j = g_act->jobs[i];
-    g_cursor = i + 1;
-    *wq = g_arena + j.off;
-    if (w_amax && j.d.amax_elems > 0) *w_amax = reinterpret_cast<const float*>(g_arena + g_act->amax_off) + j.d.amax_idx;
+    const PackJob& j = s.act->jobs[i];
+    s.cursor = i + 1;
+    *wq = s.arena + j.off;
+    if (w_amax && j.d.amax_elems > 0) *w_amax = reinterpret_cast<const float*>(s.arena + s.act->amax_off) + j.d.amax_idx;
     return true;
 }
 
-void prepack_note(const PackKey& key, size_t bytes, const PackDesc& d) {
-    if (!g_rec || g_rec->sealed || d.oscale) return;
-    if (find_job(*g_rec, key, (int)g_rec->jobs.size()) >= 0) return;        // a module applied twice in a step packs once
-    g_rec->jobs.push_back(PackJob{key, bytes, 0, d});
+void* pack_and_note(const PackKey& key, size_t bytes, const PackDesc& d, hipStream_t st) {
+    pack_launch(d, st);
+    Lock lk(g_mu);
+    PackPlan* rec = g_step.rec;
+    if (rec && !d.oscale && find_job(*rec, key, (int)rec->jobs.size()) < 0) rec->jobs.push_back(PackJob{key, bytes, 0, d});      // (a module applied twice in a step packs once)
+    return d.dst;
+}
+
+void* prepack_use(const PackKey& key, size_t bytes, const PackDesc& d, hipStream_t st, const float** w_amax) {
+    void* hit = nullptr;
+    if (!d.oscale && prepack_find(key, &hit, w_amax)) return hit;
+    return pack_and_note(key, bytes, d, st);
 }
 
 }  // namespace seg
@@ -288,18 +315,28 @@ using namespace seg;
 extern "C" {
 
 int mi355seg_prepack_record_begin(void) {
-    SEG_CHECK_ARG(!g_rec, "mi355seg_prepack_record_begin: a recording is already open");
-    SEG_CHECK_ARG(!g_act, "mi355seg_prepack_record_begin: a plan is active");
-    g_rec = new PackPlan();
+    Lock lk(g_mu);
+    if (bracket_open("mi355seg_prepack_record_begin")) return MI355SEG_EINVAL;
+    g_step.rec = new PackPlan();
     return MI355SEG_OK;
 }
 
-// closes the recording: *plan = its id (0 when nothing was recorded), *arena_bytes = the bytes mi355seg_prepack_run needs
-int mi355seg_prepack_record_end(int* plan, size_t* arena_bytes) {
-    SEG_CHECK_ARG(g_rec && plan && arena_bytes, "mi355seg_prepack_record_end: no open recording / null outputs");
-    PackPlan* p = g_rec;
-    g_rec = nullptr;
+// closes the recording: *plan = its id (0 when nothing was kept), *arena_bytes = the bytes mi355seg_prepack_run needs.  Kept is what was packed out of the
+// caller's parameter storage (the ranges [base, base + bytes)): any other weight pointer -- a contiguous copy, a computed tensor -- is a temporary no later step may read.
+int mi355seg_prepack_record_end(int* plan, size_t* arena_bytes, const void* const* param_base_host, const size_t* param_bytes_host, int nparams) {
+    Lock lk(g_mu);
+    SEG_CHECK_ARG(g_step.rec && plan && arena_bytes, "mi355seg_prepack_record_end: no open recording / null outputs");
+    SEG_CHECK_ARG(nparams >= 0 && (nparams == 0 || (param_base_host && param_bytes_host)), "mi355seg_prepack_record_end: null parameter ranges");
+    PackPlan* p = g_step.rec;
+    g_step.rec = nullptr;
     *plan = 0; *arena_bytes = 0;
+    auto outside = [&](const PackJob& j) {
+        const uintptr_t w = (uintptr_t)j.d.w, end = w + (uintptr_t)pack_src_elems(j.d) * sizeof(float);
+        for (int i = 0; i < nparams; ++i)
+            if (w >= (uintptr_t)param_base_host[i] && end <= (uintptr_t)param_base_host[i] + param_bytes_host[i]) return false;
+        return true;
+    };
+    p->jobs.erase(std::remove_if(p->jobs.begin(), p->jobs.end(), outside), p->jobs.end());
     if (p->jobs.empty()) { delete p; return MI355SEG_OK; }
     size_t off = 0;
     int first = 0, afirst = 0;
@@ -326,22 +363,22 @@ int mi355seg_prepack_record_end(int* plan, size_t* arena_bytes) {
     p->amax_off = off; off += align_up((size_t)(p->namax ? p->namax : 1) * sizeof(float), 256);
     p->tab_off = off; off += align_up(p->jobs.size() * sizeof(PackDesc), 256);
     p->arena_bytes = off;
-    p->sealed = true;
-    g_plans.push_back(p);
-    *plan = (int)g_plans.size();
+    g_step.plans.push_back(p);
+    *plan = (int)g_step.plans.size();
     *arena_bytes = p->arena_bytes;
     return MI355SEG_OK;
 }
 
-int mi355seg_prepack_jobs(int plan) { PackPlan* p = plan_of(plan); return p ? (int)p->jobs.size() : 0; }
+int mi355seg_prepack_jobs(int plan) { Lock lk(g_mu); PackPlan* p = g_step.plan_of(plan); return p ? (int)p->jobs.size() : 0; }
 
 // forms every packing of `plan` in the caller's arena on `stream` (three launches) and makes the plan the one convolutions look their
 // weights up in, until mi355seg_prepack_done.  The job table is written into the arena at the first call with that arena (a blocking
 // copy): inside a stream capture an arena that has not been used eagerly yet leaves the plan inactive (the convolutions pack in place).
 int mi355seg_prepack_run(int plan, void* arena, size_t arena_bytes, void* stream) {
-    PackPlan* p = plan_of(plan);
+    Lock lk(g_mu);
+    PackPlan* p = g_step.plan_of(plan);
     SEG_CHECK_ARG(p && arena, "mi355seg_prepack_run: unknown plan / null arena");
-    SEG_CHECK_ARG(!g_act && !g_rec, "mi355seg_prepack_run: another plan is active or being recorded");
+    if (bracket_open("mi355seg_prepack_run")) return MI355SEG_EINVAL;
     SEG_CHECK_ARG(((uintptr_t)arena % 256) == 0, "mi355seg_prepack_run: the arena must be 256-byte aligned");
     SEG_CHECK_WS(p->arena_bytes, arena_bytes);
     hipStream_t st = (hipStream_t)stream;
@@ -370,25 +407,27 @@ int mi355seg_prepack_run(int plan, void* arena, size_t arena_bytes, void* stream
     SEG_SET_LDS(pack_all_kernel, 64 * 1024);
     hipLaunchKernelGGL(pack_all_kernel, dim3(p->nblocks), dim3(256), p->lds, st, tab, n);
     SEG_CHECK_LAUNCH();
-    g_act = p; g_arena = base; g_cursor = 0;
+    g_step.act = p; g_step.act_id = plan; g_step.arena = base; g_step.cursor = 0;
     return MI355SEG_OK;
 }
 
-// end of the step: the plan is no longer consulted
+// end of the step: the plan is no longer consulted (nothing active: a no-op)
 int mi355seg_prepack_done(void* stream) {
     (void)stream;
-    g_act = nullptr; g_arena = nullptr;
+    Lock lk(g_mu);
+    g_step.act = nullptr; g_step.act_id = 0; g_step.arena = nullptr;
     return MI355SEG_OK;
 }
 
-int mi355seg_prepack_active(void) { return g_act ? 1 : 0; }
+int mi355seg_prepack_active(void) { Lock lk(g_mu); return g_step.act ? 1 : 0; }
 
 int mi355seg_prepack_free(int plan) {
-    PackPlan* p = plan_of(plan);
+    Lock lk(g_mu);
+    PackPlan* p = g_step.plan_of(plan);
     if (!p) return MI355SEG_OK;
-    SEG_CHECK_ARG(p != g_act, "mi355seg_prepack_free: the plan is active");
+    SEG_CHECK_ARG(p != g_step.act, "mi355seg_prepack_free: the plan is active");
     delete p;
-    g_plans[plan - 1] = nullptr;
+    g_step.plans[plan - 1] = nullptr;
     return MI355SEG_OK;
 }
 

@@ -8,8 +8,10 @@ Activations inside the package are channel-last: a 5-D fp32 tensor of logical sh
 [N, D, H, W, C] whose last stride is 1 and whose voxel pitch (stride of W) may exceed C
 (a channel slice of a wider concat buffer).
 """
+import ctypes
 import os
 import threading
+import weakref
 
 import numpy as np
 import torch
@@ -135,7 +137,13 @@ def workspace(nbytes, device):
 
 # ----------------------------------------------------------------------------- a step's weight packings in one launch (csrc/prepack.hip)
 _PREPACK_OFF = bool(os.environ.get("MI355SEG_NO_PREPACK"))
-_PREPACK_ACTIVE = [False]       # a recorded plan is being replayed for the running step (prepacked_weights)
+_PREPACK_PLANS = weakref.WeakKeyDictionary()       # model -> {signature: {"plan": library plan id, "arena": uint8 tensor}}
+
+
+def prepack_plans(model):
+    """The prepack plans recorded for ``model``, or an empty dict.  Kept beside the models, not in them: a deep copy or an unpickled
+    model starts without plans and records its own, and nothing of the arenas is serialised with a model."""
+    return _PREPACK_PLANS.get(model, {})
 
 
 def conv_math_signature():
@@ -156,29 +164,33 @@ def _prepack_free(plans):
 class prepacked_weights:
     """Context manager around ONE training iteration of ``model`` (forward AND backward inside it; engine.train_step).  The first
     iteration at a signature (``key`` = whatever fixes the kernels' plans: dtype, conv math, input shape; plus the parameters' storage
-    addresses) runs as always while the library records every weight packing its convolutions launch; each later one starts with
+    addresses) runs as always while the library records every weight packing its convolutions launch (kept: those of the model's own
+    parameter storage); each later one starts with
     ALL of those packings formed by one launch into an arena this object owns (include/mi355seg.h, mi355seg_prepack_run) and its
     convolutions read them there -- 44 small launches off the cfg-2 step's stream, ~50 off UNETR's.  Bit-identical results.
-    MI355SEG_NO_PREPACK=1 turns it off."""
+    One bracket per process at a time (the library refuses a second one).  MI355SEG_NO_PREPACK=1 turns it off."""
+
+    # A recorded plan is being replayed for the running step: set and cleared here only.  Process-wide like the library's bracket, not
+    # threading.local like _AUTOCAST / _COUNTERS: a step's backward runs on autograd's device thread, not on the one that entered.
+    active = False
 
     def __init__(self, model, key):
         self.model, self.key, self.mode = model, key, None
 
     @property
     def replaying(self):
-        return self.mode == "run" and _PREPACK_ACTIVE[0]
+        return self.mode == "run" and prepacked_weights.active
 
     def __enter__(self):
         if _PREPACK_OFF:
             return self
-        params = [p for p in self.model.parameters()]
-        if not params or not params[0].is_cuda:
+        self.params = [p for p in self.model.parameters()]
+        if not self.params or not self.params[0].is_cuda:
             return self
-        sig = (self.key, tuple(p.data_ptr() for p in params))
-        plans = self.model.__dict__.get("_seg_prepack")
+        sig = (self.key, tuple(p.data_ptr() for p in self.params))
+        plans = _PREPACK_PLANS.get(self.model)
         if plans is None:
-            import weakref
-            plans = self.model.__dict__["_seg_prepack"] = {}
+            plans = _PREPACK_PLANS[self.model] = {}
             weakref.finalize(self.model, _prepack_free, plans)
         rec = plans.get(sig)
         L = lib()
@@ -193,26 +205,27 @@ class prepacked_weights:
         elif rec["plan"]:
             L.call("mi355seg_prepack_run", rec["plan"], _p(rec["arena"]), rec["arena"].numel(), _stream())
             self.mode = "run"
-            _PREPACK_ACTIVE[0] = L.query("mi355seg_prepack_active") != 0
+            prepacked_weights.active = L.query("mi355seg_prepack_active") != 0
         return self
 
     def __exit__(self, *exc):
         L = lib()
-        if self.mode == "record":
-            import ctypes
+        mode, self.mode = self.mode, None
+        if mode == "record":
+            n = len(self.params)                             # the plan keeps what was packed out of these ranges (a copy _w32 made is gone by the next step)
+            base = (ctypes.c_void_p * n)(*[p.data_ptr() for p in self.params])
+            size = (ctypes.c_size_t * n)(*[p.numel() * p.element_size() for p in self.params])
             plan, nbytes = ctypes.c_int(0), ctypes.c_size_t(0)
-            L.call("mi355seg_prepack_record_end", ctypes.byref(plan), ctypes.byref(nbytes))
+            L.call("mi355seg_prepack_record_end", ctypes.byref(plan), ctypes.byref(nbytes), base, size, n)
             if exc[0] is not None:
                 if plan.value:
                     L.call("mi355seg_prepack_free", plan.value)
             else:
-                dev = next(self.model.parameters()).device
-                arena = torch.empty(max(int(nbytes.value), 256), dtype=torch.uint8, device=dev) if plan.value else None
+                arena = torch.empty(max(int(nbytes.value), 256), dtype=torch.uint8, device=self.params[0].device) if plan.value else None
                 self.plans[self.sig] = {"plan": plan.value, "arena": arena}
-        elif self.mode == "run":
-            _PREPACK_ACTIVE[0] = False
+        elif mode == "run":                                  # (also when the body raised: the next step must find no open bracket)
+            prepacked_weights.active = False
             L.call("mi355seg_prepack_done", _stream())
-        self.mode = None
         return False
 
 
@@ -520,7 +533,7 @@ def clear_weight_amax():
 
 
 def _weight_amax(w):
-    if _PREPACK_ACTIVE[0]:       # the step's packings (and max |w| with them) were formed up front: the library hands the kernels its own scalars
+    if prepacked_weights.active:       # the step's packings (and max |w| with them) were formed up front: the library hands the kernels its own scalars
         return None              # (a weight tensor the plan does not hold is measured by the entry point: NULL = measure)
     rec = _WEIGHT_AMAX.get(w.data_ptr())
     if rec is not None and rec[1] == w.numel() and rec[0].device == w.device:

@@ -15,7 +15,9 @@
  *   - weights keep the PyTorch logical layouts: Conv3d (Cout,Cin,kD,kH,kW),
  *     ConvTranspose3d (Cin,Cout,kD,kH,kW), contiguous;
  *   - `stream` is a hipStream_t passed as void*; all work is stream-ordered, nothing
- *     synchronises, allocates or frees; scratch comes from the caller (`ws`);
+ *     synchronises, allocates or frees; scratch comes from the caller (`ws`), so the
+ *     entry points may be called from several threads at once -- except the seven
+ *     mi355seg_prepack_* ones, which share one per-process bracket (see there);
  *   - return value: 0 on success, a negative MI355SEG_E* code otherwise;
  *     mi355seg_last_error() returns a static message for the calling thread.
  */
@@ -856,11 +858,17 @@ int mi355seg_cast_bf16_to_f32(const mi355seg_bf16* src, int ldsrc, float* dst, i
  *   each later step: prepack_run(plan, arena, bytes, stream) at its top -- one memset, one launch measuring max |w| where a packing scales
  *   by it (f16x3) and ONE launch that forms every recorded packing in the caller's arena, all on `stream`; until prepack_done an entry
  *   point that finds its (weight pointer, layout) in the plan reads the arena copy and launches no packing of its own.
- * Anything not found packs as before; results are bit-identical either way.  The caller guarantees that the recorded weight
- * pointers are alive and that the weights do not change between prepack_run and their last use in the step.  (The first prepack_run
- * with an arena writes the job table into it with a blocking copy; called first inside a stream capture it leaves the plan inactive.) */
+ * Anything not found packs as before; results are bit-identical either way.  A plan keeps only the packings of weights that lie inside
+ * the caller's parameter storage: record_end takes it as nparams host arrays of base pointers and byte counts (the model's parameters)
+ * and drops every recorded weight pointer outside them (a contiguous copy, a weight computed in the forward: freed by the next step).
+ * The caller guarantees that those parameters stay alive while the plan exists and that the weights do not change between
+ * prepack_run and their last use in the step.  (The first prepack_run
+ * with an arena writes the job table into it with a blocking copy; called first inside a stream capture it leaves the plan inactive.)
+ * These seven entry points share ONE bracket per process -- a recording (record_begin .. record_end) or a replay (prepack_run ..
+ * prepack_done), whichever threads run the step inside it -- and serialise on one lock.  A record_begin or prepack_run while a bracket
+ * is open fails with MI355SEG_EINVAL, names the open bracket in mi355seg_last_error() and leaves it intact. */
 int mi355seg_prepack_record_begin(void);
-int mi355seg_prepack_record_end(int* plan, size_t* arena_bytes);
+int mi355seg_prepack_record_end(int* plan, size_t* arena_bytes, const void* const* param_base_host, const size_t* param_bytes_host, int nparams);
 int mi355seg_prepack_jobs(int plan);
 int mi355seg_prepack_run(int plan, void* arena, size_t arena_bytes, void* stream);
 int mi355seg_prepack_done(void* stream);
