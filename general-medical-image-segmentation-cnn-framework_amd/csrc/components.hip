@@ -1,0 +1,503 @@
+// components.hip -- connected components of a predicted mask on the device: the clean-up between the aggregated mask (predict.py:139-147)
+// and the metrics (predict.py:151/154).  Semantics of scipy.ndimage.label with generate_binary_structure(3, 1 / 2 / 3): foreground is
+// != 0, neighbours are the 6 faces, 18 faces + edges or 26 faces + edges + corners, outside the array is background.
+//
+// Block-based union-find over parent[], an int32 per voxel: -1 on background, on foreground the linear index of another voxel of the
+// same component.
+//   INVARIANT: parent[i] <= i at all times.  The local kernel stores the minimum index of the voxel's in-tile component; the merge
+//   kernel changes parent[] only with atomicMin(&parent[hi], lo) with lo < hi, which can only lower a value.
+//   A find therefore walks strictly decreasing indices and ends after at most i steps at a voxel with parent[r] == r; a union that
+//   loses its race continues from the value the atomic returned, which is strictly below the index it tried to link, and ends too.
+//   A root is <= every voxel below it, so the root of a finished component IS its first voxel in z,y,x raster order: the label
+//   root + 1 does not depend on scheduling, and two runs are bitwise equal.
+// No workgroup waits for another one anywhere in this file; the only ordering between workgroups is the kernel boundary.
+//   components_local    one workgroup per 8 x 8 x 64 tile: union-find of the tile in LDS, parent[] and the per-tile counts out
+//   components_merge    the voxels on tile faces join their roots across tiles (device-scope atomics only)
+//   components_flatten  labels[v] = root + 1; the per-tile counts move to sizes[root], one atomic per (tile, tile-local component)
+//   components_info     foreground voxels, components, largest component (reduction over sizes[])
+//   components_filter   out[v] = keep(labels[v]) ? mask[v] : 0, and the number of voxels set to 0
+#include "common.h"
+#include "internal.h"
+
+namespace seg {
+
+constexpr int kCcTZ = 8, kCcTY = 8, kCcTX = 64;         // the tile, z x y x x: 4096 voxels, 32 KiB of LDS
+constexpr int kCcThreads = 256;
+constexpr int kCcWaves = kCcThreads / kWave;
+constexpr int kCcRows = kCcTZ * kCcTY;                  // rows of kCcTX = 64 voxels: one wave owns a row at a time
+constexpr int kCcRowsPerWave = kCcRows / kCcWaves;
+constexpr int kCcTile = kCcRows * kCcTX;
+constexpr long long kCcMaxVoxels = (1ll << 31) - 2;     // root + 1 must fit an int32
+static_assert(kCcTX == kWave, "a wave owns one row of the tile");
+static_assert(kCcRows % kCcWaves == 0, "rows divide among the waves");
+
+static int cc_grid(long long items) {
+    long long b = (items + kCcThreads - 1) / kCcThreads;
+    return (int)(b < 1 ? 1 : (b > 4096 ? 4096 : b));
+}
+
+// ---- union-find on an int array in LDS (workgroup scope) or in global memory (agent scope).
+// Every access is an atomic of that scope.  In global memory this is what makes the merge kernel correct across XCDs: the per-XCD
+// L2s are not coherent inside a kernel, a device-scope atomicMin is performed where every XCD sees it, and a relaxed agent-scope load
+// does not stay in this CU's L1.  A load that still returns an OLDER value of parent[i] is harmless: every value parent[i] ever held
+// is a voxel of i's component that is <= i, so a find that ends early hands the union a member of the right set, and the atomicMin
+// that follows returns the true value and corrects the walk.
+template <int Scope>
+__device__ __forceinline__ int uf_find(const int* p, int i) {
+    // strictly decreasing (parent[i] <= i), so at most i steps
+    for (;;) {
+        const int q = __hip_atomic_load(p + i, __ATOMIC_RELAXED, Scope);
+        if (q == i) return i;
+        i = q;
+    }
+}
+
+template <int Scope>
+__device__ __forceinline__ void uf_union(int* p, int a, int b) {
+    // max(a, b) strictly decreases from one turn to the next: `old` < hi and lo < hi
+    for (;;) {
+        a = uf_find<Scope>(p, a);
+        b = uf_find<Scope>(p, b);
+        if (a == b) return;
+        const int hi = a > b ? a : b, lo = a > b ? b : a;
+        const int old = __hip_atomic_fetch_min(p + hi, lo, __ATOMIC_RELAXED, Scope);
+        if (old == hi) return;          // hi was a root and now hangs below lo
+        // hi was linked meanwhile (or the find read an old value): it now points at min(old, lo); what is left is old ~ lo
+        a = old;
+        b = lo;
+    }
+}
+
+// (dz, dy) of the four rows that hold backward neighbours: the row above in the slice, and three rows of the slice before
+__constant__ const int kCcRowDz[4] = {0, -1, -1, -1};
+__constant__ const int kCcRowDy[4] = {-1, -1, 0, 1};
+
+// how far a row reaches in x under connectivity c: -1 = not a neighbour row, 0 = dx = 0 only, 1 = dx in {-1, 0, 1}
+__device__ __forceinline__ int cc_row_reach(int k, int conn) {
+    const bool diag = k == 1 || k == 3;          // (dz, dy) both non-zero
+    if (conn == 6) return diag ? -1 : 0;
+    if (conn == 18) return diag ? 0 : 1;
+    return 1;
+}
+
+// One workgroup per tile.  lab[t] (t = tile-local raster index, the same order as the global raster index) = -1 on background and
+// outside the volume, else a tile-local index <= t of the same in-tile component.
+template <bool Vec2>
+__global__ __launch_bounds__(kCcThreads) void components_local_kernel(const int64_t* __restrict__ mask, int D, int H, int W, int conn,
+        int* __restrict__ parent, int* __restrict__ sizes) {
+    __shared__ int lab[kCcTile];
+    __shared__ int cnt[kCcTile];
+    const int z0 = blockIdx.z * kCcTZ, y0 = blockIdx.y * kCcTY, x0 = blockIdx.x * kCcTX;
+    const long long HW = (long long)H * W;
+    const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave;
+
+    // phase 0a: foreground flags.  Vec2: W is even and the mask 16-byte aligned, so voxel pairs (x even) are one 16-byte load
+    if (Vec2) {
+        for (int p = threadIdx.x; p < kCcTile / 2; p += kCcThreads) {
+            const int r = p / (kCcTX / 2), tx = (p - r * (kCcTX / 2)) * 2;
+            const int z = z0 + r / kCcTY, y = y0 + r % kCcTY, x = x0 + tx;
+            int f0 = -1, f1 = -1;
+            if (z < D && y < H && x < W) {      // x even and W even: x + 1 < W too
+                const longlong2 v = *reinterpret_cast<const longlong2*>(mask + (z * HW + (long long)y * W + x));
+                f0 = v.x != 0 ? 0 : -1;
+                f1 = v.y != 0 ? 0 : -1;
+            }
+            lab[r * kCcTX + tx] = f0;
+            lab[r * kCcTX + tx + 1] = f1;
+            cnt[r * kCcTX + tx] = 0;
+            cnt[r * kCcTX + tx + 1] = 0;
+        }
+    } else {
+        for (int t = threadIdx.x; t < kCcTile; t += kCcThreads) {
+            const int r = t / kCcTX, tx = t - r * kCcTX;
+            const int z = z0 + r / kCcTY, y = y0 + r % kCcTY, x = x0 + tx;
+            lab[t] = (z < D && y < H && x < W && mask[z * HW + (long long)y * W + x] != 0) ? 0 : -1;
+            cnt[t] = 0;
+        }
+    }
+    __syncthreads();
+    // phase 0b: runs along x.  A wave owns a row; every foreground voxel starts at the first voxel of its run, so the x direction
+    // needs no union
+    unsigned long long rowbits[kCcRowsPerWave];
+#pragma unroll
+    for (int j = 0; j < kCcRowsPerWave; ++j) {
+        const int r = wave + j * kCcWaves;
+        const bool fg = lab[r * kCcTX + lane] >= 0;
+        const unsigned long long bits = __ballot(fg);
+        rowbits[j] = bits;
+        const unsigned long long zeros_below = ~bits & ((1ull << lane) - 1ull);      // background voxels left of this lane
+        const int start = zeros_below ? 64 - __clzll((long long)zeros_below) : 0;
+        if (fg) lab[r * kCcTX + lane] = r * kCcTX + start;
+    }
+    __syncthreads();
+    // phase 1: unions with the neighbour rows inside the tile (LDS atomics).  Per neighbour row: if the voxel straight across (dx = 0)
+    // is foreground it stands for its whole run, diagonal voxels included; the union is skipped when the left voxel of this row and
+    // the left voxel across are both foreground, because that pair has joined the same two runs (induction along the run).
+    for (int t = threadIdx.x; t < kCcTile; t += kCcThreads) {
+        if (lab[t] < 0) continue;
+        const int r = t / kCcTX, tx = t - r * kCcTX, tz = r / kCcTY, ty = r - tz * kCcTY;
+        for (int k = 0; k < 4; ++k) {
+            const int reach = cc_row_reach(k, conn);
+            const int nz = tz + kCcRowDz[k], ny = ty + kCcRowDy[k];
+            if (reach < 0 || nz < 0 || ny < 0 || ny >= kCcTY) continue;
+            const int nb = (nz * kCcTY + ny) * kCcTX;
+            const bool left_in = tx > 0, right_in = tx < kCcTX - 1;
+            if (lab[nb + tx] >= 0) {
+                if (left_in && lab[t - 1] >= 0 && lab[nb + tx - 1] >= 0) continue;
+                uf_union<__HIP_MEMORY_SCOPE_WORKGROUP>(lab, t, nb + tx);
+            } else if (reach > 0) {
+                if (left_in && lab[nb + tx - 1] >= 0) uf_union<__HIP_MEMORY_SCOPE_WORKGROUP>(lab, t, nb + tx - 1);
+                if (right_in && lab[nb + tx + 1] >= 0) uf_union<__HIP_MEMORY_SCOPE_WORKGROUP>(lab, t, nb + tx + 1);
+            }
+        }
+    }
+    __syncthreads();
+    // phase 2: lab[] is read-only now.  The first voxel of each run finds the root and adds the run's length to the root's count:
+    // one LDS atomic per run, not per voxel
+    int root[kCcRowsPerWave];
+#pragma unroll
+    for (int j = 0; j < kCcRowsPerWave; ++j) {
+        const int r = wave + j * kCcWaves;
+        const unsigned long long bits = rowbits[j];
+        const bool fg = (bits >> lane) & 1ull;
+        const unsigned long long zeros_below = ~bits & ((1ull << lane) - 1ull);
+        const int start = zeros_below ? 64 - __clzll((long long)zeros_below) : 0;
+        int rt = -1;
+        if (fg && start == lane) {
+            rt = uf_find<__HIP_MEMORY_SCOPE_WORKGROUP>(lab, r * kCcTX + lane);
+            const unsigned long long inv = ~(bits >> lane);             // bit 0 is clear; the first set bit ends the run
+            const int len = inv ? __ffsll((long long)inv) - 1 : 64;
+            atomicAdd(&cnt[rt], len);
+        }
+        rt = __shfl(rt, start, kWave);
+        root[j] = fg ? rt : -1;
+    }
+    __syncthreads();
+    // phase 3: parent[] = global index of the tile-local root, sizes[] = the count at tile-local roots and 0 elsewhere (every voxel of
+    // the tile inside the volume is written, so neither array needs clearing)
+#pragma unroll
+    for (int j = 0; j < kCcRowsPerWave; ++j) {
+        const int r = wave + j * kCcWaves;
+        const int z = z0 + r / kCcTY, y = y0 + r % kCcTY, x = x0 + lane;
+        if (z >= D || y >= H || x >= W) continue;
+        const long long g = z * HW + (long long)y * W + x;
+        const int rt = root[j];
+        int pg = -1, c = 0;
+        if (rt >= 0) {
+            const int rr = rt / kCcTX, rx = rt - rr * kCcTX;
+            pg = (int)((z0 + rr / kCcTY) * HW + (long long)(y0 + rr % kCcTY) * W + (x0 + rx));
+            if (rt == r * kCcTX + lane) c = cnt[rt];
+        }
+        parent[g] = pg;
+        sizes[g] = c;
+    }
+}
+
+// One workgroup per tile.  A foreground voxel on a face of its tile joins its root with the root of every backward neighbour (13 of
+// 26, 9 of 18, 3 of 6 offsets: the ones before it in raster order) that lies in ANOTHER tile; pairs inside a tile were joined by the
+// local kernel.  Faces, edges and corners of tiles need no cases of their own.  parent[] is touched by device-scope atomics only.
+__global__ __launch_bounds__(kCcThreads) void components_merge_kernel(int* parent, int D, int H, int W, int conn) {
+    const int z0 = blockIdx.z * kCcTZ, y0 = blockIdx.y * kCcTY, x0 = blockIdx.x * kCcTX;
+    const long long HW = (long long)H * W;
+    for (int t = threadIdx.x; t < kCcTile; t += kCcThreads) {
+        const int r = t / kCcTX, tx = t - r * kCcTX, tz = r / kCcTY, ty = r - tz * kCcTY;
+        // only these voxels have a backward neighbour outside the tile (dz is never +1)
+        if (!(tz == 0 || ty == 0 || ty == kCcTY - 1 || tx == 0 || tx == kCcTX - 1)) continue;
+        const int z = z0 + tz, y = y0 + ty, x = x0 + tx;
+        if (z >= D || y >= H || x >= W) continue;
+        const int v = (int)(z * HW + (long long)y * W + x);
+        if (__hip_atomic_load(parent + v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < 0) continue;
+        const bool left_fg = tx > 0 && __hip_atomic_load(parent + v - 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) >= 0;
+        for (int k = 0; k < 13; ++k) {
+            // k = 0: (0, 0, -1); k = 1..3: (0, -1, dx); k = 4..12: (-1, dy, dx), dy and dx from -1 to 1
+            const int dz = k < 4 ? 0 : -1;
+            const int dy = k == 0 ? 0 : (k < 4 ? -1 : (k - 4) / 3 - 1);
+            const int dx = k == 0 ? -1 : (k < 4 ? k - 2 : (k - 4) % 3 - 1);
+            const int nonzero = (dz != 0) + (dy != 0) + (dx != 0);
+            if (nonzero > (conn == 6 ? 1 : conn == 18 ? 2 : 3)) continue;
+            const int nz = z + dz, ny = y + dy, nx = x + dx;
+            if (nz < 0 || ny < 0 || ny >= H || nx < 0 || nx >= W) continue;                 // outside the array: background
+            const bool same_tile = tz + dz >= 0 && ty + dy >= 0 && ty + dy < kCcTY && tx + dx >= 0 && tx + dx < kCcTX;
+            if (same_tile) continue;
+            const int n = (int)(nz * HW + (long long)ny * W + nx);
+            if (__hip_atomic_load(parent + n, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < 0) continue;
+            // Across a z or y border of the tile the pair one step to the left, (v - 1, n - 1), is a pair of this kernel too (v - 1 lies
+            // in this tile on the same face, the offset is the same).  Where both are foreground it joins the same two runs: v ~ v - 1
+            // inside the tile, n ~ n - 1 inside n's tile or by n's own x step in this kernel.  So only the first pair of a run of pairs
+            // does the union (induction on tx, which ends at 0); whether a voxel is foreground never changes, so the test cannot be stale.
+            const bool cross_zy = tz + dz < 0 || ty + dy < 0 || ty + dy >= kCcTY;
+            if (cross_zy && left_fg && nx > 0 && __hip_atomic_load(parent + n - 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) >= 0) continue;
+            uf_union<__HIP_MEMORY_SCOPE_AGENT>(parent, v, n);
+        }
+    }
+}
+
+// Streaming pass, four voxels per thread.  parent[] is read-only here (plain loads: a kernel boundary lies between the merge and
+// this), labels[] is a separate array.  sizes[]: a tile-local root that is not its component's root moves its count to the root's slot
+// with one atomic and clears its own.  Nobody adds to a slot that is not a root, and a root never touches its own slot, so the plain
+// accesses and the atomics never meet on one address; integer adds commute, so sizes[] is exact and reproducible.
+__global__ __launch_bounds__(kCcThreads) void components_flatten_kernel(const int* __restrict__ parent, long long numel,
+        int* __restrict__ labels, int* sizes) {
+    const long long quads = numel / 4;
+    for (long long q = (long long)blockIdx.x * blockDim.x + threadIdx.x; q < quads; q += (long long)gridDim.x * blockDim.x) {
+        const int4 p = *reinterpret_cast<const int4*>(parent + 4 * q);
+        const int4 c = *reinterpret_cast<const int4*>(sizes + 4 * q);
+        const int pv[4] = {p.x, p.y, p.z, p.w}, cv[4] = {c.x, c.y, c.z, c.w};
+        int lv[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const int v = (int)(4 * q + j);
+            int rt = pv[j];
+            if (rt >= 0 && rt != v) {
+                for (;;) {                                  // strictly decreasing (parent[i] <= i)
+                    const int up = parent[rt];
+                    if (up == rt) break;
+                    rt = up;
+                }
+                if (cv[j] > 0) {
+                    atomicAdd(&sizes[rt], cv[j]);
+                    sizes[v] = 0;
+                }
+            }
+            lv[j] = rt + 1;                                 // background: -1 + 1 = 0
+        }
+        *reinterpret_cast<int4*>(labels + 4 * q) = make_int4(lv[0], lv[1], lv[2], lv[3]);
+    }
+    if (blockIdx.x == 0 && threadIdx.x < (int)(numel - 4 * quads)) {
+        const int v = (int)(4 * quads + threadIdx.x);
+        int rt = parent[v];
+        if (rt >= 0 && rt != v) {
+            for (;;) {
+                const int up = parent[rt];
+                if (up == rt) break;
+                rt = up;
+            }
+            const int c = sizes[v];
+            if (c > 0) {
+                atomicAdd(&sizes[rt], c);
+                sizes[v] = 0;
+            }
+        }
+        labels[v] = rt + 1;
+    }
+}
+
+__device__ __forceinline__ unsigned long long cc_key(int size, long long slot) {
+    // larger size wins, then the smaller label (= slot + 1)
+    return size > 0 ? ((unsigned long long)(unsigned)size << 32) | (0xFFFFFFFFull - (unsigned long long)(slot + 1)) : 0ull;
+}
+
+// part[block][3] = foreground voxels, components, max key over this block's share of sizes[]
+__global__ __launch_bounds__(kCcThreads) void components_info_kernel(const int* __restrict__ sizes, long long numel,
+        unsigned long long* __restrict__ part) {
+    unsigned long long fg = 0, ncomp = 0, key = 0;
+    const long long quads = numel / 4;
+    for (long long q = (long long)blockIdx.x * blockDim.x + threadIdx.x; q < quads; q += (long long)gridDim.x * blockDim.x) {
+        const int4 c = *reinterpret_cast<const int4*>(sizes + 4 * q);
+        const int cv[4] = {c.x, c.y, c.z, c.w};
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            fg += (unsigned)cv[j];
+            ncomp += cv[j] > 0;
+            const unsigned long long k = cc_key(cv[j], 4 * q + j);
+            key = k > key ? k : key;
+        }
+    }
+    if (blockIdx.x == 0 && threadIdx.x < (int)(numel - 4 * quads)) {
+        const long long v = 4 * quads + threadIdx.x;
+        const int c = sizes[v];
+        fg += (unsigned)c;
+        ncomp += c > 0;
+        const unsigned long long k = cc_key(c, v);
+        key = k > key ? k : key;
+    }
+    for (int o = kWave / 2; o > 0; o >>= 1) {
+        fg += __shfl_xor(fg, o, kWave);
+        ncomp += __shfl_xor(ncomp, o, kWave);
+        const unsigned long long k = __shfl_xor(key, o, kWave);
+        key = k > key ? k : key;
+    }
+    __shared__ unsigned long long sh[kCcWaves][3];
+    if ((threadIdx.x & (kWave - 1)) == 0) {
+        sh[threadIdx.x / kWave][0] = fg; sh[threadIdx.x / kWave][1] = ncomp; sh[threadIdx.x / kWave][2] = key;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        for (int w = 1; w < kCcWaves; ++w) {
+            fg += sh[w][0]; ncomp += sh[w][1];
+            key = sh[w][2] > key ? sh[w][2] : key;
+        }
+        part[(long long)blockIdx.x * 3 + 0] = fg;
+        part[(long long)blockIdx.x * 3 + 1] = ncomp;
+        part[(long long)blockIdx.x * 3 + 2] = key;
+    }
+}
+
+__global__ __launch_bounds__(kCcThreads) void components_info_finalize_kernel(const unsigned long long* __restrict__ part, int nblk,
+        int64_t* __restrict__ info) {
+    unsigned long long fg = 0, ncomp = 0, key = 0;
+    for (int i = threadIdx.x; i < nblk; i += kCcThreads) {
+        fg += part[(long long)i * 3];
+        ncomp += part[(long long)i * 3 + 1];
+        const unsigned long long k = part[(long long)i * 3 + 2];
+        key = k > key ? k : key;
+    }
+    for (int o = kWave / 2; o > 0; o >>= 1) {
+        fg += __shfl_xor(fg, o, kWave);
+        ncomp += __shfl_xor(ncomp, o, kWave);
+        const unsigned long long k = __shfl_xor(key, o, kWave);
+        key = k > key ? k : key;
+    }
+    __shared__ unsigned long long sh[kCcWaves][3];
+    if ((threadIdx.x & (kWave - 1)) == 0) {
+        sh[threadIdx.x / kWave][0] = fg; sh[threadIdx.x / kWave][1] = ncomp; sh[threadIdx.x / kWave][2] = key;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        for (int w = 1; w < kCcWaves; ++w) {
+            fg += sh[w][0]; ncomp += sh[w][1];
+            key = sh[w][2] > key ? sh[w][2] : key;
+        }
+        info[0] = (int64_t)fg;
+        info[1] = (int64_t)ncomp;
+        info[2] = (int64_t)(key >> 32);
+        info[3] = key ? (int64_t)(0xFFFFFFFFull - (key & 0xFFFFFFFFull)) : 0;
+    }
+}
+
+// Streaming pass.  mask and out may be the same array (each thread reads its own voxels before it writes them), so neither is
+// __restrict__.  keep: n_keep < 0 = no list.  Vec2: both pointers 16-byte aligned, two voxels per load.
+__device__ __forceinline__ bool cc_keep(int label, const int* __restrict__ sizes, int min_voxels, const int* keep, int n_keep) {
+    if (label == 0) return true;                            // background stays background
+    if (sizes[label - 1] < min_voxels) return false;
+    if (n_keep < 0) return true;
+    bool in = false;
+    for (int j = 0; j < n_keep; ++j) in |= keep[j] == label;
+    return in;
+}
+
+template <bool Vec2>
+__global__ __launch_bounds__(kCcThreads) void components_filter_kernel(const int64_t* mask, const int* __restrict__ labels,
+        const int* __restrict__ sizes, long long numel, int min_voxels, const int* __restrict__ keep_labels, int n_keep,
+        int64_t* out, unsigned long long* __restrict__ removed) {
+    __shared__ int keep[16];
+    __shared__ long long sh[kCcWaves];
+    if (threadIdx.x < 16) keep[threadIdx.x] = (int)threadIdx.x < n_keep ? keep_labels[threadIdx.x] : -1;
+    __syncthreads();
+    long long gone = 0;
+    if (Vec2) {
+        const long long pairs = numel / 2;
+        for (long long q = (long long)blockIdx.x * blockDim.x + threadIdx.x; q < pairs; q += (long long)gridDim.x * blockDim.x) {
+            longlong2 m = *reinterpret_cast<const longlong2*>(mask + 2 * q);
+            const int2 l = *reinterpret_cast<const int2*>(labels + 2 * q);
+            if (!cc_keep(l.x, sizes, min_voxels, keep, n_keep)) { gone += m.x != 0; m.x = 0; }
+            if (!cc_keep(l.y, sizes, min_voxels, keep, n_keep)) { gone += m.y != 0; m.y = 0; }
+            *reinterpret_cast<longlong2*>(out + 2 * q) = m;
+        }
+        if ((numel & 1) && blockIdx.x == 0 && threadIdx.x == 0) {
+            int64_t m = mask[numel - 1];
+            if (!cc_keep(labels[numel - 1], sizes, min_voxels, keep, n_keep)) { gone += m != 0; m = 0; }
+            out[numel - 1] = m;
+        }
+    } else {
+        for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < numel; i += (long long)gridDim.x * blockDim.x) {
+            int64_t m = mask[i];
+            if (!cc_keep(labels[i], sizes, min_voxels, keep, n_keep)) { gone += m != 0; m = 0; }
+            out[i] = m;
+        }
+    }
+    gone = wave_sum(gone);
+    if ((threadIdx.x & (kWave - 1)) == 0) sh[threadIdx.x / kWave] = gone;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        for (int w = 1; w < kCcWaves; ++w) gone += sh[w];
+        if (gone) atomicAdd(removed, (unsigned long long)gone);         // one per workgroup; integer, so order-independent
+    }
+}
+
+static size_t cc_parent_bytes(long long numel) { return align_up((size_t)numel * sizeof(int), 256); }
+static size_t cc_part_bytes(long long numel) { return align_up((size_t)cc_grid((numel + 3) / 4) * 3 * sizeof(unsigned long long), 256); }
+static bool cc_extent_ok(int D, int H, int W) {
+    return D > 0 && H > 0 && W > 0 && (long long)D * H <= kCcMaxVoxels && (long long)D * H * W <= kCcMaxVoxels;
+}
+
+}  // namespace seg
+
+using namespace seg;
+
+extern "C" {
+
+int mi355seg_components_tile_extent(int axis) { return axis == 0 ? kCcTZ : axis == 1 ? kCcTY : axis == 2 ? kCcTX : 0; }
+
+size_t mi355seg_components_ws_bytes(int D, int H, int W) {
+    if (!cc_extent_ok(D, H, W)) return 0;
+    const long long numel = (long long)D * H * W;
+    return cc_parent_bytes(numel) + cc_part_bytes(numel);
+}
+
+int mi355seg_components_label_steps_i64(const int64_t* mask, int D, int H, int W, int connectivity, int32_t* labels, int32_t* sizes, int64_t* info,
+                                        void* ws, size_t ws_bytes, int steps, void* stream) {
+    SEG_CHECK_ARG(steps >= 1 && steps <= 5, "components_label_steps: steps must lie in 1..5, got %d", steps);
+    SEG_CHECK_ARG(D > 0 && H > 0 && W > 0, "components_label: extents must be positive, got %d x %d x %d", D, H, W);
+    SEG_CHECK_ARG(cc_extent_ok(D, H, W), "components_label: %lld voxels; labels are int32, at most 2^31 - 2 voxels", (long long)D * H * W);
+    SEG_CHECK_ARG(connectivity == 6 || connectivity == 18 || connectivity == 26, "components_label: connectivity must be 6, 18 or 26, got %d", connectivity);
+    SEG_CHECK_WS(mi355seg_components_ws_bytes(D, H, W), ws_bytes);
+    SEG_CHECK_ARG(mask && labels && sizes && info && ws, "components_label: null pointer");
+    SEG_CHECK_ARG(((uintptr_t)labels | (uintptr_t)sizes | (uintptr_t)ws) % 16 == 0 && (uintptr_t)mask % 8 == 0, "components_label: labels, sizes and the workspace must be 16-byte aligned");
+    const dim3 tiles(cdiv(W, kCcTX), cdiv(H, kCcTY), cdiv(D, kCcTZ));
+    SEG_CHECK_ARG(tiles.y <= 65535u && tiles.z <= 65535u, "components_label: more than 65535 tiles along an axis");
+    hipStream_t st = (hipStream_t)stream;
+    const long long numel = (long long)D * H * W;
+    ProfScope ps(PF_LOSS, 0.0, (8.0 + 8 + 12 + 4) * numel, st);      // local 8 + 8, flatten 12, info 4 bytes per voxel
+    Carver cv(ws);
+    int* parent = cv.take<int>((size_t)numel);
+    unsigned long long* part = cv.take<unsigned long long>((size_t)cc_grid((numel + 3) / 4) * 3);
+    if (W % 2 == 0 && (uintptr_t)mask % 16 == 0)
+        hipLaunchKernelGGL(components_local_kernel<true>, tiles, dim3(kCcThreads), 0, st, mask, D, H, W, connectivity, parent, sizes);
+    else
+        hipLaunchKernelGGL(components_local_kernel<false>, tiles, dim3(kCcThreads), 0, st, mask, D, H, W, connectivity, parent, sizes);
+    SEG_CHECK_LAUNCH();
+    if (steps < 2) return MI355SEG_OK;
+    hipLaunchKernelGGL(components_merge_kernel, tiles, dim3(kCcThreads), 0, st, parent, D, H, W, connectivity);
+    SEG_CHECK_LAUNCH();
+    if (steps < 3) return MI355SEG_OK;
+    const int nblk = cc_grid((numel + 3) / 4);
+    hipLaunchKernelGGL(components_flatten_kernel, dim3(nblk), dim3(kCcThreads), 0, st, (const int*)parent, numel, labels, sizes);
+    SEG_CHECK_LAUNCH();
+    if (steps < 4) return MI355SEG_OK;
+    hipLaunchKernelGGL(components_info_kernel, dim3(nblk), dim3(kCcThreads), 0, st, (const int*)sizes, numel, part);
+    SEG_CHECK_LAUNCH();
+    if (steps < 5) return MI355SEG_OK;
+    hipLaunchKernelGGL(components_info_finalize_kernel, dim3(1), dim3(kCcThreads), 0, st, (const unsigned long long*)part, nblk, info);
+    SEG_CHECK_LAUNCH();
+    return MI355SEG_OK;
+}
+
+int mi355seg_components_label_i64(const int64_t* mask, int D, int H, int W, int connectivity, int32_t* labels, int32_t* sizes, int64_t* info,
+                                  void* ws, size_t ws_bytes, void* stream) {
+    return mi355seg_components_label_steps_i64(mask, D, H, W, connectivity, labels, sizes, info, ws, ws_bytes, 5, stream);
+}
+
+int mi355seg_components_filter_i64(const int64_t* mask, const int32_t* labels, const int32_t* sizes, long long numel, long long min_voxels,
+                                   const int32_t* keep_labels, int n_keep, int64_t* out, int64_t* removed, void* stream) {
+    SEG_CHECK_ARG(numel > 0 && numel <= kCcMaxVoxels, "components_filter: %lld voxels; between 1 and 2^31 - 2", numel);
+    SEG_CHECK_ARG(n_keep >= 0 && n_keep <= 16, "components_filter: the keep list holds 0 to 16 labels, got %d", n_keep);
+    SEG_CHECK_ARG(min_voxels >= 0, "components_filter: min_voxels must not be negative, got %lld", min_voxels);
+    SEG_CHECK_ARG(mask && labels && sizes && out && removed, "components_filter: null pointer");
+    SEG_CHECK_ARG((uintptr_t)labels % 8 == 0, "components_filter: labels must be 8-byte aligned");
+    hipStream_t st = (hipStream_t)stream;
+    ProfScope ps(PF_LOSS, 0.0, (8.0 + 4 + 8) * numel, st);
+    if (hipMemsetAsync(removed, 0, sizeof(int64_t), st) != hipSuccess) { set_error("components_filter: hipMemsetAsync failed"); return MI355SEG_EHIP; }
+    const int mv = (int)(min_voxels > kCcMaxVoxels + 1 ? kCcMaxVoxels + 1 : min_voxels);    // no component is larger than numel
+    const int nk = keep_labels ? n_keep : -1;
+    if (((uintptr_t)mask | (uintptr_t)out) % 16 == 0)
+        hipLaunchKernelGGL(components_filter_kernel<true>, dim3(cc_grid((numel + 1) / 2)), dim3(kCcThreads), 0, st, mask, labels, sizes, numel, mv,
+                           keep_labels, nk, out, (unsigned long long*)removed);
+    else
+        hipLaunchKernelGGL(components_filter_kernel<false>, dim3(cc_grid(numel)), dim3(kCcThreads), 0, st, mask, labels, sizes, numel, mv,
+                           keep_labels, nk, out, (unsigned long long*)removed);
+    SEG_CHECK_LAUNCH();
+    return MI355SEG_OK;
+}
+
+}  // extern "C"

@@ -1699,6 +1699,95 @@ def hd95(gt, pred, spacing, percentile=95.0):
     return torch.maximum(_percentile(d_gt, float(percentile)), _percentile(d_pred, float(percentile)))
 
 
+CONNECTIVITIES = (6, 18, 26)
+MAX_KEEP_LARGEST = 16
+
+
+def components_tile():
+    """(tz, ty, tx): the tile the library cuts a volume into before it merges components across tiles (csrc/components.hip)."""
+    L = lib()
+    return tuple(int(L.query("mi355seg_components_tile_extent", a)) for a in range(3))
+
+
+def _connectivity(connectivity, what):
+    if isinstance(connectivity, bool) or not isinstance(connectivity, int) or connectivity not in CONNECTIVITIES:
+        raise Mi355SegError(f"{what}: connectivity must be 6, 18 or 26, got {connectivity!r}")
+    return connectivity
+
+
+def _component_counts(min_voxels, keep_largest, what):
+    for name, v in (("min_voxels", min_voxels), ("keep_largest", keep_largest)):
+        if isinstance(v, bool) or not isinstance(v, int) or v < 0:
+            raise Mi355SegError(f"{what}: {name} must be a non-negative integer, got {v!r}")
+    if keep_largest > MAX_KEEP_LARGEST:
+        raise Mi355SegError(f"{what}: keep_largest must lie in 0..{MAX_KEEP_LARGEST}, got {keep_largest!r}")
+    return min_voxels, keep_largest
+
+
+def connected_components(mask, connectivity=26):
+    """Connected components of an int64 label volume on the GPU (foreground != 0; scipy.ndimage.label with the 6-, 18- or
+    26-neighbourhood) -> (labels int32 [D, H, W], sizes int32 [D*H*W], info int64[4]).  labels: 0 on background, else 1 + the raster
+    index of the first voxel of the component; sizes[r]: voxels of the component labelled r + 1, 0 elsewhere; info = (foreground
+    voxels, components, size of the largest component, its label; equal sizes: the smaller label).  Nothing is copied to the host."""
+    connectivity = _connectivity(connectivity, "connected_components")
+    mask = _label_volume(mask, "connected_components")
+    D, H, W = mask.shape
+    L = lib()
+    need = L.query("mi355seg_components_ws_bytes", D, H, W)
+    if need == 0:
+        raise Mi355SegError(f"connected_components: a volume of {D * H * W} voxels is refused (labels are int32: at most 2^31 - 2)")
+    ws = workspace(need, mask.device)
+    labels = torch.empty((D, H, W), dtype=torch.int32, device=mask.device)
+    sizes = torch.empty(D * H * W, dtype=torch.int32, device=mask.device)
+    info = torch.empty(4, dtype=torch.int64, device=mask.device)
+    L.call("mi355seg_components_label_i64", _p(mask), D, H, W, connectivity, _p(labels), _p(sizes), _p(info), _p(ws), ws.numel(), _stream())
+    return labels, sizes, info
+
+
+def select_components(labels_of_roots, sizes_of_roots, min_voxels=0, keep_largest=0):
+    """Which components stay: the compact table of components (their labels and sizes, e.g. ``r = torch.nonzero(sizes)[:, 0]``,
+    ``r + 1`` and ``sizes[r]``) -> int32 labels to keep.  Components below ``min_voxels`` go; then, with ``keep_largest`` = K > 0,
+    the K largest of the rest stay (largest first; equal sizes: the smaller label first), all of them where fewer than K remain.
+    Plain tensor code on the table's device, CPU tensors included."""
+    min_voxels, keep_largest = _component_counts(min_voxels, keep_largest, "select_components")
+    lab, sz = labels_of_roots.reshape(-1).to(torch.int64), sizes_of_roots.reshape(-1).to(torch.int64)
+    if lab.numel() != sz.numel():
+        raise Mi355SegError(f"select_components: {lab.numel()} labels and {sz.numel()} sizes")
+    big = sz >= min_voxels
+    lab, sz = lab[big], sz[big]
+    if keep_largest > 0:
+        key = (sz << 32) | (0xFFFFFFFF - lab)              # larger size first, then the smaller label
+        lab = lab[torch.sort(key, descending=True).indices[:keep_largest]]
+    return lab.to(torch.int32)
+
+
+def filter_components(mask, min_voxels=0, keep_largest=0, connectivity=26, inplace=False):
+    """Connected-component clean-up of an int64 label volume on the GPU -> (mask_out int64 of mask's shape, stats).  Components
+    below ``min_voxels`` voxels are set to 0; with ``keep_largest`` = K in 1..16 only the K largest of the rest survive (equal sizes:
+    the one that starts first in raster order).  Label values of kept voxels are preserved.  stats = {components, kept,
+    voxels_removed, largest}: components found, components kept, voxels set to 0, size of the largest component found.  The four
+    integers of stats are the only values copied to the host.  With both thresholds 0 the mask itself is returned; ``inplace`` writes
+    the result into ``mask`` (contiguous) and returns it."""
+    min_voxels, keep_largest = _component_counts(min_voxels, keep_largest, "filter_components")
+    vol = _label_volume(mask, "filter_components")
+    labels, sizes, info = connected_components(vol, connectivity)
+    if min_voxels == 0 and keep_largest == 0:
+        comps, largest = info[1:3].tolist()
+        return mask, {"components": comps, "kept": comps, "voxels_removed": 0, "largest": largest}
+    roots = torch.nonzero(sizes)[:, 0]
+    keep = select_components(roots + 1, sizes[roots], min_voxels, keep_largest)
+    listed = keep_largest > 0
+    if inplace and vol.data_ptr() != mask.data_ptr():
+        raise Mi355SegError("filter_components: inplace needs a contiguous mask")
+    out = vol if inplace else torch.empty_like(vol)
+    removed = torch.empty(1, dtype=torch.int64, device=vol.device)
+    keep_dev = keep.contiguous() if keep.numel() else torch.zeros(1, dtype=torch.int32, device=vol.device)
+    lib().call("mi355seg_components_filter_i64", _p(vol), _p(labels), _p(sizes), vol.numel(), min_voxels,
+               _p(keep_dev) if listed else None, keep.numel() if listed else 0, _p(out), _p(removed), _stream())
+    comps, kept, gone, largest = torch.stack([info[1], torch.full_like(info[1], keep.numel()), removed[0], info[2]]).tolist()
+    return out.reshape(mask.shape), {"components": comps, "kept": kept, "voxels_removed": gone, "largest": largest}
+
+
 class _BCEArgmaxDice(Function):
     """train.py:204,209,221 in ONE pass over the logits: BCE-with-logits mean loss (differentiable w.r.t. the logits),
     pred.argmax(1, keepdim) and the four integer Dice counters of metric(gt.argmax, mask)."""

@@ -11,6 +11,11 @@ NIfTI output (SimpleITK) is out of scope; volumes are ``.npy`` and metrics go to
 ``config.spacing=sz,sy,sx`` (optional; one voxel spacing for every volume of the run) switches the metrics to the five numbers the
 reference computes with ``metric(gt_t, pred_t, spacing)`` (predict.py:154): metrics.csv then holds ``file, precision, recall,
 jaccard, dice, hs95`` and a last ``mean`` row (predict.py:186-200).  Without the key the file is ``file, jaccard, dice``, no mean row.
+
+``config.keep_largest=K`` and / or ``config.min_component_voxels=N`` (optional) clean the aggregated mask by connected components on
+the device (csrc/components.hip) before it is saved and graded: components below N voxels go, then only the K largest stay;
+``config.connectivity`` = 6 | 18 | 26 (default 26).  components.csv (``file, components, kept, voxels_removed, largest``) is then
+written beside metrics.csv.  Without the two keys nothing of this runs and no file is added.
 """
 import csv
 import glob
@@ -142,6 +147,38 @@ def parse_spacing(config):
     return tuple(vals)
 
 
+COMPONENT_COLUMNS = ("components", "kept", "voxels_removed", "largest")
+
+
+def parse_postprocess(config):
+    """``config.keep_largest`` / ``config.min_component_voxels`` / ``config.connectivity`` -> (keep_largest, min_voxels, connectivity),
+    or None when neither of the first two keys is set (absent, empty or 0): no clean-up, and connectivity is not looked at."""
+    def count(key, top=None):
+        v = getattr(config, key, None)
+        if v is None or str(v) in ("", "None", "none", "null"):
+            return 0
+        if isinstance(v, bool) or not (isinstance(v, int) or (isinstance(v, str) and v.strip().isdigit())) or int(v) < 0 or (top is not None and int(v) > top):
+            raise ValueError(f"config.{key} must be an integer in 0..{top}, got {v!r}" if top is not None else
+                             f"config.{key} must be a non-negative integer, got {v!r}")
+        return int(v)
+    keep, small = count("keep_largest", F.MAX_KEEP_LARGEST), count("min_component_voxels")
+    if not keep and not small:
+        return None
+    c = getattr(config, "connectivity", None)
+    if c is None or str(c) in ("", "None", "none", "null"):
+        c = 26
+    if isinstance(c, bool) or not (isinstance(c, int) or (isinstance(c, str) and c.strip().isdigit())) or int(c) not in F.CONNECTIVITIES:
+        raise ValueError(f"config.connectivity must be 6, 18 or 26, got {c!r}")
+    return keep, small, int(c)
+
+
+def write_components_csv(path, rows):
+    with open(path, "w", newline="") as fh:
+        wr = csv.DictWriter(fh, fieldnames=["file"] + list(COMPONENT_COLUMNS))
+        wr.writeheader()
+        wr.writerows(rows)
+
+
 def write_metrics_csv(path, rows):
     """rows of {file, jaccard, dice}: those three columns, as they are.  Rows that also hold precision / recall / hs95 (a run with
     config.spacing): the reference's five columns in its order and a last row of their means (predict.py:186-200)."""
@@ -176,11 +213,16 @@ def predict(config, model, log=print):
             x = torch.from_numpy(np.load(f).astype(np.float32))
             y = torch.from_numpy(np.load(os.path.join(config.pred_gt_path, os.path.basename(f))).astype(np.float32))
             cases.append((os.path.splitext(os.path.basename(f))[0], x[None] if x.dim() == 3 else x, y[None] if y.dim() == 3 else y))
-    rows = []
+    rows, comp_rows = [], []
     spacing = parse_spacing(config)
+    post = parse_postprocess(config)
     for name, x, gt in cases:
         vol = znorm(x.to(device))
         mask = sliding_window_predict(model, vol, ps, overlap, batch_size=max(1, int(config.batch_size)), dtype=mixed_precision_dtype(config))
+        if post:
+            mask, stats = F.filter_components(mask, min_voxels=post[1], keep_largest=post[0], connectivity=post[2], inplace=True)
+            comp_rows.append({"file": name, **stats})
+            log(f"{name}: " + " ".join(f"{k} {stats[k]}" for k in COMPONENT_COLUMNS))
         gt_lab = gt.to(device).to(torch.int64).reshape(mask.shape)
         np.save(os.path.join(config.hydra_path, f"{name}_pred.npy"), mask.cpu().numpy().astype(np.uint8))
         if spacing:
@@ -193,6 +235,8 @@ def predict(config, model, log=print):
         rows.append({"file": name, "jaccard": jac, "dice": dice})
         log(f"{name}: dice {dice:.4f} jaccard {jac:.4f}")
     write_metrics_csv(os.path.join(config.hydra_path, "metrics.csv"), rows)
+    if post:
+        write_components_csv(os.path.join(config.hydra_path, "components.csv"), comp_rows)
     return rows
 
 

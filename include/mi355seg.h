@@ -523,6 +523,37 @@ int mi355seg_surface_distances_f64(const uint8_t* edges, int D, int H, int W, in
                                    const double* dt2, long long n_gt, long long n_pred, double* dist, long long row_stride,
                                    int64_t* cursor, void* stream);
 
+/* Connected components of a label volume: the clean-up of the mask between predict.py:139-147 and predict.py:151/154 (drop small
+ * islands, keep the K largest structures); semantics of scipy.ndimage.label with generate_binary_structure(3, 1 / 2 / 3).
+ * Foreground is != 0 whatever the label value, two foreground voxels are joined when they are neighbours under `connectivity`
+ * 6 (faces), 18 (+ edges) or 26 (+ corners), outside the array is background.  csrc/components.hip, DESIGN.md section 4.14.
+ *
+ * labels: int32 [D][H][W], 0 on background, on foreground 1 + the z,y,x raster index of the FIRST voxel of the voxel's component:
+ * independent of scheduling, so two runs are bitwise equal.  D*H*W <= 2^31 - 2, larger volumes are refused.
+ * sizes: int32 [D*H*W]; sizes[r] = voxels of the component whose label is r + 1, 0 in every other slot.
+ * info: int64[4] = foreground voxels, components, size of the largest component, its label (equal sizes: the smaller label;
+ * 0, 0 for an empty mask).  labels and sizes 16-byte aligned.  ws: mi355seg_components_ws_bytes(D, H, W) (0 for bad extents).
+ * mi355seg_components_tile_extent(axis): the extent along z (0), y (1), x (2) of the tiles the volume is cut into, each labelled by
+ * one workgroup before the tiles are merged (0 for any other axis); for tests that place structures across tile borders. */
+int mi355seg_components_tile_extent(int axis);
+size_t mi355seg_components_ws_bytes(int D, int H, int W);
+int mi355seg_components_label_i64(const int64_t* mask, int D, int H, int W, int connectivity,
+                                  int32_t* labels, int32_t* sizes, int64_t* info,
+                                  void* ws, size_t ws_bytes, void* stream);
+/* The same call cut short after its first `steps` of five launches (local, merge, flatten, info, info-finalise): the outputs are
+ * complete only with steps = 5.  For tools/bench_components.py, which times each launch as the difference of two prefixes. */
+int mi355seg_components_label_steps_i64(const int64_t* mask, int D, int H, int W, int connectivity,
+                                        int32_t* labels, int32_t* sizes, int64_t* info,
+                                        void* ws, size_t ws_bytes, int steps, void* stream);
+
+/* out[v] = keep(labels[v]) ? mask[v] : 0 with labels / sizes of mi355seg_components_label_i64: a component is kept when
+ * sizes[label - 1] >= min_voxels and, where a keep list is given, its label is one of keep_labels[0..n_keep) (int32 on the device,
+ * 0 <= n_keep <= 16; keep_labels == NULL: no list; a list of 0 labels keeps nothing).  Mask values are preserved.  out may be
+ * mask itself.  removed: int64[1] = the number of voxels set to 0.  labels 8-byte aligned. */
+int mi355seg_components_filter_i64(const int64_t* mask, const int32_t* labels, const int32_t* sizes, long long numel,
+                                   long long min_voxels, const int32_t* keep_labels, int n_keep,
+                                   int64_t* out, int64_t* removed, void* stream);
+
 /* The 2-channel target of the live loop (train.py:190-193): out[n][0] = (gt[n] == 0), out[n][1] = gt[n], float [N,2,S]. */
 int mi355seg_two_channel_gt_f32(const float* gt, float* out, long long N, long long S, void* stream);
 
