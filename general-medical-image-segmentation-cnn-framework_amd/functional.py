@@ -1571,6 +1571,70 @@ def argmax_channels(logits):
     return mask
 
 
+OVERLAP_MODES = ("crop", "average", "hann", "gaussian")     # sliding-window aggregation (predict.py); all but "crop" blend probabilities
+MAX_AGGREGATE_CLASSES = 16
+
+
+def _axis_vectors(vectors, extents, device, what):
+    """three 1-D arrays (numpy / lists / tensors), one per axis, of the given lengths -> float32 tensors on ``device``"""
+    if len(vectors) != 3:
+        raise Mi355SegError(f"{what}: expected three per-axis arrays (z, y, x), got {len(vectors)}")
+    out = []
+    for v, n in zip(vectors, extents):
+        v = torch.as_tensor(v)
+        if v.dim() != 1 or v.numel() != n:
+            raise Mi355SegError(f"{what}: expected per-axis arrays of {tuple(extents)} values, got one of shape {tuple(v.shape)}")
+        out.append(v.to(torch.float32).to(device).contiguous())       # rounded to fp32 where it lives, then uploaded (a no-op for a device tensor)
+    return out
+
+
+def _accumulator(acc, what):
+    _require_cuda(acc, what)
+    if acc.dim() != 4 or not acc.is_contiguous():
+        raise Mi355SegError(f"{what}: expected a contiguous accumulator [K, D, H, W], got shape {tuple(acc.shape)}")
+    if not 2 <= acc.shape[0] <= MAX_AGGREGATE_CLASSES:
+        raise Mi355SegError(f"{what}: K must lie in 2..{MAX_AGGREGATE_CLASSES}, got {acc.shape[0]}")
+    return acc
+
+
+def aggregate_patches(acc, logits, table, first, weights):
+    """One batch of torchio's GridAggregator.add_batch in a soft mode (predict.py:141), in place: for every patch ``b`` of ``logits``
+    [count, K, pd, ph, pw] (fp32, GPU), placed at the origin of row ``first + b`` of the int32 window ``table`` [P, 9] on the device,
+    ``acc[k, origin + v] += ((wz[z] * wy[y]) * wx[x]) * softmax(logits[b])[k, v]``.  acc: fp32 [K, D, H, W], zeroed by the caller
+    before the first batch; weights: the three per-axis windows (``predict.window_weights``).  Per element the additions happen in
+    ascending patch index, so the result does not depend on how the patches are batched and is bitwise reproducible."""
+    acc = _accumulator(acc, "aggregate_patches")
+    _require_cuda(logits, "aggregate_patches logits")
+    if logits.dim() != 5 or logits.shape[0] == 0 or logits.shape[1] != acc.shape[0]:
+        raise Mi355SegError(f"aggregate_patches: expected logits [count, {acc.shape[0]}, pd, ph, pw], got shape {tuple(logits.shape)}")
+    if not table.is_cuda or table.dtype != torch.int32 or table.dim() != 2 or table.shape[1] != 9 or not table.is_contiguous():
+        raise Mi355SegError("aggregate_patches: expected the contiguous int32 window table [P, 9] on the GPU")
+    count, K, pd, ph, pw = logits.shape
+    _, D, H, W = acc.shape
+    if isinstance(first, bool) or not isinstance(first, int) or first < 0 or first + count > table.shape[0]:
+        raise Mi355SegError(f"aggregate_patches: patches {first!r} .. +{count} are not rows of a table of {table.shape[0]}")
+    if pd > D or ph > H or pw > W:
+        raise Mi355SegError(f"aggregate_patches: patch {(pd, ph, pw)} larger than the volume {(D, H, W)}")
+    wz, wy, wx = _axis_vectors(weights, (pd, ph, pw), acc.device, "aggregate_patches weights")
+    logits = logits.contiguous()
+    lib().call("mi355seg_aggregate_patches_f32", _p(logits), K, _p(table), first, count, pd, ph, pw, _p(wz), _p(wy), _p(wx),
+               _p(acc), D, H, W, _stream())
+    return acc
+
+
+def aggregate_finalize(acc, axis_sums, probabilities=False):
+    """GridAggregator.get_output_tensor of a soft mode, then the argmax (predict.py:146,139): acc fp32 [K, D, H, W] -> int64 labels
+    [1, D, H, W] (first maximum on ties), or (labels, prob) with prob fp32 [K, D, H, W] = acc / ((sz[z] * sy[y]) * sx[x]);
+    axis_sums: the three per-axis normalisers (``predict.axis_weight_sums``)."""
+    acc = _accumulator(acc, "aggregate_finalize")
+    K, D, H, W = acc.shape
+    sz, sy, sx = _axis_vectors(axis_sums, (D, H, W), acc.device, "aggregate_finalize axis_sums")
+    labels = torch.empty((1, D, H, W), dtype=torch.int64, device=acc.device)
+    prob = torch.empty_like(acc) if probabilities else None
+    lib().call("mi355seg_aggregate_finalize_f32", _p(acc), K, D, H, W, _p(sz), _p(sy), _p(sx), _p(labels), _p(prob), _stream())
+    return (labels, prob) if probabilities else labels
+
+
 def dice_counts(gt, pred):
     """Integer counters of utils/metric.py on two int64 device tensors -> int64[4]
     (sum gt, sum pred, nnz(gt & pred), nnz(gt | pred))."""

@@ -16,6 +16,13 @@ jaccard, dice, hs95`` and a last ``mean`` row (predict.py:186-200).  Without the
 the device (csrc/components.hip) before it is saved and graded: components below N voxels go, then only the K largest stay;
 ``config.connectivity`` = 6 | 18 | 26 (default 26).  components.csv (``file, components, kept, voxels_removed, largest``) is then
 written beside metrics.csv.  Without the two keys nothing of this runs and no file is added.
+
+``config.overlap_mode=crop|average|hann|gaussian`` (optional, default crop) chooses how overlapping patches are aggregated.  ``crop`` is
+the reference's mode: argmax labels, each voxel from one patch.  The other three blend the patches' class PROBABILITIES with a window
+weight on the device (csrc/aggregate.hip) and take the argmax afterwards -- torchio's GridAggregator modes 'average' and 'hann', and an
+nnU-Net-style Gaussian.  ``config.patch_overlap=oz,oy,ox`` (one number: all three axes; each even and smaller than the patch axis)
+replaces the reference's (4, 4, 36).  ``config.save_probabilities=true`` (needs a blending mode) writes ``{name}_prob.npy``, float32
+[K, D, H, W], beside ``{name}_pred.npy``.  Without the keys nothing changes and no file is added.
 """
 import csv
 import glob
@@ -86,14 +93,60 @@ def window_table(size, patch, overlap):
     return np.asarray(rows, dtype=np.int32)
 
 
+def window_weights(mode, patch):
+    """The separable patch window of a blending mode: three fp64 arrays (wz, wy, wx) of the patch extents; the weight of patch voxel
+    (z, y, x) is wz[z] * wy[y] * wx[x].
+    ``average``: ones (torchio GridAggregator overlap_mode='average').
+    ``hann``: 0.5 * (1 - cos(2 pi (k + 1) / (p + 1))), k = 0 .. p-1: torchio's ``torch.hann_window(p + 2, periodic=False)[1:-1]``
+    per axis (GridAggregator._get_hann_window, torchio 0.20.3; UNPINNED like the grid above, checked against torch.hann_window).
+    ``gaussian``: exp(-0.5 * ((k - (p - 1) / 2) / (p / 8))^2).  This one is THIS PROJECT'S OWN definition, not a restatement: an
+    importance map in the manner of nnU-Net's (sigma = patch / 8) written as a product of per-axis Gaussians, without nnU-Net's
+    rescaling and clamping of the 3-D map."""
+    if mode not in F.OVERLAP_MODES or mode == "crop":
+        raise ValueError(f"window_weights: mode must be one of {F.OVERLAP_MODES[1:]}, got {mode!r}")
+    out = []
+    for p in ((patch,) * 3 if isinstance(patch, int) else tuple(patch)):
+        k = np.arange(int(p), dtype=np.float64)
+        if mode == "average":
+            out.append(np.ones(int(p), dtype=np.float64))
+        elif mode == "hann":
+            out.append(0.5 * (1.0 - np.cos(2.0 * np.pi * (k + 1.0) / (p + 1.0))))
+        else:
+            out.append(np.exp(-0.5 * ((k - (p - 1) / 2.0) / (p / 8.0)) ** 2))
+    return tuple(out)
+
+
+def axis_weight_sums(size, patch, overlap, weights):
+    """The normaliser of a blending mode, per axis: three fp64 arrays (sz, sy, sx) of the volume extents, sz[z] = the sum of wz over
+    the z-origins whose patch covers z.  The grid is a product of per-axis origins and the window a product of per-axis weights, so
+    torchio's accumulated weight volume is sz[z] * sy[y] * sx[x] and need not be kept."""
+    locs = grid_locations(size, patch, overlap)
+    out = []
+    for axis, (s, p, w) in enumerate(zip(size, patch, weights)):
+        acc = np.zeros(int(s), dtype=np.float64)
+        for l in sorted({loc[axis] for loc in locs}):
+            acc[l:l + p] += np.asarray(w, dtype=np.float64)
+        out.append(acc)
+    return tuple(out)
+
+
 @torch.no_grad()
-def sliding_window_predict(model, volume, patch_size, overlap=(4, 4, 36), batch_size=1, dtype=None):
+def sliding_window_predict(model, volume, patch_size, overlap=(4, 4, 36), batch_size=1, dtype=None, overlap_mode="crop",
+                           return_probabilities=False):
     """volume: float tensor [C, D, H, W] on the GPU -> int64 label volume [1, D, H, W] (argmax over classes).
     ``dtype`` = torch.bfloat16 runs the forward under mi355seg.autocast (``config.mixed_precision=bf16``).
     Device-resident: the window table is uploaded once, each batch is one gather launch (mi355seg_gather_patches_f32), the
     eval-mode forward (BatchNorm folded into the convolutions), the channel argmax and one paste launch
-    (mi355seg_paste_labels_i64); no host loop over patches, no host copies."""
+    (mi355seg_paste_labels_i64); no host loop over patches, no host copies.
+    ``overlap_mode`` = average | hann | gaussian blends instead: per batch one launch adds the window-weighted softmax of the logits
+    into an fp32 accumulator [K, D, H, W] (mi355seg_aggregate_patches_f32, in place of the argmax and the paste), and one launch per
+    volume takes the argmax of the blend (mi355seg_aggregate_finalize_f32).  ``return_probabilities`` (blending modes only) returns
+    (labels, prob) with prob fp32 [K, D, H, W], the normalised blend."""
     from ._lib import lib
+    if overlap_mode not in F.OVERLAP_MODES:
+        raise ValueError(f"overlap_mode must be one of {F.OVERLAP_MODES}, got {overlap_mode!r}")
+    if return_probabilities and overlap_mode == "crop":
+        raise ValueError("return_probabilities needs a blending overlap_mode (average, hann or gaussian): 'crop' aggregates labels")
     C, D, H, W = volume.shape
     ps = (patch_size,) * 3 if isinstance(patch_size, int) else tuple(patch_size)
     table_h = window_table((D, H, W), ps, overlap)
@@ -101,7 +154,13 @@ def sliding_window_predict(model, volume, patch_size, overlap=(4, 4, 36), batch_
     dev = volume.device
     table = torch.from_numpy(table_h).to(dev)
     volume = volume.contiguous().to(torch.float32)
-    out = torch.zeros((1, D, H, W), dtype=torch.int64, device=dev)
+    soft, acc = overlap_mode != "crop", None
+    if soft:
+        w64 = window_weights(overlap_mode, ps)
+        weights = [torch.from_numpy(w.astype(np.float32)).to(dev) for w in w64]
+        sums = [torch.from_numpy(s.astype(np.float32)).to(dev) for s in axis_weight_sums((D, H, W), ps, overlap, w64)]
+    else:
+        out = torch.zeros((1, D, H, W), dtype=torch.int64, device=dev)
     L, st = lib(), torch.cuda.current_stream().cuda_stream
     was_training = model.training
     model.eval()
@@ -115,9 +174,16 @@ def sliding_window_predict(model, volume, patch_size, overlap=(4, 4, 36), batch_
                 logits, _ = model(x, *frequency_bands(x, impl=getattr(model, "band_split", "fft")))
             else:
                 logits = model(x)
+        if soft:
+            if acc is None:                                              # K is known once the first batch is through the model
+                acc = torch.zeros((logits.shape[1], D, H, W), dtype=torch.float32, device=dev)
+            F.aggregate_patches(acc, logits.to(torch.float32), table, i, weights)
+            continue
         labels = F.argmax_channels(logits)                               # predict.py:133,139
         L.call("mi355seg_paste_labels_i64", labels.data_ptr(), table.data_ptr(), i, nb, ps[0], ps[1], ps[2], out.data_ptr(), D, H, W, st)
     model.train(was_training)
+    if soft:
+        return F.aggregate_finalize(acc, sums, probabilities=return_probabilities)
     return out
 
 
@@ -172,6 +238,56 @@ def parse_postprocess(config):
     return keep, small, int(c)
 
 
+def _absent(v):
+    return v is None or str(v) in ("", "None", "none", "null")
+
+
+def parse_overlap_mode(config):
+    """``config.overlap_mode`` -> one of functional.OVERLAP_MODES; "crop" (the reference's mode) when the key is absent or empty."""
+    m = getattr(config, "overlap_mode", None)
+    if _absent(m):
+        return "crop"
+    if not isinstance(m, str) or m not in F.OVERLAP_MODES:
+        raise ValueError(f"config.overlap_mode must be one of {', '.join(F.OVERLAP_MODES)}, got {m!r}")
+    return m
+
+
+def parse_patch_overlap(config, patch):
+    """``config.patch_overlap`` = oz,oy,ox (one number: all three axes) -> (oz, oy, ox), each even, >= 0 and smaller than the patch
+    axis (grid_locations' rule); None when the key is absent or empty (the reference's (4, 4, 36) then stays)."""
+    ov = getattr(config, "patch_overlap", None)
+    if _absent(ov):
+        return None
+    parts = str(ov).strip("()[] ").split(",") if isinstance(ov, str) else (list(ov) if hasattr(ov, "__len__") else [ov])
+    bad = ValueError(f"config.patch_overlap must be one or three even integers oz,oy,ox, each >= 0 and smaller than the patch axis "
+                     f"{tuple(patch)}, got {ov!r}")
+    vals = []
+    for v in parts:
+        if isinstance(v, bool) or not (isinstance(v, int) or (isinstance(v, str) and v.strip().isdigit())):
+            raise bad
+        vals.append(int(v))
+    if len(vals) == 1:
+        vals = vals * 3
+    if len(vals) != 3 or any(o < 0 or o % 2 or o >= p for o, p in zip(vals, patch)):
+        raise bad
+    return tuple(vals)
+
+
+def parse_save_probabilities(config, overlap_mode):
+    """``config.save_probabilities`` -> bool (absent: False).  True needs a blending overlap mode: 'crop' has no probabilities."""
+    v = getattr(config, "save_probabilities", None)
+    if _absent(v):
+        return False
+    if isinstance(v, str) and v.strip().lower() in ("true", "false"):
+        v = v.strip().lower() == "true"
+    if not isinstance(v, bool):
+        raise ValueError(f"config.save_probabilities must be true or false, got {v!r}")
+    if v and overlap_mode == "crop":
+        raise ValueError("config.save_probabilities=true needs config.overlap_mode=average, hann or gaussian "
+                         "(the crop mode aggregates labels, not probabilities)")
+    return v
+
+
 def write_components_csv(path, rows):
     with open(path, "w", newline="") as fh:
         wr = csv.DictWriter(fh, fieldnames=["file"] + list(COMPONENT_COLUMNS))
@@ -202,6 +318,9 @@ def predict(config, model, log=print):
     ps = config.patch_size
     ps = (ps,) * 3 if isinstance(ps, int) else tuple(ps)
     overlap = tuple(min(o, p - 2) // 2 * 2 for o, p in zip((4, 4, 36), ps))   # predict.py:100 overlap, kept valid for small patches
+    overlap = parse_patch_overlap(config, ps) or overlap
+    mode = parse_overlap_mode(config)
+    save_prob = parse_save_probabilities(config, mode)
     os.makedirs(config.hydra_path, exist_ok=True)
     if str(config.pred_data_path) == "synthetic":
         g = torch.Generator().manual_seed(7)
@@ -218,7 +337,11 @@ def predict(config, model, log=print):
     post = parse_postprocess(config)
     for name, x, gt in cases:
         vol = znorm(x.to(device))
-        mask = sliding_window_predict(model, vol, ps, overlap, batch_size=max(1, int(config.batch_size)), dtype=mixed_precision_dtype(config))
+        mask = sliding_window_predict(model, vol, ps, overlap, batch_size=max(1, int(config.batch_size)), dtype=mixed_precision_dtype(config),
+                                      overlap_mode=mode, return_probabilities=save_prob)
+        if save_prob:
+            mask, prob = mask
+            np.save(os.path.join(config.hydra_path, f"{name}_prob.npy"), prob.cpu().numpy())
         if post:
             mask, stats = F.filter_components(mask, min_voxels=post[1], keep_largest=post[0], connectivity=post[2], inplace=True)
             comp_rows.append({"file": name, **stats})

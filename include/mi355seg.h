@@ -711,6 +711,27 @@ int mi355seg_gather_patches_f32(const float* vol, int C, int D, int H, int W, co
 int mi355seg_paste_labels_i64(const int64_t* labels, const int* table, int first, int count, int pd, int ph, int pw,
                               int64_t* out, int D, int H, int W, void* stream);
 
+/* Soft aggregation (predict.py:117,141,146: tio.inference.GridAggregator, add_batch, get_output_tensor; the reference keeps
+ * the aggregator's default, overlap_mode='crop'; these are its other modes): the class PROBABILITIES of the patches are blended with a
+ * window weight and the argmax is taken afterwards.
+ * aggregate_patches restates add_batch of overlap_mode='average' (window of ones) and 'hann' (torchio's separable Hann window) for
+ * any separable window wz[pd], wy[ph], wx[pw]: for every patch b = first .. first+count-1 of the table (origin columns only) and
+ * every patch voxel (z,y,x), p = softmax over the K channels of logits [count,K,pd,ph,pw] at that voxel (fp32, maximum
+ * subtracted) and acc[k, oz+z, oy+y, ox+x] = fmaf((wz[z] * wy[y]) * wx[x], p_k, acc[...]).  acc is fp32 [K,D,H,W], zeroed by the
+ * caller before the first batch.  Rows of one batch may overlap each other; per accumulator element the fmafs happen in ascending
+ * patch index (add_batch's order), so the result does not depend on the batch size and is bitwise reproducible.  One launch.
+ * 2 <= K <= 16. */
+int mi355seg_aggregate_patches_f32(const float* logits, int K, const int* table, int first, int count,
+                                   int pd, int ph, int pw, const float* wz, const float* wy, const float* wx,
+                                   float* acc, int D, int H, int W, void* stream);
+/* get_output_tensor of those modes, then predict.py:139's argmax on the blended volume: labels[z,y,x] = argmax_k acc[k] (int64
+ * [D,H,W]; first maximum wins, as mi355seg_argmax_ch_f32) and, where prob != NULL, prob[k] = acc[k] / ((sz[z] * sy[y]) * sx[x])
+ * (fp32 [K,D,H,W]).  sz[D], sy[H], sx[W]: per axis the sum of the window over the patch origins that cover the coordinate; the
+ * patch grid is a product of per-axis origins, so their product IS torchio's accumulated weight volume and none is kept.
+ * sz, sy, sx may be NULL when prob is.  One launch. */
+int mi355seg_aggregate_finalize_f32(const float* acc, int K, int D, int H, int W, const float* sz, const float* sy, const float* sx,
+                                    int64_t* labels, float* prob, void* stream);
+
 /* ------------------------------------------------------------------ Training augmentation of the patch queue (dataloader.py:69-86)
  * config.aug=True: Compose([RandomBiasField(), ZNormalization(), RandomNoise(), RandomFlip(axes=(0,)), OneOf({RandomAffine(): 0.8,
  * RandomElasticDeformation(): 0.2})]) as ONE resampling gather per batch over the cached raw volumes x [C,D,H,W] / labels [Cy,D,H,W].
