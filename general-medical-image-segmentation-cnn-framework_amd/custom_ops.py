@@ -20,7 +20,12 @@ from torch import Tensor
 from . import functional as F
 from ._lib import lib
 
-_p, _stream, _sfx = F._p, F._stream, F._sfx
+_p, _stream = F._p, F._stream
+
+
+def _or_empty(t, like, dtype):
+    """A gradient that does not exist, as an operator output: an operator returns tensors, so an empty one stands for None."""
+    return t if t is not None else torch.empty(0, dtype=dtype, device=like.device)
 
 
 # ------------------------------------------------------------------------------------------------ Conv3d
@@ -140,12 +145,7 @@ torch.library.register_autograd("mi355seg::conv_transpose3d_k2s2", _convt_backwa
 @torch.library.custom_op("mi355seg::max_pool3d_2x", mutates_args=())
 def max_pool3d_2x(x: Tensor) -> Tuple[Tensor, Tensor]:
     """(pooled, uint8 arg-max codes 0..7 of each 2x2x2 window)."""
-    xv, ldx = F.cl_view(x, "max_pool3d input")
-    N, D, H, W, C = xv.shape
-    y = torch.empty((N, D // 2, H // 2, W // 2, C), dtype=xv.dtype, device=xv.device)
-    idx = torch.empty((N, D // 2, H // 2, W // 2, C), dtype=torch.uint8, device=xv.device)
-    lib().call("mi355seg_maxpool2_fwd_" + _sfx(xv), _p(xv), ldx, _p(y), C, _p(idx), N, D, H, W, C, _stream())
-    return y, idx
+    return F._maxpool2_fwd(*F.cl_view(x, "max_pool3d input"))
 
 
 @max_pool3d_2x.register_fake
@@ -157,10 +157,7 @@ def _(x):
 @torch.library.custom_op("mi355seg::max_pool3d_2x_backward", mutates_args=())
 def max_pool3d_2x_backward(dy: Tensor, idx: Tensor, D: int, H: int, W: int) -> Tensor:
     dyv, lddy = F.cl_view(dy, "max_pool3d grad")
-    N, C = dyv.shape[0], dyv.shape[-1]
-    dx = torch.empty((N, D, H, W, C), dtype=dyv.dtype, device=dyv.device)
-    lib().call("mi355seg_maxpool2_bwd_" + _sfx(dyv), _p(dyv), lddy, _p(idx), _p(dx), C, N, D, H, W, C, _stream())
-    return dx
+    return F._maxpool2_bwd(dyv, lddy, idx, (dyv.shape[0], D, H, W, dyv.shape[-1]))
 
 
 @max_pool3d_2x_backward.register_fake
@@ -194,11 +191,7 @@ def _(x):
 
 @torch.library.custom_op("mi355seg::upsample_nearest_2x_backward", mutates_args=())
 def upsample_nearest_2x_backward(dy: Tensor) -> Tensor:
-    dyv, lddy = F.cl_view(dy, "upsample grad")
-    N, D2, H2, W2, C = dyv.shape
-    dx = torch.empty((N, D2 // 2, H2 // 2, W2 // 2, C), dtype=dyv.dtype, device=dyv.device)
-    lib().call("mi355seg_upsample2_bwd_" + _sfx(dyv), _p(dyv), lddy, _p(dx), C, N, D2 // 2, H2 // 2, W2 // 2, C, _stream())
-    return dx
+    return F._upsample2_bwd(*F.cl_view(dy, "upsample grad"))
 
 
 @upsample_nearest_2x_backward.register_fake
@@ -336,16 +329,11 @@ def norm_stats(x: Tensor, running_mean: Optional[Tensor], running_var: Optional[
     """(mean, 1 / sqrt(var + eps)) per channel (per sample and channel for instance norm); BatchNorm running statistics are
     updated in place exactly as nn.BatchNorm3d does in training mode (unet3d.py:84-96)."""
     xv, ldx = F.cl_view(x, "norm input")
-    N, D, H, W, C = xv.shape
-    groups = N if instance else 1
-    rows = D * H * W * (1 if instance else N)
+    C = xv.shape[-1]
+    rows, groups = F._norm_rows(xv.shape, instance)
     L = lib()
-    ws = F.workspace(L.query("mi355seg_norm_ws_bytes", rows, groups, C), xv.device)
-    mean = torch.empty(groups * C, dtype=torch.float32, device=xv.device)
-    rstd = torch.empty(groups * C, dtype=torch.float32, device=xv.device)
-    L.call("mi355seg_norm_stats_" + _sfx(xv), _p(xv), ldx, rows, groups, C, eps, _p(mean), _p(rstd), _p(running_mean), _p(running_var), momentum,
-           _p(ws), ws.numel(), _stream())
-    return mean, rstd
+    ws = F._norm_ws(L, rows, groups, C, xv.device)
+    return F._batch_stats(L, xv, ldx, rows, groups, C, eps, running_mean, running_var, momentum, ws)
 
 
 @norm_stats.register_fake
@@ -359,13 +347,10 @@ def norm_apply_act(x: Tensor, mean: Tensor, rstd: Tensor, gamma: Optional[Tensor
                    act: int, slope: float, instance: bool) -> Tensor:
     """act((x - mean) * rstd * gamma + beta [+ residual]) in one pass."""
     xv, ldx = F.cl_view(x, "norm input")
-    N, D, H, W, C = xv.shape
-    groups = N if instance else 1
-    rows = D * H * W * (1 if instance else N)
-    res, ldres = (None, 0) if residual is None else F.cl_view(residual, "norm residual")
-    y = torch.empty((N, D, H, W, C), dtype=xv.dtype, device=xv.device)
-    lib().call("mi355seg_norm_act_fwd_" + _sfx(xv), _p(xv), ldx, _p(mean), _p(rstd), _p(gamma), _p(beta), _p(res), ldres, _p(y), C, rows, groups, C,
-               act, slope, _stream())
+    C = xv.shape[-1]
+    rows, groups = F._norm_rows(xv.shape, instance)
+    y = torch.empty(xv.shape, dtype=xv.dtype, device=xv.device)
+    F._norm_act_fwd(lib(), xv, ldx, mean, rstd, gamma, beta, F._opt_view(residual, "norm residual"), _p(y), C, rows, groups, C, act, slope)
     return y
 
 
@@ -381,21 +366,13 @@ def norm_act_backward(dy: Tensor, x: Tensor, mean: Tensor, rstd: Tensor, gamma: 
     where the forward had no gamma / residual."""
     xv, ldx = F.cl_view(x, "norm input")
     dyv, lddy = F.cl_view(F._like(dy, xv), "norm grad")
-    N, D, H, W, C = xv.shape
-    groups = N if instance else 1
-    rows = D * H * W * (1 if instance else N)
-    res, ldres = (None, 0) if residual is None else F.cl_view(residual, "norm residual")
+    C = xv.shape[-1]
+    rows, groups = F._norm_rows(xv.shape, instance)
     L = lib()
-    dev = xv.device
-    ws = F.workspace(L.query("mi355seg_norm_ws_bytes", rows, groups, C), dev)
-    dx = torch.empty(xv.shape, dtype=xv.dtype, device=dev)
-    dgamma = torch.empty(C if gamma is not None else 0, dtype=torch.float32, device=dev)
-    dbeta = torch.empty(C if gamma is not None else 0, dtype=torch.float32, device=dev)
-    dres = torch.empty(xv.shape if res is not None else (0,), dtype=xv.dtype, device=dev)
-    L.call("mi355seg_norm_act_bwd_" + _sfx(xv), _p(dyv), lddy, _p(xv), ldx, _p(mean), _p(rstd), _p(gamma), _p(beta), _p(res), ldres,
-           _p(dx), C, _p(dgamma) if gamma is not None else None, _p(dbeta) if gamma is not None else None, _p(dres) if res is not None else None, C,
-           rows, groups, C, act, slope, _p(ws), ws.numel(), _stream())
-    return dx, dgamma, dbeta, dres
+    ws = F._norm_ws(L, rows, groups, C, xv.device)
+    dx, dgamma, dbeta, dres, _ = F._norm_act_bwd(L, dyv, lddy, xv, ldx, mean, rstd, gamma, beta, F._opt_view(residual, "norm residual"),
+                                                 rows, groups, C, act, slope, ws)
+    return dx, _or_empty(dgamma, xv, torch.float32), _or_empty(dbeta, xv, torch.float32), _or_empty(dres, xv, xv.dtype)
 
 
 @norm_act_backward.register_fake
@@ -443,14 +420,14 @@ def conv_bn_act(x: Tensor, weight: Tensor, bias: Optional[Tensor], gamma: Tensor
     Cout, rows = g.Cout, g.rows_out
     dev = xv.device
     L = lib()
-    ws = F.workspace(max(g.ws_bytes(L, xv.dtype), L.query("mi355seg_norm_ws_bytes", rows, 1, Cout)), dev)
+    ws = F.workspace(F._conv_norm_ws(L, g, xv.dtype, rows, Cout), dev)
     y = torch.empty(g.out_shape, dtype=xv.dtype, device=dev)
     sums = torch.empty(2 * Cout, dtype=torch.float64, device=dev)
     F._conv_fwd(L, g, xv, ldx, w, bias, y, Cout, ws, sums)
     new_rm, new_rv = running_mean.detach().clone(), running_var.detach().clone()
     mean, rstd = F._stats_from_sums(L, sums, rows, Cout, eps, new_rm, new_rv, momentum)
     a = torch.empty_like(y)
-    L.call("mi355seg_norm_act_fwd_" + _sfx(xv), _p(y), Cout, _p(mean), _p(rstd), _p(gamma), _p(beta), None, 0, _p(a), Cout, rows, 1, Cout, act, slope, _stream())
+    F._norm_act_fwd(L, y, Cout, mean, rstd, gamma, beta, F._NO_RES, _p(a), Cout, rows, 1, Cout, act, slope)
     return a, y, mean, rstd, new_rm, new_rv
 
 
@@ -472,19 +449,14 @@ def conv_bn_act_backward(da: Tensor, x: Tensor, weight: Tensor, y: Tensor, mean:
     Cout, rows = g.Cout, g.rows_out
     dev = xv.device
     L = lib()
-    ws = F.workspace(max(g.ws_bytes(L, xv.dtype), L.query("mi355seg_norm_ws_bytes", rows, 1, Cout)), dev)
-    dy = torch.empty_like(y)
-    dgamma = torch.empty(Cout, dtype=torch.float32, device=dev)
-    dbeta = torch.empty(Cout, dtype=torch.float32, device=dev)
-    db = torch.empty(Cout if with_bias else 0, dtype=torch.float32, device=dev)
-    L.call("mi355seg_norm_act_bwd_colsum_" + _sfx(xv), _p(dav), ldda, _p(y), Cout, _p(mean), _p(rstd), _p(gamma), _p(beta), None, 0,
-           _p(dy), Cout, _p(dgamma), _p(dbeta), None, 0, _p(db) if with_bias else None, rows, 1, Cout, act, slope, _p(ws), ws.numel(), _stream())
+    ws = F.workspace(F._conv_norm_ws(L, g, xv.dtype, rows, Cout), dev)
+    dy, dgamma, dbeta, _, db = F._norm_act_bwd(L, dav, ldda, y, Cout, mean, rstd, gamma, beta, F._NO_RES, rows, 1, Cout, act, slope, ws, with_bias)
     dx = torch.empty(xv.shape if need_dx else (0,), dtype=xv.dtype, device=dev)
     if need_dx:
         F._conv_dgrad(L, g, dy, Cout, w, dx, g.Cin, ws)
     dw = torch.empty_like(w)
     F._conv_wgrad(L, g, dy, Cout, xv, ldx, dw, None, ws)
-    return dx, dw, db, dgamma, dbeta
+    return dx, dw, _or_empty(db, xv, torch.float32), dgamma, dbeta
 
 
 @conv_bn_act_backward.register_fake
@@ -538,10 +510,8 @@ def _(x, act, slope):
 def activation_backward(dy: Tensor, x: Tensor, act: int, slope: float) -> Tensor:
     xv, ldx = F.cl_view(x, "activation input")
     dyv, lddy = F.cl_view(F._like(dy, xv), "activation grad")
-    N, D, H, W, C = xv.shape
-    dx = torch.empty(xv.shape, dtype=xv.dtype, device=xv.device)
-    lib().call("mi355seg_act_bwd_" + _sfx(xv), _p(dyv), lddy, _p(xv), ldx, None, 0, _p(dx), C, N * D * H * W, C, act, slope, _stream())
-    return dx
+    C = xv.shape[-1]
+    return F._act_bwd(dyv, lddy, xv, ldx, F._NO_RES, xv.numel() // C, C, act, slope)
 
 
 @activation_backward.register_fake

@@ -306,10 +306,6 @@ class _ConvGeom:
         return L.query("mi355seg_conv3d_ws_bytes_bf16" if dtype == torch.bfloat16 else "mi355seg_conv3d_ws_bytes", *self.args)
 
 
-def _conv_ws(L, x, *geom):
-    return _ConvGeom(*geom).ws_bytes(L, x.dtype)
-
-
 def _conv_geom(x, w, stride, pad, what):
     """(geometry, contiguous fp32 weight) of ``what`` = a convolution of x -- a channel-last [N, D, H, W, Cin] tensor, or that shape --
     with the weight w (Cout, Cin, k, k, k)."""
@@ -620,6 +616,117 @@ def _concat_base(t, Cout, lead_shape, dtype):
     return base if ok else None
 
 
+def _concat_out(lead_shape, left_pad, C, dtype, device):
+    """(buffer, result, pitch) of a node whose C-channel result is the RIGHT channel slice of a fresh buffer with left_pad free channels on
+    its left, which a later node fills (_concat_base recognises the slice): the skip concatenations without the copies.  left_pad = 0: no
+    buffer (None), a dense result."""
+    full = torch.empty(tuple(lead_shape) + (left_pad + C,), dtype=dtype, device=device)
+    return (full, full[..., left_pad:], left_pad + C) if left_pad else (None, full, C)
+
+
+# ----------------------------------------------------------------------------- norm / activation / pool launchers
+# As for the convolutions: the only places that name a mi355seg_norm_stats_*, rstd_from_var, norm_act_fwd*, norm_act_bwd_colsum*,
+# maxpool2_{fwd,bwd}*, upsample2_bwd_* or act_bwd_* entry point (norm_fold, bn_act_head / bn_act_pool, norm_act_bwd_apply_ax have one caller
+# each and stay with it).  The norm passes always take the widest entry (_ax / _colsum_ax): the library defines the narrower ones as exactly
+# that call with a NULL maximum and / or a NULL column sum.  An optional tensor travels as the pair (tensor, ld) that _opt_view returns.
+_NO_RES = (None, 0)
+_EVAL_BN_BACKWARD = "backward through eval-mode BatchNorm (running statistics) is not supported"
+
+
+def _opt_view(t, what):
+    """cl_view of an optional tensor: (t, ld), or (None, 0) for an absent one."""
+    return _NO_RES if t is None else cl_view(t, what)
+
+
+def _norm_rows(shape, instance):
+    """(rows, groups) a norm reduces over for a channel-last ``shape``: every voxel of the batch in one group (BatchNorm), or one group per sample."""
+    N, D, H, W, _ = shape
+    return (D * H * W, N) if instance else (N * D * H * W, 1)
+
+
+def _norm_ws(L, rows, groups, C, device):
+    """The workspace of a norm pass (statistics, backward) over rows x C in ``groups`` groups."""
+    return workspace(L.query("mi355seg_norm_ws_bytes", rows, groups, C), device)
+
+
+def _conv_norm_ws(L, g, dtype, rows, C):
+    """Bytes of the one workspace a convolution g and the norm passes over its rows x C output share."""
+    return max(g.ws_bytes(L, dtype), L.query("mi355seg_norm_ws_bytes", rows, 1, C))
+
+
+def _batch_stats(L, x, ldx, rows, groups, C, eps, rm, rv, momentum, ws):
+    """(mean, rstd) fp32 [groups * C] of x by a pass over it; rm / rv: running statistics to update in place as nn.BatchNorm3d does in
+    training mode (None: leave them alone)."""
+    mean = torch.empty(groups * C, dtype=torch.float32, device=x.device)
+    rstd = torch.empty(groups * C, dtype=torch.float32, device=x.device)
+    L.call("mi355seg_norm_stats_" + _sfx(x), _p(x), ldx, rows, groups, C, eps, _p(mean), _p(rstd), _p(rm), _p(rv), momentum,
+           _p(ws), ws.numel(), _stream())
+    return mean, rstd
+
+
+def _running_stats(L, rm, rv, eps, C):
+    """(mean, rstd) of eval-mode BatchNorm: the running mean itself and 1 / sqrt(running_var + eps)."""
+    rstd = torch.empty(C, dtype=torch.float32, device=rv.device)
+    L.call("mi355seg_rstd_from_var_f32", _p(rv), eps, _p(rstd), C, _stream())
+    return rm, rstd
+
+
+def _norm_act_fwd(L, x, ldx, mean, rstd, gamma, beta, res, y_ptr, ldy, rows, groups, C, act, slope, amax=None):
+    """act((x - mean) * rstd * gamma + beta [+ res]) written at the address y_ptr with pitch ldy; amax: a zeroed slot that receives max |y|."""
+    L.call("mi355seg_norm_act_fwd_ax_" + _sfx(x), _p(x), ldx, _p(mean), _p(rstd), _p(gamma), _p(beta), _p(res[0]), res[1],
+           y_ptr, ldy, rows, groups, C, act, slope, _p(amax), _stream())
+
+
+def _norm_act_bwd(L, dy, lddy, x, ldx, mean, rstd, gamma, beta, res, rows, groups, C, act, slope, ws, colsum=False, amax=None):
+    """(dx, dgamma, dbeta, dres, db) of _norm_act_fwd under batch / instance statistics, all allocated here: dgamma / dbeta are None without
+    affine parameters, dres without a residual, and db -- the column sums of dx, the bias gradient of the convolution in front of the
+    norm -- unless ``colsum``; amax: a zeroed slot that receives max |dx|."""
+    dev = x.device
+    dx = torch.empty(x.shape, dtype=x.dtype, device=dev)
+    dgamma = torch.empty(C, dtype=torch.float32, device=dev) if gamma is not None else None
+    dbeta = torch.empty(C, dtype=torch.float32, device=dev) if gamma is not None else None
+    dres = torch.empty(x.shape, dtype=x.dtype, device=dev) if res[0] is not None else None
+    db = torch.empty(C, dtype=torch.float32, device=dev) if colsum else None
+    L.call("mi355seg_norm_act_bwd_colsum_ax_" + _sfx(x), _p(dy), lddy, _p(x), ldx, _p(mean), _p(rstd), _p(gamma), _p(beta), _p(res[0]), res[1],
+           _p(dx), C, _p(dgamma), _p(dbeta), _p(dres), C, _p(db), _p(amax), rows, groups, C, act, slope, _p(ws), ws.numel(), _stream())
+    return dx, dgamma, dbeta, dres, db
+
+
+def _act_bwd(dy, lddy, x, ldx, res, rows, C, act, slope, add=None):
+    """dx = dy * act'(x [+ res]); add = (tensor, ld): the one-pass form that also sums a second gradient of x in (a NULL tensor adds nothing)."""
+    dx = torch.empty(x.shape, dtype=x.dtype, device=x.device)
+    extra = () if add is None else (_p(add[0]), add[1])
+    lib().call("mi355seg_act_bwd_" + ("add_" if extra else "") + _sfx(x), _p(dy), lddy, _p(x), ldx, _p(res[0]), res[1], *extra, _p(dx), C,
+               rows, C, act, slope, _stream())
+    return dx
+
+
+def _maxpool2_fwd(x, ldx):
+    """(pooled, uint8 argmax codes 0..7 of each 2x2x2 window) of MaxPool3d(2, 2)."""
+    N, D, H, W, C = x.shape
+    y = torch.empty((N, D // 2, H // 2, W // 2, C), dtype=x.dtype, device=x.device)
+    idx = torch.empty((N, D // 2, H // 2, W // 2, C), dtype=torch.uint8, device=x.device)
+    lib().call("mi355seg_maxpool2_fwd_" + _sfx(x), _p(x), ldx, _p(y), C, _p(idx), N, D, H, W, C, _stream())
+    return y, idx
+
+
+def _maxpool2_bwd(dy, lddy, idx, shape, add=None):
+    """dx of the pooled tensor's input of ``shape``; add = (tensor, ld): a second gradient of that input, summed in the same pass."""
+    N, D, H, W, C = shape
+    dx = torch.empty((N, D, H, W, C), dtype=dy.dtype, device=dy.device)
+    extra = () if add is None else (_p(add[0]), add[1])
+    lib().call("mi355seg_maxpool2_bwd_" + ("add_" if extra else "") + _sfx(dy), _p(dy), lddy, _p(idx), *extra, _p(dx), C, N, D, H, W, C, _stream())
+    return dx
+
+
+def _upsample2_bwd(dy, lddy):
+    """dx of nearest-neighbour upsampling by two: the sums of dy's 2x2x2 windows."""
+    N, D2, H2, W2, C = dy.shape
+    dx = torch.empty((N, D2 // 2, H2 // 2, W2 // 2, C), dtype=dy.dtype, device=dy.device)
+    lib().call("mi355seg_upsample2_bwd_" + _sfx(dy), _p(dy), lddy, _p(dx), C, N, D2 // 2, H2 // 2, W2 // 2, C, _stream())
+    return dx
+
+
 class _Conv3d(Function):
     @staticmethod
     def forward(ctx, x, w, b, stride, pad, res=None):
@@ -833,34 +940,18 @@ class _NormAct(Function):
         # left_pad > 0: the result is the RIGHT channel slice of a buffer with left_pad free channels on its left, which a later node
         # fills (conv_in_act(..., cat_right=)): the skip concatenation of residual_unet3d.py:174-209 without the copies
         x, ldx = cl_view(x, "norm input")
-        N, D, H, W, C = x.shape
-        groups = N if instance else 1
-        rows = D * H * W * (1 if instance else N)
+        C = x.shape[-1]
+        rows, groups = _norm_rows(x.shape, instance)
         L = lib()
-        dev = x.device
-        ws = workspace(L.query("mi355seg_norm_ws_bytes", rows, groups, C), dev)
-        if res is not None:
-            res, ldres = cl_view(res, "norm residual")
-        else:
-            ldres = 0
+        ws = _norm_ws(L, rows, groups, C, x.device)
+        res, ldres = _opt_view(res, "norm residual")
         if training or instance:
-            mean = torch.empty(groups * C, dtype=torch.float32, device=dev)
-            rstd = torch.empty(groups * C, dtype=torch.float32, device=dev)
             upd = training and (running_mean is not None) and not instance
-            L.call("mi355seg_norm_stats_" + _sfx(x), _p(x), ldx, rows, groups, C, eps, _p(mean), _p(rstd),
-                   _p(running_mean) if upd else None, _p(running_var) if upd else None, momentum,
-                   _p(ws), ws.numel(), _stream())
+            mean, rstd = _batch_stats(L, x, ldx, rows, groups, C, eps, running_mean if upd else None, running_var if upd else None, momentum, ws)
         else:
-            mean = running_mean
-            rstd = torch.empty(C, dtype=torch.float32, device=dev)
-            L.call("mi355seg_rstd_from_var_f32", _p(running_var), eps, _p(rstd), C, _stream())
-        if left_pad:
-            full = torch.empty((N, D, H, W, left_pad + C), dtype=x.dtype, device=dev)
-            y = full[..., left_pad:]
-        else:
-            y = torch.empty((N, D, H, W, C), dtype=x.dtype, device=dev)
-        L.call("mi355seg_norm_act_fwd_" + _sfx(x), _p(x), ldx, _p(mean), _p(rstd), _p(gamma), _p(beta), _p(res), ldres,
-               y.data_ptr(), left_pad + C, rows, groups, C, act, slope, _stream())
+            mean, rstd = _running_stats(L, running_mean, running_var, eps, C)
+        _, y, ldy = _concat_out(x.shape[:4], left_pad, C, x.dtype, x.device)
+        _norm_act_fwd(L, x, ldx, mean, rstd, gamma, beta, (res, ldres), y.data_ptr(), ldy, rows, groups, C, act, slope)
         ctx.save_for_backward(x, mean, rstd, gamma, beta, res)
         ctx.cfg = (ldx, ldres, rows, groups, C, act, slope, bool(training or instance))
         return y
@@ -870,17 +961,11 @@ class _NormAct(Function):
         x, mean, rstd, gamma, beta, res = ctx.saved_tensors
         ldx, ldres, rows, groups, C, act, slope, batch_stats = ctx.cfg
         if not batch_stats:
-            raise Mi355SegError("backward through eval-mode BatchNorm (running statistics) is not supported")
+            raise Mi355SegError(_EVAL_BN_BACKWARD)
         dy, lddy = cl_view(_like(dy, x), "norm grad")
         L = lib()
-        dev = x.device
-        ws = workspace(L.query("mi355seg_norm_ws_bytes", rows, groups, C), dev)
-        dx = torch.empty(x.shape, dtype=x.dtype, device=dev)
-        dgamma = torch.empty(C, dtype=torch.float32, device=dev) if gamma is not None else None
-        dbeta = torch.empty(C, dtype=torch.float32, device=dev) if gamma is not None else None
-        dres = torch.empty(x.shape, dtype=x.dtype, device=dev) if res is not None else None
-        L.call("mi355seg_norm_act_bwd_" + _sfx(x), _p(dy), lddy, _p(x), ldx, _p(mean), _p(rstd), _p(gamma), _p(beta), _p(res), ldres,
-               _p(dx), C, _p(dgamma), _p(dbeta), _p(dres), C, rows, groups, C, act, slope, _p(ws), ws.numel(), _stream())
+        ws = _norm_ws(L, rows, groups, C, x.device)
+        dx, dgamma, dbeta, dres, _ = _norm_act_bwd(L, dy, lddy, x, ldx, mean, rstd, gamma, beta, (res, ldres), rows, groups, C, act, slope, ws)
         return dx, dgamma, dbeta, dres, None, None, None, None, None, None, None, None, None
 
 
@@ -916,17 +1001,16 @@ class _ConvBnAct(Function):
         Cout, rows = g.Cout, g.rows_out
         dev = x.device
         L = lib()
-        ws = workspace(max(g.ws_bytes(L, x.dtype), L.query("mi355seg_norm_ws_bytes", rows, 1, Cout)), dev)
+        ws = workspace(_conv_norm_ws(L, g, x.dtype, rows, Cout), dev)
         if (not training) and inference and x.data_ptr() % 16 == 0 and \
                 L.query("mi355seg_conv3d_fused_supported_" + _sfx(x), *g, ldx, left_pad + Cout):
             # inference (model.eval() under no_grad, predict.py:79-81,133): eval-mode BatchNorm folded into the packed weights and
             # the bias slot, the activation in the convolution's epilogue -- one pass, nothing saved for a backward
             fold = torch.empty(2 * Cout, dtype=torch.float32, device=dev)
             L.call("mi355seg_bn_fold_f32", _p(gamma), _p(beta), _p(rmean), _p(rvar), _p(b), eps, Cout, fold.data_ptr(), fold.data_ptr() + 4 * Cout, _stream())
-            full = torch.empty(g.out_shape[:4] + (left_pad + Cout,), dtype=x.dtype, device=dev)
-            a = full[..., left_pad:] if left_pad else full
+            _, a, lda = _concat_out(g.out_shape[:4], left_pad, Cout, x.dtype, dev)
             L.call("mi355seg_conv3d_fwd_fused_" + _sfx(x), _p(x), ldx, _p(w), fold.data_ptr(), fold.data_ptr() + 4 * Cout, act, slope,
-                   a.data_ptr(), left_pad + Cout, *g, _p(ws), ws.numel(), _stream())
+                   a.data_ptr(), lda, *g, _p(ws), ws.numel(), _stream())
             return a
         y = torch.empty(g.out_shape, dtype=x.dtype, device=dev)
         ax = training and _takes_amax(x)          # f16x3: operand maxima ride along (this layer's input, weights, and its output for the next layer)
@@ -940,10 +1024,7 @@ class _ConvBnAct(Function):
             mean, rstd = _stats_from_sums(L, sums, rows, Cout, eps, rmean, rvar, momentum)
         else:
             _conv_fwd(L, g, x, ldx, w, b, y, Cout, ws)
-            mean = rmean
-            rstd = torch.empty(Cout, dtype=torch.float32, device=dev)
-            L.call("mi355seg_rstd_from_var_f32", _p(rvar), eps, _p(rstd), Cout, _stream())
-        lda = left_pad + Cout
+            mean, rstd = _running_stats(L, rmean, rvar, eps, Cout)
         ctx.cat = 0
         if cat_right is not None:
             full = None if left_pad else _concat_base(cat_right, Cout, g.out_shape[:4], x.dtype)
@@ -951,16 +1032,12 @@ class _ConvBnAct(Function):
                 raise Mi355SegError("conv_bn_act: `cat_right` is not the right channel slice of a matching concat buffer")
             a, lda = full[..., :Cout], full.shape[-1]
             ctx.cat = lda - Cout
-        elif left_pad:
-            # the activation lands in the RIGHT channel slice of a wider buffer whose left `left_pad` channels a later
-            # up-convolution fills (conv_transpose3d_k2s2_cat): the skip concatenation then costs no copy
-            full = torch.empty(g.out_shape[:4] + (left_pad + Cout,), dtype=x.dtype, device=dev)
-            a = full[..., left_pad:]
         else:
-            a = torch.empty_like(y)
+            # left_pad: the activation lands in the RIGHT channel slice of a wider buffer whose left `left_pad` channels a later
+            # up-convolution fills (conv_transpose3d_k2s2_cat): the skip concatenation then costs no copy
+            full, a, lda = _concat_out(g.out_shape[:4], left_pad, Cout, x.dtype, dev)
         aa = _amax_slot(dev) if ax else None
-        L.call("mi355seg_norm_act_fwd_ax_" + _sfx(x), _p(y), Cout, _p(mean), _p(rstd), _p(gamma), _p(beta), None, 0,
-               a.data_ptr(), lda, rows, 1, Cout, act, slope, _p(aa), _stream())
+        _norm_act_fwd(L, y, Cout, mean, rstd, gamma, beta, _NO_RES, a.data_ptr(), lda, rows, 1, Cout, act, slope, aa)
         if not ctx.cat:
             _set_amax(a, aa)
         ctx.save_for_backward(x, w, y, mean, rstd, gamma, beta)
@@ -978,7 +1055,7 @@ class _ConvBnAct(Function):
         g, ldx, has_b, act, slope, training = ctx.cfg
         Cin, Cout, rows = g.Cin, g.Cout, g.rows_out
         if not training:
-            raise Mi355SegError("backward through eval-mode BatchNorm (running statistics) is not supported")
+            raise Mi355SegError(_EVAL_BN_BACKWARD)
         if da is None:                       # (fork, only the pass-through was used)
             return (dpass,) + (None,) * 17
         if dpass is not None:
@@ -990,15 +1067,10 @@ class _ConvBnAct(Function):
         da, ldda = cl_view(_like(da, x), "conv+norm grad")
         L = lib()
         dev = x.device
-        ws = workspace(max(g.ws_bytes(L, x.dtype), L.query("mi355seg_norm_ws_bytes", rows, 1, Cout)), dev)
-        dy = torch.empty_like(y)
-        dgamma = torch.empty(Cout, dtype=torch.float32, device=dev) if gamma is not None else None      # no affine: instance norm
-        dbeta = torch.empty(Cout, dtype=torch.float32, device=dev) if gamma is not None else None
-        db = torch.empty(Cout, dtype=torch.float32, device=dev) if has_b else None
+        ws = workspace(_conv_norm_ws(L, g, x.dtype, rows, Cout), dev)
         xa, wa = ctx.amax or (None, None)
         dya = _amax_slot(dev) if ctx.amax is not None else None       # f16x3: max |dy| from the kernel that writes dy
-        L.call("mi355seg_norm_act_bwd_colsum_ax_" + _sfx(x), _p(da), ldda, _p(y), Cout, _p(mean), _p(rstd), _p(gamma), _p(beta), None, 0,
-               _p(dy), Cout, _p(dgamma), _p(dbeta), None, 0, _p(db), _p(dya), rows, 1, Cout, act, slope, _p(ws), ws.numel(), _stream())
+        dy, dgamma, dbeta, _, db = _norm_act_bwd(L, da, ldda, y, Cout, mean, rstd, gamma, beta, _NO_RES, rows, 1, Cout, act, slope, ws, has_b, dya)
         dx = dw = None
         if ctx.needs_input_grad[0]:
             dx = torch.empty(x.shape, dtype=x.dtype, device=dev)
@@ -1078,7 +1150,7 @@ class _DoubleConvBnAct(Function):
             convolution's input is the previous layer's RAW output, normalised + activated while its tiles are staged."""
             N, Do, Ho, Wo, Cout = g.out_shape
             rows = g.rows_out
-            ws = workspace(max(g.ws_bytes(L, inp.dtype), L.query("mi355seg_norm_ws_bytes", rows, 1, Cout)), dev)
+            ws = workspace(_conv_norm_ws(L, g, inp.dtype, rows, Cout), dev)
             y = torch.empty(g.out_shape, dtype=inp.dtype, device=dev)
             sums = torch.empty(2 * Cout, dtype=torch.float64, device=dev)
             aa = None
@@ -1116,18 +1188,16 @@ class _DoubleConvBnAct(Function):
                 L.call("mi355seg_bn_act_head_fwd_f32", _p(y), Cout, _p(mean), _p(rstd), _p(gm), _p(be), act, slope, _p(hw), _p(hb),
                        _p(lg), K, rows, Cout, K, _stream())
                 return y, mean, rstd, lg, cfg, (xa, wa, None)
-            full = torch.empty((N, Do, Ho, Wo, lp + Cout), dtype=inp.dtype, device=dev)
-            a = full[..., lp:] if lp else full
+            _, a, lda = _concat_out((N, Do, Ho, Wo), lp, Cout, inp.dtype, dev)
             if ax:
                 aa = _amax_slot(dev)
             if pool:                         # norm + activation + MaxPool3d(2, 2): the skip tensor, the pooled tensor and the argmax codes
                 pd = torch.empty((N, Do // 2, Ho // 2, Wo // 2, Cout), dtype=inp.dtype, device=dev)
                 idx = torch.empty((N, Do // 2, Ho // 2, Wo // 2, Cout), dtype=torch.uint8, device=dev)
-                L.call("mi355seg_bn_act_pool_fwd_f32", _p(y), Cout, _p(mean), _p(rstd), _p(gm), _p(be), act, slope, a.data_ptr(), lp + Cout,
+                L.call("mi355seg_bn_act_pool_fwd_f32", _p(y), Cout, _p(mean), _p(rstd), _p(gm), _p(be), act, slope, a.data_ptr(), lda,
                        _p(pd), _p(idx), _p(aa), N, Do, Ho, Wo, Cout, _stream())
                 return y, mean, rstd, (a, pd, idx), cfg, (xa, wa, aa)
-            L.call("mi355seg_norm_act_fwd_ax_f32", _p(y), Cout, _p(mean), _p(rstd), _p(gm), _p(be), None, 0,
-                   a.data_ptr(), lp + Cout, rows, 1, Cout, act, slope, _p(aa), _stream())
+            _norm_act_fwd(L, y, Cout, mean, rstd, gm, be, _NO_RES, a.data_ptr(), lda, rows, 1, Cout, act, slope, aa)
             return y, mean, rstd, a, cfg, (xa, wa, aa)
 
         head = None
@@ -1170,15 +1240,15 @@ class _DoubleConvBnAct(Function):
         dev = x.device
         if da2 is not None:
             da2, ldda2 = cl_view(_like(da2, x), "conv+norm grad")
-        ws = workspace(max(cg1.ws_bytes(L, x.dtype), cg2.ws_bytes(L, y1.dtype),
-                           L.query("mi355seg_norm_ws_bytes", rows1, 1, C1), L.query("mi355seg_norm_ws_bytes", rows2, 1, C2),
+        ws = workspace(max(_conv_norm_ws(L, cg1, x.dtype, rows1, C1), _conv_norm_ws(L, cg2, y1.dtype, rows2, C2),
                            L.query("mi355seg_bn_act_head_ws_bytes", C2, wh.shape[0]) if wh is not None else 0,
                            L.query("mi355seg_bn_act_pool_ws_bytes", C2) if idx is not None else 0), dev)
         f32 = dict(dtype=torch.float32, device=dev)
         # layer 2: BatchNorm + activation backward (its dx column sums are conv2's bias gradient)
-        dy2 = torch.empty_like(y2)
-        dg2, dbe2 = torch.empty(C2, **f32), torch.empty(C2, **f32)
-        db2 = torch.empty(C2, **f32) if has_b2 else None
+        if idx is not None or wh is not None:            # (the plain form's launcher allocates what it returns)
+            dy2 = torch.empty_like(y2)
+            dg2, dbe2 = torch.empty(C2, **f32), torch.empty(C2, **f32)
+            db2 = torch.empty(C2, **f32) if has_b2 else None
         (xa1, wa1, _), (xa2, wa2, _) = ctx.amax
         # f16x3: the two gradients d(conv output) take their maxima from the norm-backward kernels that write them
         dya2 = _amax_slot(dev) if (wa2 is not None or xa2 is not None) else None
@@ -1208,8 +1278,7 @@ class _DoubleConvBnAct(Function):
             L.call("mi355seg_bn_act_head_bwd_apply_f32", _p(da2), ldda2, _p(y2), C2, _p(mean2), _p(rstd2), _p(g2), _p(be2), act, slope, _p(wh),
                    sh.data_ptr(), sh.data_ptr() + 4 * C2, _p(dy2), C2, _p(db2), _p(dya2), rows2, C2, K, _p(ws), ws.numel(), _stream())
         else:
-            L.call("mi355seg_norm_act_bwd_colsum_ax_f32", _p(da2), ldda2, _p(y2), C2, _p(mean2), _p(rstd2), _p(g2), _p(be2), None, 0,
-                   _p(dy2), C2, _p(dg2), _p(dbe2), None, 0, _p(db2), _p(dya2), rows2, 1, C2, act, slope, _p(ws), ws.numel(), _stream())
+            dy2, dg2, dbe2, _, db2 = _norm_act_bwd(L, da2, ldda2, y2, C2, mean2, rstd2, g2, be2, _NO_RES, rows2, 1, C2, act, slope, ws, has_b2, dya2)
         # conv2 input gradient = d(act1); BN1's two column sums come out of the same kernel
         da1 = torch.empty((N, D2, H2, W2, C1), dtype=x.dtype, device=dev)
         s12 = torch.empty(2 * C1, **f32)
@@ -1303,10 +1372,7 @@ class _Act(Function):
     def forward(ctx, x, res, act, slope):
         x, ldx = cl_view(x, "activation input")
         N, D, H, W, C = x.shape
-        if res is not None:
-            res, ldres = cl_view(res, "activation residual")
-        else:
-            ldres = 0
+        res, ldres = _opt_view(res, "activation residual")
         y = torch.empty((N, D, H, W, C), dtype=x.dtype, device=x.device)
         rows = N * D * H * W
         lib().call("mi355seg_act_fwd_" + _sfx(x), _p(x), ldx, _p(res), ldres, _p(y), C, rows, C, act, slope, _stream())
@@ -1325,8 +1391,7 @@ class _Act(Function):
             return g, (g if ctx.has_res else None), None, None
         x, res = ctx.saved_tensors
         dy, lddy = cl_view(_like(dy, x), "activation grad")
-        dx = torch.empty(x.shape, dtype=x.dtype, device=x.device)
-        lib().call("mi355seg_act_bwd_" + _sfx(x), _p(dy), lddy, _p(x), ldx, _p(res), ldres, _p(dx), C, rows, C, act, slope, _stream())
+        dx = _act_bwd(dy, lddy, x, ldx, (res, ldres), rows, C, act, slope)
         return dx, (dx if res is not None else None), None, None
 
 
@@ -1344,12 +1409,10 @@ class _ActFork(Function):
     def forward(ctx, x, act, slope, left_pad=0):
         xv, ldx = cl_view(x, "activation input")
         N, D, H, W, C = xv.shape
-        if left_pad:                         # the activation is the RIGHT channel slice of a concat buffer a later node fills on the left
-            y = torch.empty((N, D, H, W, left_pad + C), dtype=xv.dtype, device=xv.device)[..., left_pad:]
-        else:
-            y = torch.empty((N, D, H, W, C), dtype=xv.dtype, device=xv.device)
+        # left_pad: the activation is the RIGHT channel slice of a concat buffer a later node fills on the left
+        _, y, ldy = _concat_out((N, D, H, W), left_pad, C, xv.dtype, xv.device)
         rows = N * D * H * W
-        lib().call("mi355seg_act_fwd_" + _sfx(xv), _p(xv), ldx, None, 0, y.data_ptr(), left_pad + C, rows, C, act, slope, _stream())
+        lib().call("mi355seg_act_fwd_" + _sfx(xv), _p(xv), ldx, None, 0, y.data_ptr(), ldy, rows, C, act, slope, _stream())
         ctx.cfg = (ldx, rows, C, act, slope)
         ctx.save_for_backward(xv)
         ctx.set_materialize_grads(False)
@@ -1362,12 +1425,8 @@ class _ActFork(Function):
         if dy is None:
             return dpass, None, None, None
         dy, lddy = cl_view(_like(dy, x), "activation grad")
-        add = ldadd = None
-        if dpass is not None:
-            add, ldadd = cl_view(_like(dpass, x), "pass-through grad")
-        dx = torch.empty(x.shape, dtype=x.dtype, device=x.device)
-        lib().call("mi355seg_act_bwd_add_" + _sfx(x), _p(dy), lddy, _p(x), ldx, None, 0, _p(add), ldadd or 0, _p(dx), C, rows, C, act, slope, _stream())
-        return dx, None, None, None
+        add = _opt_view(None if dpass is None else _like(dpass, x), "pass-through grad")
+        return _act_bwd(dy, lddy, x, ldx, _NO_RES, rows, C, act, slope, add), None, None, None
 
 
 def activation_fork(x, act, slope=0.01, left_pad=0):
@@ -1381,10 +1440,7 @@ class _PReLU(Function):
     def forward(ctx, x, res, slope):
         x, ldx = cl_view(x, "prelu input")
         N, D, H, W, C = x.shape
-        if res is not None:
-            res, ldres = cl_view(res, "prelu residual")
-        else:
-            ldres = 0
+        res, ldres = _opt_view(res, "prelu residual")
         slope = slope.contiguous().to(torch.float32)
         if slope.numel() != C:
             raise Mi355SegError(f"prelu: {slope.numel()} slopes for {C} channels")
@@ -1403,7 +1459,7 @@ class _PReLU(Function):
         L = lib()
         dx = torch.empty(x.shape, dtype=x.dtype, device=x.device)
         dslope = torch.empty(C, dtype=torch.float32, device=x.device)
-        ws = workspace(L.query("mi355seg_norm_ws_bytes", rows, 1, C), x.device)
+        ws = _norm_ws(L, rows, 1, C, x.device)
         L.call("mi355seg_prelu_bwd_" + _sfx(x), _p(dy), lddy, _p(x), ldx, _p(res), ldres, _p(slope), _p(dx), C, _p(dslope), rows, C,
                _p(ws), ws.numel(), _stream())
         return dx, (dx if res is not None else None), dslope
@@ -1443,27 +1499,25 @@ def scale_channels(x, scale):
 
 
 # ----------------------------------------------------------------------------- pool / upsample
+def _pool_forward(ctx, x):
+    """The forward the two pooling nodes share: the pooled tensor; the argmax codes and the input's shape are kept for the backward."""
+    x, ldx = cl_view(x, "max_pool3d input")
+    y, idx = _maxpool2_fwd(x, ldx)
+    ctx.save_for_backward(idx)
+    ctx.geom = tuple(x.shape)
+    return y
+
+
 class _MaxPool2(Function):
     @staticmethod
     def forward(ctx, x):
         xa = _get_amax(x)
-        x, ldx = cl_view(x, "max_pool3d input")
-        N, D, H, W, C = x.shape
-        y = torch.empty((N, D // 2, H // 2, W // 2, C), dtype=x.dtype, device=x.device)
-        idx = torch.empty((N, D // 2, H // 2, W // 2, C), dtype=torch.uint8, device=x.device)
-        lib().call("mi355seg_maxpool2_fwd_" + _sfx(x), _p(x), ldx, _p(y), C, _p(idx), N, D, H, W, C, _stream())
-        ctx.save_for_backward(idx)
-        ctx.geom = (N, D, H, W, C)
-        return _set_amax(y, xa)             # max |max_pool(x)| <= max |x|
+        return _set_amax(_pool_forward(ctx, x), xa)             # max |max_pool(x)| <= max |x|
 
     @staticmethod
     def backward(ctx, dy):
         (idx,) = ctx.saved_tensors
-        N, D, H, W, C = ctx.geom
-        dy, lddy = cl_view(dy, "max_pool3d grad")
-        dx = torch.empty((N, D, H, W, C), dtype=dy.dtype, device=dy.device)
-        lib().call("mi355seg_maxpool2_bwd_" + _sfx(dy), _p(dy), lddy, _p(idx), _p(dx), C, N, D, H, W, C, _stream())
-        return dx
+        return _maxpool2_bwd(*cl_view(dy, "max_pool3d grad"), idx, ctx.geom)
 
 
 class _PoolAndSkip(Function):
@@ -1472,13 +1526,7 @@ class _PoolAndSkip(Function):
 
     @staticmethod
     def forward(ctx, x):
-        xv, ldx = cl_view(x, "max_pool3d input")
-        N, D, H, W, C = xv.shape
-        y = torch.empty((N, D // 2, H // 2, W // 2, C), dtype=xv.dtype, device=xv.device)
-        idx = torch.empty((N, D // 2, H // 2, W // 2, C), dtype=torch.uint8, device=xv.device)
-        lib().call("mi355seg_maxpool2_fwd_" + _sfx(xv), _p(xv), ldx, _p(y), C, _p(idx), N, D, H, W, C, _stream())
-        ctx.save_for_backward(idx)
-        ctx.geom = (N, D, H, W, C)
+        y = _pool_forward(ctx, x)
         skip = x.view_as(x)
         xa = _get_amax(x)
         if xa is not None:              # max |max_pool(x)| <= max |x| (equal for the non-negative outputs of a ReLU)
@@ -1489,12 +1537,8 @@ class _PoolAndSkip(Function):
     @staticmethod
     def backward(ctx, dy, dskip):
         (idx,) = ctx.saved_tensors
-        N, D, H, W, C = ctx.geom
         dy, lddy = cl_view(dy, "max_pool3d grad")
-        ds, lds = cl_view(dskip, "skip grad")
-        dx = torch.empty((N, D, H, W, C), dtype=dy.dtype, device=dy.device)
-        lib().call("mi355seg_maxpool2_bwd_add_" + _sfx(dy), _p(dy), lddy, _p(idx), _p(ds), lds, _p(dx), C, N, D, H, W, C, _stream())
-        return dx
+        return _maxpool2_bwd(dy, lddy, idx, ctx.geom, cl_view(dskip, "skip grad"))
 
 
 def max_pool3d_2x_and_skip(x):
@@ -1513,16 +1557,11 @@ class _Upsample2(Function):
         N, D, H, W, C = x.shape
         y = torch.empty((N, 2 * D, 2 * H, 2 * W, C), dtype=x.dtype, device=x.device)
         lib().call("mi355seg_upsample2_fwd_" + _sfx(x), _p(x), ldx, _p(y), C, N, D, H, W, C, _stream())
-        ctx.geom = (N, D, H, W, C)
         return y
 
     @staticmethod
     def backward(ctx, dy):
-        N, D, H, W, C = ctx.geom
-        dy, lddy = cl_view(dy, "upsample grad")
-        dx = torch.empty((N, D, H, W, C), dtype=dy.dtype, device=dy.device)
-        lib().call("mi355seg_upsample2_bwd_" + _sfx(dy), _p(dy), lddy, _p(dx), C, N, D, H, W, C, _stream())
-        return dx
+        return _upsample2_bwd(*cl_view(dy, "upsample grad"))
 
 
 def upsample_nearest_2x(x):
@@ -2450,20 +2489,14 @@ class _BnActCatScaled(Function):
         rows = N * D * H * W
         L = lib()
         dev = y.device
-        ws = workspace(L.query("mi355seg_norm_ws_bytes", rows, 1, Cu), dev)
+        ws = _norm_ws(L, rows, 1, Cu, dev)
         if training:
-            mean = torch.empty(Cu, dtype=torch.float32, device=dev)
-            rstd = torch.empty(Cu, dtype=torch.float32, device=dev)
-            L.call("mi355seg_norm_stats_" + _sfx(y), _p(y), ldy, rows, 1, Cu, eps, _p(mean), _p(rstd), _p(rmean), _p(rvar), momentum,
-                   _p(ws), ws.numel(), _stream())
+            mean, rstd = _batch_stats(L, y, ldy, rows, 1, Cu, eps, rmean, rvar, momentum, ws)
         else:
-            mean = rmean
-            rstd = torch.empty(Cu, dtype=torch.float32, device=dev)
-            L.call("mi355seg_rstd_from_var_f32", _p(rvar), eps, _p(rstd), Cu, _stream())
+            mean, rstd = _running_stats(L, rmean, rvar, eps, Cu)
         both = torch.empty((N, D, H, W, Cu + Cs), dtype=y.dtype, device=dev)
         right = both.data_ptr() + both.element_size() * Cu
-        L.call("mi355seg_norm_act_fwd_" + _sfx(y), _p(y), ldy, _p(mean), _p(rstd), _p(gamma), _p(beta), None, 0,
-               both.data_ptr(), Cu + Cs, rows, 1, Cu, act, slope, _stream())
+        _norm_act_fwd(L, y, ldy, mean, rstd, gamma, beta, _NO_RES, both.data_ptr(), Cu + Cs, rows, 1, Cu, act, slope)
         if scale is not None:
             scale = scale.contiguous().to(torch.float32)
             L.call("mi355seg_scale_channels_" + _sfx(y), _p(skip), lds, _p(scale), right, Cu + Cs, D * H * W, N, Cs, _stream())
@@ -2478,16 +2511,12 @@ class _BnActCatScaled(Function):
         y, mean, rstd, gamma, beta, scale = ctx.saved_tensors
         ldy, rows, Cu, Cs, act, slope, training, (N, D, H, W) = ctx.cfg
         if not training:
-            raise Mi355SegError("backward through eval-mode BatchNorm (running statistics) is not supported")
+            raise Mi355SegError(_EVAL_BN_BACKWARD)
         dboth, ldd = cl_view(_like(dboth, y), "up-transition concat grad")
         L = lib()
         dev = y.device
-        ws = workspace(L.query("mi355seg_norm_ws_bytes", rows, 1, Cu), dev)
-        dy = torch.empty(y.shape, dtype=y.dtype, device=dev)
-        dgamma = torch.empty(Cu, dtype=torch.float32, device=dev)
-        dbeta = torch.empty(Cu, dtype=torch.float32, device=dev)
-        L.call("mi355seg_norm_act_bwd_" + _sfx(y), _p(dboth), ldd, _p(y), ldy, _p(mean), _p(rstd), _p(gamma), _p(beta), None, 0,
-               _p(dy), Cu, _p(dgamma), _p(dbeta), None, 0, rows, 1, Cu, act, slope, _p(ws), ws.numel(), _stream())
+        ws = _norm_ws(L, rows, 1, Cu, dev)
+        dy, dgamma, dbeta, _, _ = _norm_act_bwd(L, dboth, ldd, y, ldy, mean, rstd, gamma, beta, _NO_RES, rows, 1, Cu, act, slope, ws)
         right = dboth.data_ptr() + dboth.element_size() * Cu
         if scale is not None:
             dskip = torch.empty((N, D, H, W, Cs), dtype=y.dtype, device=dev)
@@ -2707,9 +2736,7 @@ class _Linear(Function):
         if mask is not None:
             dy2 = _mul(dy2, mask.view(M, N))
         if relu:                                            # dy * 1[y > 0]: the ReLU backward kernel, keyed on the saved output (mask 0 => y 0 and dy 0)
-            g = torch.empty_like(dy2)
-            lib().call("mi355seg_act_bwd_f32", _p(dy2), N, _p(yrelu), N, None, 0, _p(g), N, M, N, ACT_RELU, 0.0, _stream())
-            dy2 = g
+            dy2 = _act_bwd(dy2, N, yrelu, N, _NO_RES, M, N, ACT_RELU, 0.0)
         dx = torch.empty((M, K), dtype=dy2.dtype, device=dy2.device)
         _gemm(_p(dy2), N, 1, 0, 0, _p(w), K, 1, 0, 0, _p(dx), K, 0, 0, None, M, K, N, lowp=lowp)
         # weight gradient; the bias gradient (column sums of dy) rides in the same launch on the token encoder's shapes

@@ -59,6 +59,42 @@ def test_concat_base_accepts_only_the_right_slice_of_a_matching_buffer():
     assert F._concat_base(torch.zeros(lead + (Cs,)), Cout, lead, torch.float32) is None                     # no base at all
 
 
+def _source(name):
+    return open(os.path.join(os.path.dirname(os.path.abspath(mi355seg.functional.__file__)), name)).read()
+
+
+# entry-point stem -> the one function of functional.py that names it (the _add_ forms are spelt by their base launcher);
+# norm_stats_from_sums is another entry point, with a launcher of its own (_stats_from_sums)
+LAUNCHERS = {"norm_stats_(?!from_sums)": "_batch_stats", "rstd_from_var": "_running_stats", "norm_act_fwd": "_norm_act_fwd",
+             "norm_act_bwd_colsum": "_norm_act_bwd", "maxpool2_fwd": "_maxpool2_fwd", "maxpool2_bwd": "_maxpool2_bwd",
+             "upsample2_bwd": "_upsample2_bwd", "act_bwd_": "_act_bwd"}
+
+
+@pytest.mark.parametrize("stem", sorted(LAUNCHERS))
+def test_each_norm_act_pool_entry_is_named_by_its_launcher_alone(stem):
+    src, pattern = _source("functional.py"), '"mi355seg_' + stem
+    hits = [m.start() for m in re.finditer(pattern, src)]
+    assert len(hits) == 1, f"{pattern} occurs {len(hits)} times in functional.py"
+    begin = src.index(f"\ndef {LAUNCHERS[stem]}(")
+    assert begin < hits[0] < src.index("\n\n\n", begin + 1), f"{pattern} is named outside {LAUNCHERS[stem]}"
+    assert not re.search(pattern, _source("custom_ops.py"))
+    assert not re.search(r"mi355seg_(norm|maxpool2|upsample2|act)_", _source("custom_ops.py"))
+
+
+def test_concat_out_is_the_slice_concat_base_recognises():
+    lead, dtype = (1, 2, 3, 4), torch.float32
+    full, y, pitch = F._concat_out(lead, 0, 10, dtype, "cpu")
+    assert full is None and tuple(y.shape) == lead + (10,) and y.is_contiguous() and y._base is None and pitch == 10
+    full, y, pitch = F._concat_out(lead, 6, 10, torch.bfloat16, "cpu")
+    assert tuple(full.shape) == lead + (16,) and full.is_contiguous() and full.dtype == torch.bfloat16 and pitch == 16
+    assert tuple(y.shape) == lead + (10,) and y.stride(3) == 16 and y.data_ptr() == full.data_ptr() + 6 * full.element_size()
+    assert F._concat_base(y, 6, lead, torch.bfloat16) is full
+
+
+def test_opt_view_of_an_absent_tensor(no_library):
+    assert F._opt_view(None, "residual") == (None, 0)
+
+
 def test_unread_fusion_switches_are_gone():
     src = open(os.path.join(os.path.dirname(os.path.abspath(mi355seg.functional.__file__)), "functional.py")).read()
     for name in ("RES_EPILOGUE", "CAT_FUSION", "STEM_FUSION", "HEAD_FUSION", "POOL_FUSION"):
