@@ -85,6 +85,11 @@ def compose(conf_dir, overrides=(), job_name="train", now=None):
     return out
 
 
+def absent(v):
+    """A config value that stands for "key not given": None, the empty string, or the words a command line writes for it."""
+    return v is None or str(v) in ("", "None", "none", "null")
+
+
 def parse_patch_size(config):
     """train.py:312-320: 'a, b, c' -> (a, b, c); 'a' -> int."""
     ps = config.patch_size

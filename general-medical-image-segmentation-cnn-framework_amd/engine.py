@@ -58,10 +58,12 @@ def train_step(model, optimizer, x, gt, criterion=None, sync_metric=True, grad_h
     """One iteration.  ``gt`` is the single-channel label volume [N,1,D,H,W].  ``dtype`` = torch.bfloat16 runs the
     forward under mi355seg.autocast (bf16 activations; the loss and everything after it stay fp32).
     ``grad_hook`` (if given) runs between backward and optimizer.step -- the data-parallel
-    gradient all-reduce plugs in there.  Returns a dict with pred, mask, loss and, when
+    gradient all-reduce plugs in there.  A ``criterion`` with a ``tail`` method (CompoundLoss) runs its fused tail and adds
+    'loss_terms' to the result.  Returns a dict with pred, mask, loss and, when
     ``sync_metric``, python floats jaccard/dice (one tiny D2H copy); otherwise the raw
     int64[4] counters stay on the device under 'counts'."""
     optimizer.zero_grad(set_to_none=True)
+    loss_terms = None
     gt2 = two_channel_gt(gt)
     x = x.to(torch.float32)
     # every training-mode BatchNorm counter advanced by one multi-tensor launch AFTER the forward (the modules tally their calls
@@ -90,6 +92,9 @@ def train_step(model, optimizer, x, gt, criterion=None, sync_metric=True, grad_h
         if criterion is None:
             # nn.BCEWithLogitsLoss + pred.argmax + gt.argmax + the Dice counters in one pass over the logits
             loss, mask, counts = F.bce_argmax_dice(pred, gt2)
+        elif hasattr(criterion, "tail"):
+            # a compound loss (utils.loss_function.CompoundLoss): the same four results from its own fused pass, plus its two terms
+            loss, mask, counts, loss_terms = criterion.tail(pred, gt2)
         else:
             loss = criterion(pred, gt2)
             with torch.no_grad():
@@ -105,6 +110,8 @@ def train_step(model, optimizer, x, gt, criterion=None, sync_metric=True, grad_h
     if step_optimizer:                       # (GraphedTrainStep with a gradient hook captures the optimizer step as a graph of its own)
         optimizer.step()
     out = {"pred": pred, "mask": mask, "loss": loss.detach(), "counts": counts}
+    if loss_terms is not None:
+        out["loss_terms"] = loss_terms           # fp64[2] on the device: voxel term, region term (unweighted)
     if sync_metric:
         out["jaccard"], out["dice"] = metric_from_counts(counts.cpu().tolist())
     return out
@@ -157,6 +164,8 @@ class GraphedTrainStep:
             for _ in range(warmup):
                 o = train_step(model, optimizer, self.x, self.gt, criterion, sync_metric=False, dtype=dtype, grad_hook=grad_hook)
                 self.first = {"loss": o["loss"].detach().clone(), "counts": o["counts"].clone()}
+                if "loss_terms" in o:
+                    self.first["loss_terms"] = o["loss_terms"].clone()
                 del o
         torch.cuda.current_stream().wait_stream(side)
         torch.cuda.synchronize()

@@ -8,6 +8,7 @@ Activations inside the package are channel-last: a 5-D fp32 tensor of logical sh
 [N, D, H, W, C] whose last stride is 1 and whose voxel pitch (stride of W) may exceed C
 (a channel slice of a wider concat buffer).
 """
+import collections
 import ctypes
 import os
 import threading
@@ -1927,6 +1928,108 @@ def bce_argmax_dice(logits, target):
     """Fused tail of the train step: (loss, mask int64 [N,1,...], counts int64[4]); the loss carries the autograd
     edge of nn.BCEWithLogitsLoss()."""
     return _BCEArgmaxDice.apply(logits, target)
+
+
+# ----------------------------------------------------------------------------- compound losses (config.loss; csrc/loss_tail.hip)
+LOSS_MODES = ("dice", "dice_bce", "ce", "dice_ce", "focal", "dice_focal", "tversky")
+LOSS_VOXEL_TERMS = {None: 0, "bce": 1, "focal": 2, "ce": 3}          # the C-ABI's voxel_term / region_term selectors
+LOSS_REGION_TERMS = {None: 0, "dice": 1, "tversky": 2}
+_LOSS_MODE_TERMS = {"dice": (None, "dice"), "dice_bce": ("bce", "dice"), "ce": ("ce", None), "dice_ce": ("ce", "dice"),
+                    "focal": ("focal", None), "dice_focal": ("focal", "dice"), "tversky": (None, "tversky")}
+MAX_LOSS_CLASSES = 16
+FOCAL_GAMMA, TVERSKY_ALPHA, TVERSKY_BETA = 2.0, 0.3, 0.7        # the defaults of LossSpec.from_mode / CompoundLoss
+
+
+class LossSpec(collections.namedtuple("LossSpec", "voxel region gamma alpha beta w_voxel w_region")):
+    """What mi355seg_loss_tail_*_f32 computes: loss = w_voxel * voxel + w_region * region with voxel in (None, "bce", "focal", "ce")
+    and region in (None, "dice", "tversky"); gamma is the focal exponent (0 or 1..8), alpha / beta the Tversky weights of false
+    positives / false negatives.  Definitions: DESIGN.md 4.16."""
+    __slots__ = ()
+
+    @classmethod
+    def from_mode(cls, mode, weights=(1.0, 1.0), focal_gamma=FOCAL_GAMMA, tversky_alpha=TVERSKY_ALPHA, tversky_beta=TVERSKY_BETA):
+        if not isinstance(mode, str) or mode not in _LOSS_MODE_TERMS:
+            raise ValueError(f"loss mode must be one of {', '.join(LOSS_MODES)}, got {mode!r}")
+        voxel, region = _LOSS_MODE_TERMS[mode]
+        try:
+            wv, wr = (float(w) for w in weights)
+        except (TypeError, ValueError):
+            raise ValueError(f"loss weights must be two numbers (voxel term, region term), got {weights!r}") from None
+        return cls(voxel, region, float(focal_gamma), float(tversky_alpha), float(tversky_beta), wv, wr).checked()
+
+    def checked(self):
+        """The refusals of the C entry points, as ValueError before anything reaches the device."""
+        if self.voxel not in LOSS_VOXEL_TERMS or self.region not in LOSS_REGION_TERMS:
+            raise ValueError(f"unknown loss term in {tuple(self)!r}: voxel in (None, 'bce', 'focal', 'ce'), region in (None, 'dice', 'tversky')")
+        if self.voxel is None and self.region is None:
+            raise ValueError("a loss needs a voxel term or a region term")
+        if not (self.w_voxel >= 0 and self.w_region >= 0):
+            raise ValueError(f"loss weights must be >= 0, got {(self.w_voxel, self.w_region)!r}")
+        if not (self.gamma == 0 or 1 <= self.gamma <= 8):
+            raise ValueError(f"focal gamma must be 0 or in [1, 8], got {self.gamma!r}")
+        if not (self.alpha >= 0 and self.beta >= 0) or (self.region == "tversky" and not self.alpha + self.beta > 0):
+            raise ValueError(f"tversky alpha and beta must be >= 0 with alpha + beta > 0, got {(self.alpha, self.beta)!r}")
+        return self
+
+
+class _LossTail(Function):
+    """The fused tail for a LossSpec: (loss, mask, counts, terms, sums) from one pass over logits and target plus a one-block
+    finalise; the backward is one pass.  The coefficients of the backward stay on the device (coef), so the pair is capturable
+    in a HIP graph exactly like _BCEArgmaxDice."""
+
+    @staticmethod
+    def forward(ctx, logits, target, spec):
+        _require_cuda(logits, "loss_tail input")
+        logits, target = aligned_contiguous(logits), aligned_contiguous(target.to(torch.float32))
+        if logits.shape != target.shape:
+            raise ValueError(f"Target size ({tuple(target.shape)}) must be the same as input size ({tuple(logits.shape)})")
+        if logits.dim() < 3:
+            raise Mi355SegError(f"loss_tail: expected [N,K,...], got {tuple(logits.shape)}")
+        N, K = logits.shape[0], logits.shape[1]
+        S = logits[0, 0].numel()
+        dev = logits.device
+        L = lib()
+        ws = workspace(L.query("mi355seg_loss_tail_ws_bytes", N, K, S), dev)
+        loss = torch.empty((), dtype=torch.float32, device=dev)
+        mask = torch.empty((N, 1) + tuple(logits.shape[2:]), dtype=torch.int64, device=dev)
+        counts = torch.empty(4, dtype=torch.int64, device=dev)
+        terms = torch.empty(2, dtype=torch.float64, device=dev)
+        sums = torch.empty((K, 5), dtype=torch.float64, device=dev)
+        coef = torch.empty(1 + 2 * MAX_LOSS_CLASSES, dtype=torch.float64, device=dev)
+        args = (LOSS_VOXEL_TERMS[spec.voxel], LOSS_REGION_TERMS[spec.region], spec.gamma)
+        L.call("mi355seg_loss_tail_fwd_f32", _p(logits), _p(target), N, K, S, *args, spec.alpha, spec.beta, spec.w_voxel, spec.w_region,
+               _p(loss), _p(terms), _p(sums), _p(mask), _p(counts), _p(coef), _p(ws), ws.numel(), _stream())
+        ctx.save_for_backward(logits, target, coef)
+        ctx.args = args
+        ctx.mark_non_differentiable(mask, counts, terms, sums)
+        ctx.set_materialize_grads(False)         # (or autograd zero-fills a gradient for each of them, the int64 mask included, per backward)
+        return loss, mask, counts, terms, sums
+
+    @staticmethod
+    def backward(ctx, g, _gmask, _gcounts, _gterms, _gsums):
+        if g is None:
+            return None, None, None
+        logits, target, coef = ctx.saved_tensors
+        g = g.contiguous().to(torch.float32)
+        N, K = logits.shape[0], logits.shape[1]
+        d = torch.empty_like(logits)
+        lib().call("mi355seg_loss_tail_bwd_f32", _p(logits), _p(target), _p(coef), _p(g), N, K, logits[0, 0].numel(), *ctx.args, _p(d), _stream())
+        return d, None, None
+
+
+def loss_tail_full(logits, target, spec):
+    """loss_tail plus the per-class sums: (loss, mask, counts, terms, sums fp64 [K,5]) -- sums[k] = (sum p t, sum p, sum t, sum p^2,
+    sum t^2) with p = sigmoid(logits[:, k]), what dice_sums gives for class k."""
+    if not isinstance(spec, LossSpec):
+        raise TypeError(f"loss_tail: spec must be a functional.LossSpec, got {type(spec).__name__}")
+    return _LossTail.apply(logits, target, spec.checked())
+
+
+def loss_tail(logits, target, spec):
+    """Fused tail of the train step for a compound loss: (loss, mask int64 [N,1,...], counts int64[4], terms fp64[2]).  ``loss`` =
+    spec.w_voxel * terms[0] + spec.w_region * terms[1] carries the autograd edge; mask, counts and terms do not.  logits and
+    target [N,K,...] float32, 1 <= K <= 16 (target: the K-channel float target bce_argmax_dice takes)."""
+    return loss_tail_full(logits, target, spec)[:4]
 
 
 def two_channel_gt(gt):

@@ -33,7 +33,7 @@ import numpy as np
 import torch
 
 from . import functional as F
-from .config import compose, parse_patch_size
+from .config import absent as _absent, compose, parse_patch_size
 from .engine import mixed_precision_dtype
 from .registry import build_model
 from .models.three_d.IS import set_band_split
@@ -236,10 +236,6 @@ def parse_postprocess(config):
     if isinstance(c, bool) or not (isinstance(c, int) or (isinstance(c, str) and c.strip().isdigit())) or int(c) not in F.CONNECTIVITIES:
         raise ValueError(f"config.connectivity must be 6, 18 or 26, got {c!r}")
     return keep, small, int(c)
-
-
-def _absent(v):
-    return v is None or str(v) in ("", "None", "none", "null")
 
 
 def parse_overlap_mode(config):

@@ -14,12 +14,73 @@ import torch
 from torch.optim.lr_scheduler import StepLR
 
 from . import distributed as D
-from .config import compose, parse_patch_size
+from .config import absent as _absent, compose, parse_patch_size
 from .data import make_loader
+from . import functional as F
 from .utils.metric import metric_from_counts
 from .engine import GraphedTrainStep, make_adam, mixed_precision_dtype, train_step, weights_init_normal
 from .registry import build_model
 from .models.three_d.IS import set_band_split
+
+
+LOSS_KEYS = ("loss_weights", "focal_gamma", "tversky_alpha", "tversky_beta")
+
+
+def parse_loss(config):
+    """``config.loss`` -> the criterion of the run: None (the live BCE path of train.py:115, engine.train_step's default) when the key
+    is absent, empty or "bce"; otherwise a utils.loss_function.CompoundLoss built from ``config.loss_weights=wv,wr``,
+    ``config.focal_gamma``, ``config.tversky_alpha`` and ``config.tversky_beta`` (each only with a mode that has that term)."""
+    from .utils.loss_function import CompoundLoss
+    get = lambda k: config.get(k) if hasattr(config, "get") else getattr(config, k, None)
+    mode = get("loss")
+    allowed = ("bce",) + F.LOSS_MODES
+    if not _absent(mode) and (not isinstance(mode, str) or mode not in allowed):
+        raise ValueError(f"config.loss must be one of {', '.join(allowed)}, got {mode!r}")
+    mode = None if _absent(mode) or mode == "bce" else mode
+    given = {k: get(k) for k in LOSS_KEYS if not _absent(get(k))}
+    has = {"loss_weights": mode is not None, "focal_gamma": mode in ("focal", "dice_focal"),
+           "tversky_alpha": mode == "tversky", "tversky_beta": mode == "tversky"}
+    needs = {"loss_weights": "a compound mode (" + ", ".join(F.LOSS_MODES) + ")", "focal_gamma": "focal or dice_focal",
+             "tversky_alpha": "tversky", "tversky_beta": "tversky"}
+    for k, v in given.items():
+        if not has[k]:
+            raise ValueError(f"config.{k} must be given only with config.loss = {needs[k]}, got {v!r} with config.loss={mode or 'bce'}")
+    if mode is None:
+        return None
+
+    def number(k, rule, ok):
+        v = given[k]
+        if isinstance(v, str):
+            try:
+                v = float(v)
+            except ValueError:
+                v = None
+        if isinstance(v, bool) or not isinstance(v, (int, float)) or not ok(float(v)):
+            raise ValueError(f"config.{k} must be {rule}, got {given[k]!r}")
+        return float(v)
+
+    kw = {}
+    if "loss_weights" in given:
+        w = given["loss_weights"]
+        parts = w.strip("()[] ").split(",") if isinstance(w, str) else (list(w) if hasattr(w, "__len__") else [w])
+        bad = ValueError(f"config.loss_weights must be two numbers wv,wr (voxel term, region term), each >= 0, got {w!r}")
+        try:
+            vals = [float(p) for p in parts if not isinstance(p, bool)]
+        except (TypeError, ValueError):
+            raise bad from None
+        if len(parts) != 2 or len(vals) != 2 or not all(v >= 0 for v in vals):
+            raise bad
+        kw["weights"] = tuple(vals)
+    if "focal_gamma" in given:
+        kw["focal_gamma"] = number("focal_gamma", "0 or a number in [1, 8]", lambda v: v == 0 or 1 <= v <= 8)
+    for k in ("tversky_alpha", "tversky_beta"):
+        if k in given:
+            kw[k] = number(k, "a number >= 0", lambda v: v >= 0)
+    if mode == "tversky":
+        a, b = kw.get("tversky_alpha", F.TVERSKY_ALPHA), kw.get("tversky_beta", F.TVERSKY_BETA)
+        if not a + b > 0:
+            raise ValueError(f"config.tversky_alpha and config.tversky_beta must not both be 0, got {a!r} and {b!r}")
+    return CompoundLoss(mode, **kw)
 
 
 class AverageMeter:
@@ -75,6 +136,9 @@ def train(config, model, logger):
     # accelerator.prepare (train.py:167-169): rank 0's parameters / buffers everywhere (after the optional checkpoint
     # load, so a resumed rank 0 wins), flat buffers for the per-step broadcast, bucketed gradient reducer
     reducer = D.setup_replica(model)
+    criterion = parse_loss(config)                                              # config.loss: None = the live BCE path (train.py:115)
+    if criterion is not None:
+        logger.info(f"loss: {criterion}")
     act_dtype = mixed_precision_dtype(config)                                   # Accelerator(mixed_precision=...) of train.py:167
     if act_dtype != torch.float32:
         logger.info(f"mixed precision: activations in {act_dtype} (fp32 parameters, gradients, statistics, loss)")
@@ -92,18 +156,21 @@ def train(config, model, logger):
             if hip_graph and graphed is None:
                 # the first iteration runs inside the constructor (eager, on a side stream: workspaces sized, kernel attributes set),
                 # then the iteration is captured for the following ones; a replay waits for the buffer broadcast launched above
-                graphed = GraphedTrainStep(model, optimizer, x, gt, warmup=1, dtype=act_dtype, grad_hook=reducer)
+                graphed = GraphedTrainStep(model, optimizer, x, gt, criterion=criterion, warmup=1, dtype=act_dtype, grad_hook=reducer)
                 out = dict(graphed.first)
                 out["jaccard"], out["dice"] = metric_from_counts(out["counts"].cpu().tolist())
             elif hip_graph:
                 out = graphed(x, gt)
             else:
-                out = train_step(model, optimizer, x, gt, grad_hook=reducer, dtype=act_dtype)    # train.py:187-221
+                out = train_step(model, optimizer, x, gt, criterion=criterion, grad_hook=reducer, dtype=act_dtype)    # train.py:187-221
             iteration += 1
             loss_meter.update(out["loss"].item(), x.size(0))
             dice_meter.update(out["dice"], x.size(0))
             if scalars:
-                scalars.write(json.dumps({"iteration": iteration, "Training/Loss": loss_meter.val, "Training/dice": dice_meter.val}) + "\n")
+                row = {"iteration": iteration, "Training/Loss": loss_meter.val, "Training/dice": dice_meter.val}
+                if criterion is not None:                       # a compound loss: its two terms, unweighted
+                    row["Training/loss_voxel"], row["Training/loss_region"] = out["loss_terms"].tolist()
+                scalars.write(json.dumps(row) + "\n")
                 scalars.flush()
             logger.info(f"\nEpoch: {epoch} Batch: {i}, train time: {time.time() - t0:.3f}s\nLoss: {loss_meter.val}\nDice: {dice_meter.val}\n")
         if scheduler is not None:

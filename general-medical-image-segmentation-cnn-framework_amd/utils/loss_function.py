@@ -102,3 +102,27 @@ class DiceLossss(nn.Module):
         dice = 1 - (2 * s[:, 0] + smooth) / (s[:, 3] + s[:, 4] + smooth)
         w = torch.as_tensor(weight, dtype=torch.float64, device=dice.device)
         return ((dice * w).sum() / self.n_classes).to(torch.float32)
+
+
+class CompoundLoss(nn.Module):
+    """``config.loss``: a voxel term plus a region term on the fused tail (functional.loss_tail: one pass over logits and target
+    forward, one backward).  Modes (functional.LOSS_MODES): dice | dice_bce | ce | dice_ce | focal | dice_focal | tversky, where
+    bce = nn.BCEWithLogitsLoss (train.py:115), ce = cross_entropy_3D against target.argmax(1) (loss_function.py:8-16), dice =
+    DiceLoss (loss_function.py:121-130); focal (Lin et al., exponent ``focal_gamma``, no alpha balancing) and tversky (Salehi et
+    al., ``tversky_alpha`` on false positives, ``tversky_beta`` on false negatives, per class over the batch) are the project's
+    own.  ``weights`` = (voxel, region).  ``forward`` returns the scalar loss (an ordinary criterion); ``tail`` returns (loss,
+    mask, counts, terms), which engine.train_step uses in place of criterion + two argmaxes + dice_counts."""
+
+    def __init__(self, mode, weights=(1, 1), focal_gamma=2.0, tversky_alpha=0.3, tversky_beta=0.7):
+        super().__init__()
+        self.mode = mode
+        self.spec = F.LossSpec.from_mode(mode, weights, focal_gamma, tversky_alpha, tversky_beta)
+
+    def tail(self, pred, target):
+        return F.loss_tail(pred, target, self.spec)
+
+    def forward(self, pred, target):
+        return self.tail(pred, target)[0]
+
+    def extra_repr(self):
+        return f"mode={self.mode!r}, spec={tuple(self.spec)!r}"

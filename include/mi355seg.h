@@ -564,6 +564,36 @@ int mi355seg_bce_argmax_dice_f32(const float* logits, const float* target, long 
                                  float* loss, int64_t* mask, int64_t* counts,
                                  void* ws, size_t ws_bytes, void* stream);
 
+/* Fused train-step tail for the compound losses (config.loss; csrc/loss_tail.hip): loss = w_voxel * voxel + w_region * region,
+ * the argmax mask, gt.argmax and the four Dice counters (train.py:204,221; same order, NaN rule and counter arithmetic as
+ * mi355seg_bce_argmax_dice_f32) from ONE pass over logits and target [N,K,S], 1 <= K <= 16, plus a one-block finalise.
+ *   voxel_term: 0 none | 1 bce   (nn.BCEWithLogitsLoss, train.py:115,209: mean over N*K*S of max(x,0) - x t + log1p(exp(-|x|)))
+ *                      | 2 focal (no reference line; Lin et al.: mean of q^gamma * bce, q = p + t - 2 p t, p = sigmoid(x);
+ *                                 gamma = 0 or 1 <= gamma <= 8, gamma = 0 is the bce path)
+ *                      | 3 ce    (cross_entropy_3D, loss_function.py:8-16, size_average=True, label = argmax_k target; K >= 2)
+ *   region_term: 0 none | 1 dice    (DiceLoss, loss_function.py:121-130: 1 - 2 (sum I + eps) / (sum P + sum T + eps), eps = 1e-5)
+ *                       | 2 tversky (no reference line; Salehi et al.: 1 - (1/K) sum_k (I_k + eps) / (I_k + alpha (P_k - I_k)
+ *                                    + beta (T_k - I_k) + eps), alpha, beta >= 0, alpha + beta > 0)
+ * with per class I_k = sum p t, P_k = sum p, T_k = sum t over the batch.  Outputs (device): loss fp32[1]; terms fp64[2] (voxel,
+ * region, unweighted; 0 for an absent term); sums fp64[K][5] (the five sums of mi355seg_dice_sums_f32 with the sigmoid, per
+ * class); mask int64 [N,1,S]; counts int64[4]; coef fp64[1 + 2 K], what the backward needs (w_voxel, w_region *
+ * dRegion/dI_k, w_region * dRegion/dP_k).  Nothing passes through the host; deterministic (fixed-order partials, no atomics).
+ * Refused before any launch: null pointers, K outside 1..16, an unknown term, both terms absent, ce with K = 1, gamma outside
+ * {0} u [1,8], negative alpha / beta / weights, a workspace below mi355seg_loss_tail_ws_bytes (which is 0 for bad extents). */
+size_t mi355seg_loss_tail_ws_bytes(long long N, int K, long long S);
+int mi355seg_loss_tail_fwd_f32(const float* logits, const float* target, long long N, int K, long long S,
+                               int voxel_term, int region_term, float gamma, float alpha, float beta, float w_voxel, float w_region,
+                               float* loss, double* terms, double* sums, int64_t* mask, int64_t* counts, double* coef,
+                               void* ws, size_t ws_bytes, void* stream);
+/* dlogits = gscale[0] * dloss/dlogits in ONE pass over logits and target (16-byte loads when S % 4 == 0 and the pointers are
+ * aligned); coef from the forward, gscale the upstream scalar on the device.  No workspace.  Each term's gradient is rounded to
+ * fp32 as the kernels of the unfused criterion round it (mi355seg_bce_logits_bwd_f32, mi355seg_ce3d_bwd_f32,
+ * mi355seg_dice_sums_bwd_f32) and the two are then added: with 0 / 1 targets and unit weights bce + dice and ce + dice have the
+ * bits of those kernels' summed outputs. */
+int mi355seg_loss_tail_bwd_f32(const float* logits, const float* target, const double* coef, const float* gscale,
+                               long long N, int K, long long S, int voxel_term, int region_term, float gamma,
+                               float* dlogits, void* stream);
+
 /* Sum-type reductions for the library losses (loss_function.py:61-185):
  * out[0]=sum(a*b) out[1]=sum(a) out[2]=sum(b) out[3]=sum(a*a) out[4]=sum(b*b), a = sigmoid(x) if
  * apply_sigmoid else x.  Deterministic wavefront-shuffle + two-stage reduce. */
