@@ -21,6 +21,13 @@
 // aligned, a thread owns four consecutive x (128-bit loads and stores), provided every patch of the batch starts at an x that is
 // a multiple of 4: then the four voxels are covered by the same patches.  A batch with another origin takes the same kernel one
 // voxel at a time; every other shape takes the scalar kernel.  The arithmetic per element is the same in all three.
+//
+// MIRROR TEST-TIME AUGMENTATION (aggregate_patches_flip; not in the reference, whose predict.py:133 calls the model once per patch).
+// The logits are those of a patch that was read mirrored (gather_patches_flip, api.hip), flip code 0..7: bit 2 mirrors z, bit 1 y,
+// bit 0 x.  The FLIP instantiations un-mirror them as they read them -- softmax over logits[b, :, m_z(z), m_y(y), m_x(x)] -- while
+// the weight and the destination keep (z, y, x); with the x bit a thread that owns four x loads the mirrored quad and reverses it in
+// registers.  Everything else is the code above, so the result is bitwise aggregate_patches on flipped logits.  The caller loops
+// over the flips OUTSIDE its walk of the grid: per element the order is (flip, patch), still independent of the batch size.
 #include "common.h"
 #include "internal.h"
 
@@ -36,6 +43,7 @@ static int agg_grid(long long items) {
 
 struct AggGeom {
     int K, first, count, pd, ph, pw, D, H, W;
+    int flip;                                                 // read by the FLIP kernels only: bit 2 mirrors z, bit 1 y, bit 0 x
 };
 
 // origin of patch `first + c`, and whether the whole patch lies inside the volume (a row that does not is skipped: nothing is
@@ -46,13 +54,17 @@ __device__ __forceinline__ bool agg_origin(const int* __restrict__ table, const 
     return oz >= 0 && oy >= 0 && ox >= 0 && oz <= g.D - g.pd && oy <= g.H - g.ph && ox <= g.W - g.pw;
 }
 
-// acc[k] = fmaf(w, softmax_k, acc[k]) for V consecutive x of patch c at patch coordinates (z, y, x ..)
-template <int KMAX, int V>
+// acc[k] = fmaf(w, softmax_k, acc[k]) for V consecutive x of patch c at patch coordinates (z, y, x ..).
+// FLIP: the logits are read at the mirrored coordinates (pd-1-z, ph-1-y, pw-1-x on the axes whose bit of g.flip is set); the window
+// weight keeps (z, y, x).  With the x bit the V = 4 mirrored voxels are the aligned quad at pw-4-x, reversed in registers.
+template <int KMAX, int V, bool FLIP>
 __device__ __forceinline__ void agg_add(const float* __restrict__ logits, const AggGeom& g, int c, int z, int y, int x,
                                         const float* __restrict__ wz, const float* __restrict__ wy, const float* __restrict__ wx,
                                         float (&a)[KMAX][V]) {
     const long long S = (long long)g.pd * g.ph * g.pw;
-    const float* p = logits + (long long)c * g.K * S + ((long long)z * g.ph + y) * g.pw + x;
+    const bool rev = FLIP && (g.flip & 1);
+    const int sz = FLIP && (g.flip & 4) ? g.pd - 1 - z : z, sy = FLIP && (g.flip & 2) ? g.ph - 1 - y : y, sx = rev ? g.pw - V - x : x;
+    const float* p = logits + (long long)c * g.K * S + ((long long)sz * g.ph + sy) * g.pw + sx;
     float e[KMAX][V], m[V], s[V], w[V];
 #pragma unroll
     for (int k = 0; k < KMAX; ++k) {
@@ -60,7 +72,7 @@ __device__ __forceinline__ void agg_add(const float* __restrict__ logits, const 
             if constexpr (V == 4) {
                 const f32x4_t v = ld4(p + (long long)k * S);
 #pragma unroll
-                for (int j = 0; j < V; ++j) e[k][j] = v[j];
+                for (int j = 0; j < V; ++j) e[k][j] = rev ? v[V - 1 - j] : v[j];
             } else {
                 e[k][0] = p[(long long)k * S];
             }
@@ -100,7 +112,7 @@ __device__ __forceinline__ void agg_add(const float* __restrict__ logits, const 
 }
 
 // V consecutive x of patch b, starting at patch coordinates (z, y, x); all V volume voxels are covered by the same patches
-template <int KMAX, int V>
+template <int KMAX, int V, bool FLIP>
 __device__ __forceinline__ void agg_voxels(const float* __restrict__ logits, const int* __restrict__ table, const AggGeom& g,
                                            int b, int z, int y, int x, const float* __restrict__ wz, const float* __restrict__ wy,
                                            const float* __restrict__ wx, float* __restrict__ acc) {
@@ -127,12 +139,12 @@ __device__ __forceinline__ void agg_voxels(const float* __restrict__ logits, con
             }
         }
     }
-    agg_add<KMAX, V>(logits, g, b, z, y, x, wz, wy, wx, a);
+    agg_add<KMAX, V, FLIP>(logits, g, b, z, y, x, wz, wy, wx, a);
     for (int c = b + 1; c < g.count; ++c) {                   // ascending patch index
         int cz, cy, cx;
         if (!agg_origin(table, g, c, cz, cy, cx)) continue;
         if (vz >= cz && vz < cz + g.pd && vy >= cy && vy < cy + g.ph && vx >= cx && vx < cx + g.pw)
-            agg_add<KMAX, V>(logits, g, c, vz - cz, vy - cy, vx - cx, wz, wy, wx, a);
+            agg_add<KMAX, V, FLIP>(logits, g, c, vz - cz, vy - cy, vx - cx, wz, wy, wx, a);
     }
 #pragma unroll
     for (int k = 0; k < KMAX; ++k) {
@@ -143,7 +155,7 @@ __device__ __forceinline__ void agg_voxels(const float* __restrict__ logits, con
     }
 }
 
-template <int KMAX, int V>
+template <int KMAX, int V, bool FLIP>
 __global__ __launch_bounds__(kAggThreads) void aggregate_patches_kernel(const float* __restrict__ logits, const int* __restrict__ table,
         AggGeom g, const float* __restrict__ wz, const float* __restrict__ wy, const float* __restrict__ wx, float* __restrict__ acc) {
     const int xw = g.pw / V;                                  // V == 4: the host checked pw % 4 == 0
@@ -158,9 +170,9 @@ __global__ __launch_bounds__(kAggThreads) void aggregate_patches_kernel(const fl
         const int y = (int)(r % g.ph);
         const int z = (int)(r / g.ph);
         if (V == 1 || quads) {
-            agg_voxels<KMAX, V>(logits, table, g, b, z, y, x, wz, wy, wx, acc);
+            agg_voxels<KMAX, V, FLIP>(logits, table, g, b, z, y, x, wz, wy, wx, acc);
         } else {
-            for (int j = 0; j < V; ++j) agg_voxels<KMAX, 1>(logits, table, g, b, z, y, x + j, wz, wy, wx, acc);
+            for (int j = 0; j < V; ++j) agg_voxels<KMAX, 1, FLIP>(logits, table, g, b, z, y, x + j, wz, wy, wx, acc);
         }
     }
 }
@@ -215,27 +227,52 @@ using namespace seg;
 
 extern "C" {
 
-int mi355seg_aggregate_patches_f32(const float* logits, int K, const int* table, int first, int count, int pd, int ph, int pw,
-                                   const float* wz, const float* wy, const float* wx, float* acc, int D, int H, int W, void* stream) {
-    SEG_CHECK_ARG(K >= 2 && K <= kAggMaxK, "aggregate_patches: K must lie in 2..%d, got %d", kAggMaxK, K);
-    SEG_CHECK_ARG(count > 0 && first >= 0 && pd > 0 && ph > 0 && pw > 0, "aggregate_patches: bad arguments (first %d, count %d, patch %dx%dx%d)",
+// flip < 0: the un-mirrored kernels (the instantiations that never look at g.flip)
+static int aggregate_patches_launch(const char* name, const float* logits, int K, const int* table, int first, int count, int pd, int ph,
+                                    int pw, const float* wz, const float* wy, const float* wx, int flip, float* acc, int D, int H, int W,
+                                    void* stream) {
+    SEG_CHECK_ARG(K >= 2 && K <= kAggMaxK, "%s: K must lie in 2..%d, got %d", name, kAggMaxK, K);
+    SEG_CHECK_ARG(count > 0 && first >= 0 && pd > 0 && ph > 0 && pw > 0, "%s: bad arguments (first %d, count %d, patch %dx%dx%d)", name,
                   first, count, pd, ph, pw);
-    SEG_CHECK_ARG(pd <= D && ph <= H && pw <= W, "aggregate_patches: patch %dx%dx%d larger than the volume %dx%dx%d", pd, ph, pw, D, H, W);
-    SEG_CHECK_ARG(logits && table && wz && wy && wx && acc, "aggregate_patches: null pointer");
+    SEG_CHECK_ARG(pd <= D && ph <= H && pw <= W, "%s: patch %dx%dx%d larger than the volume %dx%dx%d", name, pd, ph, pw, D, H, W);
+    SEG_CHECK_ARG(logits && table && wz && wy && wx && acc, "%s: null pointer", name);
     hipStream_t st = (hipStream_t)stream;
-    const AggGeom g{K, first, count, pd, ph, pw, D, H, W};
+    const AggGeom g{K, first, count, pd, ph, pw, D, H, W, flip < 0 ? 0 : flip};
     const double per = (double)pd * ph * pw;
     // logits read, and one read and one write of the covered accumulator (counted as if no two patches of the batch overlapped)
     ProfScope ps(PF_LOSS, 0.0, 12.0 * K * count * per, st);
     const bool vec = pw % 4 == 0 && W % 4 == 0 && ((uintptr_t)logits | (uintptr_t)acc) % 16 == 0;
     const long long items = (long long)count * pd * ph * (vec ? pw / 4 : pw);
     const dim3 grid(agg_grid(items)), block(kAggThreads);
-    if (vec && K <= 4) hipLaunchKernelGGL((aggregate_patches_kernel<4, 4>), grid, block, 0, st, logits, table, g, wz, wy, wx, acc);
-    else if (vec) hipLaunchKernelGGL((aggregate_patches_kernel<kAggMaxK, 4>), grid, block, 0, st, logits, table, g, wz, wy, wx, acc);
-    else if (K <= 4) hipLaunchKernelGGL((aggregate_patches_kernel<4, 1>), grid, block, 0, st, logits, table, g, wz, wy, wx, acc);
-    else hipLaunchKernelGGL((aggregate_patches_kernel<kAggMaxK, 1>), grid, block, 0, st, logits, table, g, wz, wy, wx, acc);
+#define SEG_AGG_LAUNCH(KMAX, V, FLIP) \
+    hipLaunchKernelGGL((aggregate_patches_kernel<KMAX, V, FLIP>), grid, block, 0, st, logits, table, g, wz, wy, wx, acc)
+    if (flip < 0) {
+        if (vec && K <= 4) SEG_AGG_LAUNCH(4, 4, false);
+        else if (vec) SEG_AGG_LAUNCH(kAggMaxK, 4, false);
+        else if (K <= 4) SEG_AGG_LAUNCH(4, 1, false);
+        else SEG_AGG_LAUNCH(kAggMaxK, 1, false);
+    } else {
+        if (vec && K <= 4) SEG_AGG_LAUNCH(4, 4, true);
+        else if (vec) SEG_AGG_LAUNCH(kAggMaxK, 4, true);
+        else if (K <= 4) SEG_AGG_LAUNCH(4, 1, true);
+        else SEG_AGG_LAUNCH(kAggMaxK, 1, true);
+    }
+#undef SEG_AGG_LAUNCH
     SEG_CHECK_LAUNCH();
     return MI355SEG_OK;
+}
+
+int mi355seg_aggregate_patches_f32(const float* logits, int K, const int* table, int first, int count, int pd, int ph, int pw,
+                                   const float* wz, const float* wy, const float* wx, float* acc, int D, int H, int W, void* stream) {
+    return aggregate_patches_launch("aggregate_patches", logits, K, table, first, count, pd, ph, pw, wz, wy, wx, -1, acc, D, H, W, stream);
+}
+
+int mi355seg_aggregate_patches_flip_f32(const float* logits, int K, const int* table, int first, int count, int pd, int ph, int pw,
+                                        const float* wz, const float* wy, const float* wx, int flip, float* acc, int D, int H, int W,
+                                        void* stream) {
+    SEG_CHECK_ARG(flip >= 0 && flip <= 7, "aggregate_patches_flip: flip must lie in 0..7 (bit 2 z, bit 1 y, bit 0 x), got %d", flip);
+    return aggregate_patches_launch("aggregate_patches_flip", logits, K, table, first, count, pd, ph, pw, wz, wy, wx, flip, acc, D, H, W,
+                                    stream);
 }
 
 int mi355seg_aggregate_finalize_f32(const float* acc, int K, int D, int H, int W, const float* sz, const float* sy, const float* sx,

@@ -270,6 +270,23 @@ __global__ __launch_bounds__(256) void gather_patches_kernel(const float* __rest
         out[i] = vol[(((long long)c * D + t[0] + z) * H + t[1] + y) * W + t[2] + x];
     }
 }
+// the same batch read mirrored (test-time augmentation): bit 2 of flip mirrors z inside the patch, bit 1 y, bit 0 x.  A wave still
+// reads whole rows of the volume, in descending x where x is mirrored; the stores stay ascending.
+__global__ __launch_bounds__(256) void gather_patches_flip_kernel(const float* __restrict__ vol, int C, int D, int H, int W, const int* __restrict__ table,
+        int first, int count, int pd, int ph, int pw, int flip, float* __restrict__ out) {
+    const long long per = (long long)C * pd * ph * pw, total = per * count;
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
+        const int b = (int)(i / per);
+        long long r = i - (long long)b * per;
+        const int x = (int)(r % pw); r /= pw;
+        const int y = (int)(r % ph); r /= ph;
+        const int z = (int)(r % pd);
+        const int c = (int)(r / pd);
+        const int mz = flip & 4 ? pd - 1 - z : z, my = flip & 2 ? ph - 1 - y : y, mx = flip & 1 ? pw - 1 - x : x;
+        const int* t = table + (long long)(first + b) * 9;
+        out[i] = vol[(((long long)c * D + t[0] + mz) * H + t[1] + my) * W + t[2] + mx];
+    }
+}
 __global__ __launch_bounds__(256) void paste_labels_kernel(const long long* __restrict__ labels, const int* __restrict__ table, int first, int count,
         int pd, int ph, int pw, long long* __restrict__ out, int D, int H, int W) {
     const long long per = (long long)pd * ph * pw, total = per * count;
@@ -365,6 +382,18 @@ int mi355seg_gather_patches_f32(const float* vol, int C, int D, int H, int W, co
     const long long total = (long long)count * C * pd * ph * pw;
     ProfScope ps(PF_POOL, 0.0, 8.0 * total, (hipStream_t)stream);
     hipLaunchKernelGGL(gather_patches_kernel, dim3(rows_grid(total)), dim3(256), 0, (hipStream_t)stream, vol, C, D, H, W, table, first, count, pd, ph, pw, out);
+    SEG_CHECK_LAUNCH();
+    return MI355SEG_OK;
+}
+int mi355seg_gather_patches_flip_f32(const float* vol, int C, int D, int H, int W, const int* table, int first, int count,
+                                     int pd, int ph, int pw, int flip, float* out, void* stream) {
+    SEG_CHECK_ARG(vol && table && out && C > 0 && count > 0 && first >= 0 && pd > 0 && ph > 0 && pw > 0 && pd <= D && ph <= H && pw <= W,
+                  "gather_patches_flip: bad arguments (patch %dx%dx%d in volume %dx%dx%d)", pd, ph, pw, D, H, W);
+    SEG_CHECK_ARG(flip >= 0 && flip <= 7, "gather_patches_flip: flip must lie in 0..7 (bit 2 z, bit 1 y, bit 0 x), got %d", flip);
+    const long long total = (long long)count * C * pd * ph * pw;
+    ProfScope ps(PF_POOL, 0.0, 8.0 * total, (hipStream_t)stream);
+    hipLaunchKernelGGL(gather_patches_flip_kernel, dim3(rows_grid(total)), dim3(256), 0, (hipStream_t)stream, vol, C, D, H, W, table, first, count,
+                       pd, ph, pw, flip, out);
     SEG_CHECK_LAUNCH();
     return MI355SEG_OK;
 }

@@ -1613,6 +1613,50 @@ def argmax_channels(logits):
 
 OVERLAP_MODES = ("crop", "average", "hann", "gaussian")     # sliding-window aggregation (predict.py); all but "crop" blend probabilities
 MAX_AGGREGATE_CLASSES = 16
+TTA_AXES = ("z", "y", "x")                                   # mirror test-time augmentation: flip code = 4 * z + 2 * y + 1 * x
+
+
+def tta_flip_codes(axes=TTA_AXES):
+    """The flip codes of mirror test-time augmentation over ``axes`` (a non-empty subset of TTA_AXES, no duplicates): the ascending
+    tuple of every code 0..7 whose set bits (4 mirrors z, 2 mirrors y, 1 mirrors x) lie within the chosen axes.  The identity 0 is
+    always first; there are 2, 4 or 8 codes."""
+    axes = (axes,) if isinstance(axes, str) else tuple(axes)
+    if not axes or any(a not in TTA_AXES for a in axes) or len(set(axes)) != len(axes):
+        raise ValueError(f"tta_flip_codes: axes must be a non-empty subset of {TTA_AXES} without duplicates, got {axes!r}")
+    mask = sum(4 >> TTA_AXES.index(a) for a in axes)
+    return tuple(c for c in range(8) if c & ~mask == 0)
+
+
+def _flip_code(flip, what):
+    if isinstance(flip, bool) or not isinstance(flip, int) or not 0 <= flip <= 7:
+        raise Mi355SegError(f"{what}: flip must be an integer in 0..7 (bit 2 mirrors z, bit 1 y, bit 0 x), got {flip!r}")
+    return flip
+
+
+def gather_patches(volume, table, first, count, patch, flip=0):
+    """``count`` grid patches of ``volume`` [C, D, H, W] (fp32, GPU, contiguous), rows ``first`` .. of the int32 window ``table``
+    [P, 9] on the device, as one batch [count, C, pd, ph, pw]; one launch.  ``flip`` (0..7: bit 2 mirrors z, bit 1 y, bit 0 x) reads
+    every patch mirrored inside its window (mi355seg_gather_patches_flip_f32); 0 is mi355seg_gather_patches_f32."""
+    flip = _flip_code(flip, "gather_patches")
+    _require_cuda(volume, "gather_patches volume")
+    if volume.dim() != 4 or volume.dtype != torch.float32 or not volume.is_contiguous():
+        raise Mi355SegError(f"gather_patches: expected a contiguous float32 volume [C, D, H, W], got {volume.dtype} {tuple(volume.shape)}")
+    if not table.is_cuda or table.dtype != torch.int32 or table.dim() != 2 or table.shape[1] != 9 or not table.is_contiguous():
+        raise Mi355SegError("gather_patches: expected the contiguous int32 window table [P, 9] on the GPU")
+    ps = (patch,) * 3 if isinstance(patch, int) else tuple(int(p) for p in patch)
+    C, D, H, W = volume.shape
+    if len(ps) != 3 or any(p < 1 for p in ps):
+        raise Mi355SegError(f"gather_patches: patch must be three positive extents, got {patch!r}")
+    if ps[0] > D or ps[1] > H or ps[2] > W:
+        raise Mi355SegError(f"gather_patches: patch {ps} larger than the volume {(D, H, W)}")
+    if any(isinstance(v, bool) or not isinstance(v, int) for v in (first, count)) or first < 0 or count < 1 or first + count > table.shape[0]:
+        raise Mi355SegError(f"gather_patches: patches {first!r} .. +{count!r} are not rows of a table of {table.shape[0]}")
+    out = torch.empty((count, C) + ps, dtype=torch.float32, device=volume.device)
+    if flip:
+        lib().call("mi355seg_gather_patches_flip_f32", _p(volume), C, D, H, W, _p(table), first, count, ps[0], ps[1], ps[2], flip, _p(out), _stream())
+    else:
+        lib().call("mi355seg_gather_patches_f32", _p(volume), C, D, H, W, _p(table), first, count, ps[0], ps[1], ps[2], _p(out), _stream())
+    return out
 
 
 def _axis_vectors(vectors, extents, device, what):
@@ -1637,12 +1681,16 @@ def _accumulator(acc, what):
     return acc
 
 
-def aggregate_patches(acc, logits, table, first, weights):
+def aggregate_patches(acc, logits, table, first, weights, flip=0):
     """One batch of torchio's GridAggregator.add_batch in a soft mode (predict.py:141), in place: for every patch ``b`` of ``logits``
     [count, K, pd, ph, pw] (fp32, GPU), placed at the origin of row ``first + b`` of the int32 window ``table`` [P, 9] on the device,
     ``acc[k, origin + v] += ((wz[z] * wy[y]) * wx[x]) * softmax(logits[b])[k, v]``.  acc: fp32 [K, D, H, W], zeroed by the caller
     before the first batch; weights: the three per-axis windows (``predict.window_weights``).  Per element the additions happen in
-    ascending patch index, so the result does not depend on how the patches are batched and is bitwise reproducible."""
+    ascending patch index, so the result does not depend on how the patches are batched and is bitwise reproducible.
+    ``flip`` (0..7, as in gather_patches): the logits are those of the mirrored patches and are un-mirrored as they are read
+    (mi355seg_aggregate_patches_flip_f32) -- bitwise the call with ``torch.flip(logits, axes)`` and flip=0; weights and destination
+    keep the un-mirrored coordinates."""
+    flip = _flip_code(flip, "aggregate_patches")
     acc = _accumulator(acc, "aggregate_patches")
     _require_cuda(logits, "aggregate_patches logits")
     if logits.dim() != 5 or logits.shape[0] == 0 or logits.shape[1] != acc.shape[0]:
@@ -1657,8 +1705,12 @@ def aggregate_patches(acc, logits, table, first, weights):
         raise Mi355SegError(f"aggregate_patches: patch {(pd, ph, pw)} larger than the volume {(D, H, W)}")
     wz, wy, wx = _axis_vectors(weights, (pd, ph, pw), acc.device, "aggregate_patches weights")
     logits = logits.contiguous()
-    lib().call("mi355seg_aggregate_patches_f32", _p(logits), K, _p(table), first, count, pd, ph, pw, _p(wz), _p(wy), _p(wx),
-               _p(acc), D, H, W, _stream())
+    if flip:
+        lib().call("mi355seg_aggregate_patches_flip_f32", _p(logits), K, _p(table), first, count, pd, ph, pw, _p(wz), _p(wy), _p(wx),
+                   flip, _p(acc), D, H, W, _stream())
+    else:
+        lib().call("mi355seg_aggregate_patches_f32", _p(logits), K, _p(table), first, count, pd, ph, pw, _p(wz), _p(wy), _p(wx),
+                   _p(acc), D, H, W, _stream())
     return acc
 
 

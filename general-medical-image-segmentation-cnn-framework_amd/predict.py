@@ -23,6 +23,13 @@ weight on the device (csrc/aggregate.hip) and take the argmax afterwards -- torc
 nnU-Net-style Gaussian.  ``config.patch_overlap=oz,oy,ox`` (one number: all three axes; each even and smaller than the patch axis)
 replaces the reference's (4, 4, 36).  ``config.save_probabilities=true`` (needs a blending mode) writes ``{name}_prob.npy``, float32
 [K, D, H, W], beside ``{name}_pred.npy``.  Without the keys nothing changes and no file is added.
+
+``config.tta=mirror`` (optional; absent, empty or ``none``: off) turns on mirror test-time augmentation, which the reference does
+not have (its predict.py:133 calls the model once per patch): every patch is predicted under every combination of flips along
+``config.tta_axes=z,y,x`` (any non-empty subset, default all three: 2, 4 or 8 forwards per patch), the class probabilities are
+un-mirrored and averaged, and the argmax comes last.  The mirrors happen inside the gather and accumulate launches (csrc/api.hip,
+csrc/aggregate.hip); in a blending mode the flips are the outer loop over the grid, in crop mode they are averaged per patch before
+its labels are pasted.  Output files and their columns do not change.
 """
 import csv
 import glob
@@ -130,9 +137,78 @@ def axis_weight_sums(size, patch, overlap, weights):
     return tuple(out)
 
 
+def tta_axis_sums(sums, flips):
+    """The normaliser of a blend that holds ``len(flips)`` predictions of every patch: (F * sz, sy, sx).  F is a power of two, so in
+    any float format (F * sz[z] * sy[y]) * sx[x] is exactly F times the un-augmented normaliser."""
+    sz, sy, sx = sums
+    return len(flips) * sz, sy, sx
+
+
+def check_tta_flips(tta_flips):
+    """``tta_flips`` of sliding_window_predict -> the tuple of flip codes, or None for no augmentation (None or (0,)).  A tuple must be
+    what functional.tta_flip_codes gives for some axes: ascending codes 0..7, the identity first, closed under the axes they use."""
+    if tta_flips is None:
+        return None
+    flips = tuple(tta_flips)
+    if any(isinstance(f, bool) or not isinstance(f, int) or not 0 <= f <= 7 for f in flips):
+        raise ValueError(f"tta_flips must hold integers in 0..7 (bit 2 mirrors z, bit 1 y, bit 0 x), got {tta_flips!r}")
+    mask = 0
+    for f in flips:
+        mask |= f
+    if flips != tuple(c for c in range(8) if c & ~mask == 0):
+        raise ValueError(f"tta_flips must be the ascending codes of every flip combination of some axes (functional.tta_flip_codes), "
+                         f"got {tta_flips!r}")
+    return None if flips == (0,) else flips
+
+
+def _forward(model, x, dtype):
+    with F.autocast(dtype or F.compute_dtype()):
+        if getattr(model, "takes_frequency_bands", False):           # predict.py:128-131 (IS: first output only)
+            from .models.three_d.IS import frequency_bands
+            logits, _ = model(x, *frequency_bands(x, impl=getattr(model, "band_split", "fft")))
+            return logits
+        return model(x)
+
+
+def _predict_tta(model, volume, ps, table, flips, batch_size, dtype, weights, sums, return_probabilities, out):
+    """sliding_window_predict with mirror test-time augmentation; crop mode: ``weights`` is None and ``out`` the zeroed label volume."""
+    from ._lib import lib
+    C, D, H, W = volume.shape
+    P, dev = table.shape[0], volume.device
+    if weights is not None:
+        # the flips are the OUTER loop: per accumulator element the additions happen in (flip, patch) order whatever the batch size
+        acc = None
+        for f in flips:
+            for i in range(0, P, batch_size):
+                nb = min(batch_size, P - i)
+                logits = _forward(model, F.gather_patches(volume, table, i, nb, ps, flip=f), dtype)
+                if acc is None:
+                    acc = torch.zeros((logits.shape[1], D, H, W), dtype=torch.float32, device=dev)
+                F.aggregate_patches(acc, logits.to(torch.float32), table, i, weights, flip=f)
+        return F.aggregate_finalize(acc, tta_axis_sums(sums, flips), probabilities=return_probabilities)
+    # crop mode: the F un-mirrored softmaxes of a batch are summed (ascending flip code) in a buffer that the accumulate kernel sees
+    # as a volume [K, count * pd, ph, pw] -- patch b at origin (b * pd, 0, 0), windows of ones -- then argmax and paste as without TTA
+    L, st = lib(), torch.cuda.current_stream().cuda_stream
+    rows = np.zeros((min(batch_size, P), 9), dtype=np.int32)
+    rows[:, 0] = np.arange(rows.shape[0]) * ps[0]
+    stack = torch.from_numpy(rows).to(dev)
+    ones = [torch.ones(p, dtype=torch.float32, device=dev) for p in ps]
+    for i in range(0, P, batch_size):
+        nb = min(batch_size, P - i)
+        buf = None
+        for f in flips:
+            logits = _forward(model, F.gather_patches(volume, table, i, nb, ps, flip=f), dtype)
+            if buf is None:
+                buf = torch.zeros((logits.shape[1], nb * ps[0], ps[1], ps[2]), dtype=torch.float32, device=dev)
+            F.aggregate_patches(buf, logits.to(torch.float32), stack, 0, ones, flip=f)
+        labels = F.argmax_channels(buf[None])                            # int64 [1, 1, nb * pd, ph, pw]: the batch's label maps in order
+        L.call("mi355seg_paste_labels_i64", labels.data_ptr(), table.data_ptr(), i, nb, ps[0], ps[1], ps[2], out.data_ptr(), D, H, W, st)
+    return out
+
+
 @torch.no_grad()
 def sliding_window_predict(model, volume, patch_size, overlap=(4, 4, 36), batch_size=1, dtype=None, overlap_mode="crop",
-                           return_probabilities=False):
+                           return_probabilities=False, tta_flips=None):
     """volume: float tensor [C, D, H, W] on the GPU -> int64 label volume [1, D, H, W] (argmax over classes).
     ``dtype`` = torch.bfloat16 runs the forward under mi355seg.autocast (``config.mixed_precision=bf16``).
     Device-resident: the window table is uploaded once, each batch is one gather launch (mi355seg_gather_patches_f32), the
@@ -141,12 +217,19 @@ def sliding_window_predict(model, volume, patch_size, overlap=(4, 4, 36), batch_
     ``overlap_mode`` = average | hann | gaussian blends instead: per batch one launch adds the window-weighted softmax of the logits
     into an fp32 accumulator [K, D, H, W] (mi355seg_aggregate_patches_f32, in place of the argmax and the paste), and one launch per
     volume takes the argmax of the blend (mi355seg_aggregate_finalize_f32).  ``return_probabilities`` (blending modes only) returns
-    (labels, prob) with prob fp32 [K, D, H, W], the normalised blend."""
+    (labels, prob) with prob fp32 [K, D, H, W], the normalised blend.
+    ``tta_flips`` (None or (0,): off, the launches above) = functional.tta_flip_codes(axes) predicts every patch under each of the F
+    flip codes and averages the un-mirrored class probabilities before the argmax.  The gather reads the volume mirrored
+    (mi355seg_gather_patches_flip_f32) and the accumulate reads the logits mirrored (mi355seg_aggregate_patches_flip_f32): no flipped
+    copies.  Blending modes: the flips are the outer loop over the whole grid, all into the one accumulator, whose normaliser is
+    F * sz -- the result stays bitwise independent of the batch size.  Crop mode: the F softmaxes of a batch are summed per patch,
+    then argmax and paste as above."""
     from ._lib import lib
     if overlap_mode not in F.OVERLAP_MODES:
         raise ValueError(f"overlap_mode must be one of {F.OVERLAP_MODES}, got {overlap_mode!r}")
     if return_probabilities and overlap_mode == "crop":
         raise ValueError("return_probabilities needs a blending overlap_mode (average, hann or gaussian): 'crop' aggregates labels")
+    flips = check_tta_flips(tta_flips)
     C, D, H, W = volume.shape
     ps = (patch_size,) * 3 if isinstance(patch_size, int) else tuple(patch_size)
     table_h = window_table((D, H, W), ps, overlap)
@@ -164,16 +247,16 @@ def sliding_window_predict(model, volume, patch_size, overlap=(4, 4, 36), batch_
     L, st = lib(), torch.cuda.current_stream().cuda_stream
     was_training = model.training
     model.eval()
+    if flips:
+        res = _predict_tta(model, volume, ps, table, flips, batch_size, dtype, weights if soft else None, sums if soft else None,
+                           return_probabilities, None if soft else out)
+        model.train(was_training)
+        return res
     for i in range(0, P, batch_size):
         nb = min(batch_size, P - i)
         x = torch.empty((nb, C) + ps, dtype=torch.float32, device=dev)
         L.call("mi355seg_gather_patches_f32", volume.data_ptr(), C, D, H, W, table.data_ptr(), i, nb, ps[0], ps[1], ps[2], x.data_ptr(), st)
-        with F.autocast(dtype or F.compute_dtype()):
-            if getattr(model, "takes_frequency_bands", False):           # predict.py:128-131 (IS: first output only)
-                from .models.three_d.IS import frequency_bands
-                logits, _ = model(x, *frequency_bands(x, impl=getattr(model, "band_split", "fft")))
-            else:
-                logits = model(x)
+        logits = _forward(model, x, dtype)
         if soft:
             if acc is None:                                              # K is known once the first batch is through the model
                 acc = torch.zeros((logits.shape[1], D, H, W), dtype=torch.float32, device=dev)
@@ -284,6 +367,24 @@ def parse_save_probabilities(config, overlap_mode):
     return v
 
 
+def parse_tta(config):
+    """``config.tta`` / ``config.tta_axes`` -> the flip codes of mirror test-time augmentation (functional.tta_flip_codes), or None
+    when ``config.tta`` is absent, empty or ``none``.  ``config.tta_axes`` = any non-empty subset of z,y,x without duplicates (default:
+    all three); giving it without ``config.tta=mirror`` is an error."""
+    t, ax = getattr(config, "tta", None), getattr(config, "tta_axes", None)
+    on = not _absent(t)
+    if on and (not isinstance(t, str) or t != "mirror"):
+        raise ValueError(f"config.tta must be mirror or none, got {t!r}")
+    if _absent(ax):
+        return F.tta_flip_codes(F.TTA_AXES) if on else None
+    if not on:
+        raise ValueError(f"config.tta_axes={ax!r} needs config.tta=mirror")
+    parts = [a.strip() for a in ax.strip("()[] ").split(",")] if isinstance(ax, str) else (list(ax) if isinstance(ax, (list, tuple)) else [ax])
+    if not parts or any(a not in F.TTA_AXES for a in parts) or len(set(parts)) != len(parts):
+        raise ValueError(f"config.tta_axes must be a non-empty subset of {','.join(F.TTA_AXES)} without duplicates, got {ax!r}")
+    return F.tta_flip_codes(parts)
+
+
 def write_components_csv(path, rows):
     with open(path, "w", newline="") as fh:
         wr = csv.DictWriter(fh, fieldnames=["file"] + list(COMPONENT_COLUMNS))
@@ -317,6 +418,9 @@ def predict(config, model, log=print):
     overlap = parse_patch_overlap(config, ps) or overlap
     mode = parse_overlap_mode(config)
     save_prob = parse_save_probabilities(config, mode)
+    flips = parse_tta(config)
+    if flips:
+        log(f"tta: mirror, {len(flips)} flips per patch (codes {','.join(str(f) for f in flips)})")
     os.makedirs(config.hydra_path, exist_ok=True)
     if str(config.pred_data_path) == "synthetic":
         g = torch.Generator().manual_seed(7)
@@ -334,7 +438,7 @@ def predict(config, model, log=print):
     for name, x, gt in cases:
         vol = znorm(x.to(device))
         mask = sliding_window_predict(model, vol, ps, overlap, batch_size=max(1, int(config.batch_size)), dtype=mixed_precision_dtype(config),
-                                      overlap_mode=mode, return_probabilities=save_prob)
+                                      overlap_mode=mode, return_probabilities=save_prob, tta_flips=flips)
         if save_prob:
             mask, prob = mask
             np.save(os.path.join(config.hydra_path, f"{name}_prob.npy"), prob.cpu().numpy())

@@ -740,6 +740,13 @@ int mi355seg_gather_patches_f32(const float* vol, int C, int D, int H, int W, co
                                 int pd, int ph, int pw, float* out, void* stream);
 int mi355seg_paste_labels_i64(const int64_t* labels, const int* table, int first, int count, int pd, int ph, int pw,
                               int64_t* out, int D, int H, int W, void* stream);
+/* Mirror test-time augmentation (not in the reference: predict.py:133 calls the model once per patch).  A flip code is an integer
+ * 0..7: bit 2 (value 4) mirrors z, bit 1 (value 2) mirrors y, bit 0 (value 1) mirrors x, inside the patch; m_z(z) = pd-1-z where
+ * the z bit is set, else z, and m_y, m_x likewise.  gather_patches_flip reads the batch mirrored,
+ * out[b,c,z,y,x] = vol[c, oz + m_z(z), oy + m_y(y), ox + m_x(x)], in one launch; flip = 0 gives the bytes of
+ * mi355seg_gather_patches_f32, a flip outside 0..7 is an argument error. */
+int mi355seg_gather_patches_flip_f32(const float* vol, int C, int D, int H, int W, const int* table, int first, int count,
+                                     int pd, int ph, int pw, int flip, float* out, void* stream);
 
 /* Soft aggregation (predict.py:117,141,146: tio.inference.GridAggregator, add_batch, get_output_tensor; the reference keeps
  * the aggregator's default, overlap_mode='crop'; these are its other modes): the class PROBABILITIES of the patches are blended with a
@@ -754,6 +761,16 @@ int mi355seg_paste_labels_i64(const int64_t* labels, const int* table, int first
 int mi355seg_aggregate_patches_f32(const float* logits, int K, const int* table, int first, int count,
                                    int pd, int ph, int pw, const float* wz, const float* wy, const float* wx,
                                    float* acc, int D, int H, int W, void* stream);
+/* The accumulate half of mirror test-time augmentation (flip codes: mi355seg_gather_patches_flip_f32): aggregate_patches with the
+ * softmax taken over logits[b, :, m_z(z), m_y(y), m_x(x)] -- the prediction of a mirrored patch, un-mirrored as it is read.  The
+ * weight (wz[z] * wy[y]) * wx[x] and the destination acc[k, oz+z, oy+y, ox+x] keep the un-mirrored coordinates.  Arithmetic, order,
+ * owner rule and kernel choice are those of mi355seg_aggregate_patches_f32 (a thread that owns four consecutive x loads the
+ * mirrored quad and reverses it in registers), so the result is bitwise that entry point's on logits flipped along the same axes;
+ * flip = 0 gives its bytes.  A caller that adds F flips of every patch into one accumulator hands F * sz to aggregate_finalize.
+ * A flip outside 0..7 is an argument error.  One launch. */
+int mi355seg_aggregate_patches_flip_f32(const float* logits, int K, const int* table, int first, int count,
+                                        int pd, int ph, int pw, const float* wz, const float* wy, const float* wx, int flip,
+                                        float* acc, int D, int H, int W, void* stream);
 /* get_output_tensor of those modes, then predict.py:139's argmax on the blended volume: labels[z,y,x] = argmax_k acc[k] (int64
  * [D,H,W]; first maximum wins, as mi355seg_argmax_ch_f32) and, where prob != NULL, prob[k] = acc[k] / ((sz[z] * sy[y]) * sx[x])
  * (fp32 [K,D,H,W]).  sz[D], sy[H], sx[W]: per axis the sum of the window over the patch origins that cover the coordinate; the
