@@ -539,9 +539,10 @@ def _weight_amax(w):
 
 
 # ----------------------------------------------------------------------------- conv
-# The three passes of a convolution.  These launchers are the only places that name a plain mi355seg_conv3d_{fwd,dgrad,wgrad} entry
-# point (the pro / yamax / bnsums / fused / stem forms have one caller each and stay with it).  fp32 tensors always take the _ax
-# entry: the library defines each plain fp32 entry as exactly that call with NULL maxima (NULL = the pass measures what it needs).
+# The three passes of a convolution, then their fused forms (yamax / pro / folded forward, bnsums input gradient, pro / stem weight
+# gradient).  These launchers are the only places that name a mi355seg_conv3d_* launch; what a fused form computes is in its
+# launcher's docstring.  fp32 tensors always take the _ax entry: the library defines each plain fp32 entry as exactly that call with
+# NULL maxima (NULL = the pass measures what it needs).
 def _sums_ptrs(sums, C):
     """(sum, sum of squares): the two halves of an fp64 [2 * C] buffer a convolution's epilogue reduces its output into."""
     return (None, None) if sums is None else (sums.data_ptr(), sums.data_ptr() + 8 * C)
@@ -581,6 +582,135 @@ def _conv_wgrad(L, g, dy, lddy, x, ldx, dw, db, ws, da=None, xa=None):
         L.call("mi355seg_conv3d_wgrad_bf16", _p(dy), lddy, _p(x), ldx, _p(dw), _p(db), *g, 0, _p(ws), ws.numel(), _stream())
 
 
+def _conv_fwd_yamax(L, g, x, ldx, w, b, y, ldy, ws, sums, xa, wa, ya):
+    """_conv_fwd (fp32 tensors, f16x3) whose epilogue also max-combines max |y| into the zeroed slot ya: what _norm_fold turns into a
+    bound on the maximum of the activation that a norm-prologue convolution behind this one never sees written."""
+    L.call("mi355seg_conv3d_fwd_yamax_ax_f32", _p(x), ldx, _p(w), _p(b), _p(y), ldy, *g, *_sums_ptrs(sums, g.Cout), _p(xa), _p(wa), _p(ya),
+           _p(ws), ws.numel(), _stream())
+
+
+def _conv_fwd_pro(L, g, x, ldx, alpha, beta, act, slope, w, b, y, ldy, ws, sums, xa, wa):
+    """y = conv(act(x * alpha + beta)) + b (fp32 tensors, f16x3): x is the RAW output of the layer in front, normalised (in the folded
+    per-channel form of _norm_fold) and activated while the tiles are staged, so that activation is never written; zero padding stays
+    zero behind the prologue.  xa: a bound on max |act(x * alpha + beta)|."""
+    L.call("mi355seg_conv3d_fwd_pro_ax_f32", _p(x), ldx, _p(alpha), _p(beta), act, slope, _p(w), _p(b), _p(y), ldy, *g,
+           *_sums_ptrs(sums, g.Cout), _p(xa), _p(wa), _p(ws), ws.numel(), _stream())
+
+
+def _conv_fwd_folded(L, g, x, ldx, w, b, gamma, beta, rmean, rvar, eps, act, slope, left_pad, ws):
+    """act(BatchNorm(conv(x) + b)) under running statistics in one pass over x (inference: nothing is kept for a backward): a small launch
+    folds the statistics, the affine parameters and the bias into a per-channel (scale, shift), which the convolution applies with the
+    activation in its epilogue.  Returns the activation, the right channel slice of a concat buffer where left_pad (_concat_out)."""
+    Cout = g.Cout
+    fold = torch.empty(2 * Cout, dtype=torch.float32, device=x.device)
+    L.call("mi355seg_bn_fold_f32", _p(gamma), _p(beta), _p(rmean), _p(rvar), _p(b), eps, Cout, fold.data_ptr(), fold.data_ptr() + 4 * Cout, _stream())
+    _, a, lda = _concat_out(g.out_shape[:4], left_pad, Cout, x.dtype, x.device)
+    L.call("mi355seg_conv3d_fwd_fused_" + _sfx(x), _p(x), ldx, _p(w), fold.data_ptr(), fold.data_ptr() + 4 * Cout, act, slope,
+           a.data_ptr(), lda, *g, _p(ws), ws.numel(), _stream())
+    return a
+
+
+def _conv_dgrad_bnsums(L, g, dy, lddy, w, y_in, mean, rstd, gamma, beta, act, slope, ws, da=None, wa=None):
+    """(dx, sums, dgamma, dbeta) of a convolution g whose input is act(norm(y_in)) with exactly this one consumer (fp32): dx is the input
+    gradient, i.e. d(that activation), and the kernel's epilogue reduces the norm backward's two column sums over it and y_in -- sums,
+    fp32 [2 * Cin], which _norm_act_bwd_apply or _stem_wgrad_bnbwd goes on from -- and the norm's affine gradients, instead of a pass of
+    their own over dx and y_in."""
+    Cin, dev = g.Cin, dy.device
+    dx = torch.empty((g.N, g.D, g.H, g.W, Cin), dtype=dy.dtype, device=dev)
+    sums = torch.empty(2 * Cin, dtype=torch.float32, device=dev)
+    dgamma, dbeta = torch.empty(Cin, dtype=torch.float32, device=dev), torch.empty(Cin, dtype=torch.float32, device=dev)
+    L.call("mi355seg_conv3d_dgrad_bnsums_ax_f32", _p(dy), lddy, _p(w), _p(dx), Cin, *g, _p(y_in), Cin, _p(mean), _p(rstd), _p(gamma), _p(beta),
+           act, slope, sums.data_ptr(), sums.data_ptr() + 4 * Cin, _p(dgamma), _p(dbeta), _p(da), _p(wa), _p(ws), ws.numel(), _stream())
+    return dx, sums, dgamma, dbeta
+
+
+def _conv_wgrad_pro(L, g, dy, lddy, x, ldx, alpha, beta, act, slope, w, ws, da=None, xa=None):
+    """dw of _conv_fwd_pro: the weight gradient against act(x * alpha + beta), formed from the raw x while the tiles are staged.  The
+    form exists under the conv math of its forward only and the entry point refuses under another (the activation the plain form would
+    need was never written): _DoubleConvBnAct.backward runs under the forward's math for that reason."""
+    dw = torch.empty_like(w)
+    L.call("mi355seg_conv3d_wgrad_pro_ax_f32", _p(dy), lddy, _p(x), ldx, _p(alpha), _p(beta), act, slope, _p(dw), None, *g,
+           0, _p(da), _p(xa), _p(ws), ws.numel(), _stream())
+    return dw
+
+
+def _stem_wgrad_bnbwd(L, lay, da, y, mean, rstd, gamma, beta, act, slope, sums, x, w, ws):
+    """(dw, db) of the 1-channel stem ``lay`` behind a norm + activation whose gradient da = d(activation) has ONE consumer, this weight
+    gradient (the stem's input needs none): the kernel forms d(conv output) from da, y and the norm backward's column sums
+    (_conv_dgrad_bnsums) on the fly -- the apply half of the norm backward and the tensor it would write are gone.  db: None without a bias."""
+    g, C = lay.g, lay.g.Cout
+    dw = torch.empty_like(w)
+    db = torch.empty(C, dtype=torch.float32, device=x.device) if lay.has_bias else None
+    L.call("mi355seg_stem_wgrad_bnbwd_f32", _p(da), C, _p(y), C, _p(mean), _p(rstd), _p(gamma), _p(beta), act, slope,
+           sums.data_ptr(), sums.data_ptr() + 4 * C, _p(x), lay.ldx, _p(dw), _p(db), *g, _p(ws), ws.numel(), _stream())
+    return dw, db
+
+
+class _ConvLayer:
+    """What one conv (+ norm) layer of a node keeps for its backward beside the saved tensors: g the _ConvGeom, ldx the input's pitch,
+    has_bias, amax = the f16x3 operand slots (xa, wa) of (input, weight) -- None where the backward hands its convolutions no maxima and
+    draws no slot for max |dy| -- and out_amax, the slot with the maximum of the activation the layer hands on (None: nothing carried)."""
+    __slots__ = ("g", "ldx", "has_bias", "amax", "out_amax")
+
+    def __init__(self, g, ldx, has_bias, amax=None, out_amax=None):
+        self.g, self.ldx, self.has_bias, self.amax, self.out_amax = g, ldx, has_bias, amax, out_amax
+
+
+def _conv_stats_fwd(L, g, x, ldx, w, b, ws, xa_in, ya=None, pro=None):
+    """(y, sums, layer record) of a training-mode conv + BatchNorm layer: y = conv(x) + b with the batch statistics' fp64 column sums
+    (_sums_ptrs) from the convolution's epilogue and the f16x3 operand maxima riding along (xa_in: what x carries).  ya: the yamax form
+    (_conv_fwd_yamax); pro = (alpha, beta, act, slope): the norm-prologue form (_conv_fwd_pro; x is raw, xa_in bounds its activation)."""
+    Cout = g.Cout
+    y = torch.empty(g.out_shape, dtype=x.dtype, device=x.device)
+    sums = torch.empty(2 * Cout, dtype=torch.float64, device=x.device)
+    xa, wa = _operand_amax(g, x, ldx, w, xa_in, True) or (None, None)
+    if _CHECK_AMAX:
+        _assert_amax(w, wa, "conv weights")
+        if pro is not None:              # the bound on the prologue's output against the activation it stands for
+            z = x * pro[0] + pro[1]
+            _assert_amax(torch.where(z > 0, z, z * (pro[3] if pro[2] == ACT_LRELU else 0.0)), xa, "the norm prologue's bound")
+        elif xa is not None:
+            _assert_amax(x, xa, "conv input")
+    if pro is not None:
+        _conv_fwd_pro(L, g, x, ldx, *pro, w, b, y, Cout, ws, sums, xa, wa)
+    elif ya is not None:
+        _conv_fwd_yamax(L, g, x, ldx, w, b, y, Cout, ws, sums, xa, wa, ya)
+    else:
+        _conv_fwd(L, g, x, ldx, w, b, y, Cout, ws, sums, xa, wa)
+    return y, sums, _ConvLayer(g, ldx, b is not None, (xa, wa) if (xa is not None or wa is not None) else None)
+
+
+def _conv_grads(L, lay, dy, lddy, x, w, need_dx, need_dw, ws, da=None, add=None, bias_grad=False):
+    """(dx, dw, db) of the convolution ``lay`` from one dy, each None unless needed; db -- the column sums of dy, from the weight gradient --
+    only with bias_grad (behind a norm the bias gradient comes out of the norm backward).  da: the slot with max |dy| where something
+    carried it; where the layer's passes read maxima (lay.amax), nothing carried dy's and both gradients read it, it is measured here,
+    once.  add = (tensor, ld): a second gradient of x summed into dx, bf16 in the input gradient's epilogue, fp32 by a pass straight after."""
+    g = lay.g
+    xa, wa = lay.amax or (None, None)
+    if lay.amax is not None and da is None and need_dx and need_dw:
+        da = _measure_amax(dy, lddy, g.rows_out, g.Cout)
+    dx = dw = db = None
+    if need_dx:
+        dx = torch.empty(x.shape, dtype=x.dtype, device=x.device)
+        res = add if x.dtype == torch.bfloat16 else None
+        _conv_dgrad(L, g, dy, lddy, w, dx, g.Cin, ws, da, wa, res)
+        if add is not None and res is None:
+            L.call("mi355seg_act_fwd_" + _sfx(x), _p(dx), g.Cin, _p(add[0]), add[1], _p(dx), g.Cin, g.rows_in, g.Cin, ACT_NONE, 0.0, _stream())
+    if need_dw:
+        dw = torch.empty_like(w)
+        db = torch.empty(g.Cout, dtype=torch.float32, device=x.device) if bias_grad and lay.has_bias else None
+        _conv_wgrad(L, g, dy, lddy, x, lay.ldx, dw, db, ws, da, xa)
+    return dx, dw, db
+
+
+def _grads(names, **by_name):
+    """A backward's result: for each forward parameter in ``names`` the gradient given under its name, None for the rest."""
+    out = [None] * len(names)
+    for name, grad in by_name.items():
+        out[names.index(name)] = grad
+    return tuple(out)
+
+
 def _operand_amax(g, x, ldx, w, xa_in, measure_x):
     """The f16x3 operand maxima (xa, wa) that the three passes of the layer g are handed -- or None where none of them reads maxima (bf16
     tensors, the other conv maths, a layer without an f16x3 form).  xa_in: the maximum x carries, if any; it is kept whenever some
@@ -608,6 +738,20 @@ def _stats_from_sums(L, sums, rows, C, eps, running_mean, running_var, momentum)
     return mean, rstd
 
 
+def _norm_fold(L, sums, rows, C, eps, gamma, beta, act, running_mean, running_var, momentum, ya):
+    """(mean, rstd, alpha, shift, bound) by one small launch: _stats_from_sums, the normalisation folded into the per-channel form
+    y * alpha + shift that a norm-prologue convolution applies (_conv_fwd_pro), and -- from ya, the slot with max |y| (_conv_fwd_yamax) --
+    a fresh slot with a bound on max |act(y * alpha + shift)|, the maximum of the activation that is never written."""
+    dev = sums.device
+    mean = torch.empty(C, dtype=torch.float32, device=dev)
+    rstd = torch.empty(C, dtype=torch.float32, device=dev)
+    fold = torch.empty(2 * C, dtype=torch.float32, device=dev)
+    bound = _amax_slot(dev)
+    L.call("mi355seg_norm_fold_f32", *_sums_ptrs(sums, C), rows, C, eps, _p(gamma), _p(beta), act, _p(mean), _p(rstd), _p(running_mean),
+           _p(running_var), momentum, _p(ya), fold.data_ptr(), fold.data_ptr() + 4 * C, _p(bound), _stream())
+    return mean, rstd, fold[:C], fold[C:], bound
+
+
 def _concat_base(t, Cout, lead_shape, dtype):
     """The concat buffer that ``t`` is the right channel slice of -- a contiguous 5-D ``dtype`` tensor of shape lead_shape + (Cout + C_t,)
     with exactly Cout free channels on t's left -- or None if t is no such slice."""
@@ -627,8 +771,8 @@ def _concat_out(lead_shape, left_pad, C, dtype, device):
 
 # ----------------------------------------------------------------------------- norm / activation / pool launchers
 # As for the convolutions: the only places that name a mi355seg_norm_stats_*, rstd_from_var, norm_act_fwd*, norm_act_bwd_colsum*,
-# maxpool2_{fwd,bwd}*, upsample2_bwd_* or act_bwd_* entry point (norm_fold, bn_act_head / bn_act_pool, norm_act_bwd_apply_ax have one caller
-# each and stay with it).  The norm passes always take the widest entry (_ax / _colsum_ax): the library defines the narrower ones as exactly
+# norm_act_bwd_apply*, bn_act_head_*, bn_act_pool_*, maxpool2_{fwd,bwd}*, upsample2_bwd_* or act_bwd_* entry point (norm_fold sits beside
+# _stats_from_sums).  The norm passes always take the widest entry (_ax / _colsum_ax): the library defines the narrower ones as exactly
 # that call with a NULL maximum and / or a NULL column sum.  An optional tensor travels as the pair (tensor, ld) that _opt_view returns.
 _NO_RES = (None, 0)
 _EVAL_BN_BACKWARD = "backward through eval-mode BatchNorm (running statistics) is not supported"
@@ -693,6 +837,91 @@ def _norm_act_bwd(L, dy, lddy, x, ldx, mean, rstd, gamma, beta, res, rows, group
     return dx, dgamma, dbeta, dres, db
 
 
+def _norm_act_bwd_apply(L, dy, lddy, x, mean, rstd, gamma, beta, sums, act, slope, ws, colsum=False, amax=None):
+    """(dx, db): the second half of _norm_act_bwd for a dense fp32 x under batch statistics, where the first half -- the two column sums,
+    ``sums`` fp32 [2 * C], and with them dgamma / dbeta -- came out of another kernel (_conv_dgrad_bnsums).  db: the column sums of dx
+    with ``colsum``, else None; amax: a zeroed slot that receives max |dx|."""
+    C = x.shape[-1]
+    dx = torch.empty_like(x)
+    db = torch.empty(C, dtype=torch.float32, device=x.device) if colsum else None
+    L.call("mi355seg_norm_act_bwd_apply_ax_f32", _p(dy), lddy, _p(x), C, _p(mean), _p(rstd), _p(gamma), _p(beta), None, 0,
+           sums.data_ptr(), sums.data_ptr() + 4 * C, _p(dx), C, None, 0, _p(db), _p(amax), x.numel() // C, 1, C, act, slope, _p(ws), ws.numel(), _stream())
+    return dx, db
+
+
+def _layer_norm_act_bwd(L, lay, da, ldda, y, mean, rstd, gamma, beta, act, slope, ws, amax=None):
+    """(dy, dgamma, dbeta, db) of the norm + activation behind the convolution ``lay`` under batch statistics (_norm_act_bwd over that
+    layer's dense output y): dy = d(conv output), db the convolution's bias gradient (None without a bias)."""
+    g = lay.g
+    dy, dgamma, dbeta, _, db = _norm_act_bwd(L, da, ldda, y, g.Cout, mean, rstd, gamma, beta, _NO_RES, g.rows_out, 1, g.Cout, act, slope, ws,
+                                             lay.has_bias, amax)
+    return dy, dgamma, dbeta, db
+
+
+def _bn_act_head_fwd(L, y, mean, rstd, gamma, beta, act, slope, wh, bh):
+    """The logits head(act(norm(y))) of a 1x1x1 head (weight wh [K, C, 1, 1, 1], bias bh or None) behind a norm + activation, as one
+    kernel over the dense fp32 y (csrc/bn_head.hip): the activation itself is never written."""
+    C, K = y.shape[-1], wh.shape[0]
+    logits = torch.empty(y.shape[:4] + (K,), dtype=y.dtype, device=y.device)
+    L.call("mi355seg_bn_act_head_fwd_f32", _p(y), C, _p(mean), _p(rstd), _p(gamma), _p(beta), act, slope, _p(wh), _p(bh),
+           _p(logits), K, y.numel() // C, C, K, _stream())
+    return logits
+
+
+def _bn_act_head_bwd(L, dlogits, lddl, y, mean, rstd, gamma, beta, act, slope, wh, head_bias, colsum, ws, amax=None):
+    """(dy, dgamma, dbeta, db, dwh, dbh) of _bn_act_head_fwd in two launches: one pass over y and d(logits) for the norm backward's column
+    sums (with them dgamma / dbeta) and the head's weight / bias gradients (dbh: None unless head_bias), a second one for dy with db, its
+    column sums (the bias gradient of the convolution in front; None unless ``colsum``); amax: a zeroed slot that receives max |dy|."""
+    C, K = y.shape[-1], wh.shape[0]
+    rows = y.numel() // C
+    f32 = dict(dtype=torch.float32, device=y.device)
+    dy = torch.empty_like(y)
+    dgamma, dbeta = torch.empty(C, **f32), torch.empty(C, **f32)
+    db = torch.empty(C, **f32) if colsum else None
+    sums = torch.empty(2 * C, **f32)
+    dwh = torch.empty_like(wh)
+    dbh = torch.empty(K, **f32) if head_bias else None
+    L.call("mi355seg_bn_act_head_bwd_sums_f32", _p(dlogits), lddl, _p(y), C, _p(mean), _p(rstd), _p(gamma), _p(beta), act, slope, _p(wh),
+           sums.data_ptr(), sums.data_ptr() + 4 * C, _p(dgamma), _p(dbeta), _p(dwh), _p(dbh), rows, C, K, _p(ws), ws.numel(), _stream())
+    L.call("mi355seg_bn_act_head_bwd_apply_f32", _p(dlogits), lddl, _p(y), C, _p(mean), _p(rstd), _p(gamma), _p(beta), act, slope, _p(wh),
+           sums.data_ptr(), sums.data_ptr() + 4 * C, _p(dy), C, _p(db), _p(amax), rows, C, K, _p(ws), ws.numel(), _stream())
+    return dy, dgamma, dbeta, db, dwh, dbh
+
+
+def _bn_act_pool_fwd(L, y, mean, rstd, gamma, beta, act, slope, left_pad, amax=None):
+    """(a, pooled, idx) as one kernel over the dense fp32 y: a = act(norm(y)) -- the right channel slice of a concat buffer where left_pad
+    (_concat_out) --, pooled = MaxPool3d(2, 2)(a) and the uint8 argmax codes of its windows (_maxpool2_fwd); amax: a zeroed slot that
+    receives max |a|."""
+    N, D, H, W, C = y.shape
+    _, a, lda = _concat_out((N, D, H, W), left_pad, C, y.dtype, y.device)
+    pooled = torch.empty((N, D // 2, H // 2, W // 2, C), dtype=y.dtype, device=y.device)
+    idx = torch.empty((N, D // 2, H // 2, W // 2, C), dtype=torch.uint8, device=y.device)
+    L.call("mi355seg_bn_act_pool_fwd_f32", _p(y), C, _p(mean), _p(rstd), _p(gamma), _p(beta), act, slope, a.data_ptr(), lda,
+           _p(pooled), _p(idx), _p(amax), N, D, H, W, C, _stream())
+    return a, pooled, idx
+
+
+def _bn_act_pool_bwd(L, da, dpooled, idx, y, mean, rstd, gamma, beta, act, slope, colsum, ws, amax=None):
+    """(dy, dgamma, dbeta, db) of _bn_act_pool_fwd: d(activation) = da + pool_backward(dpooled) exists only inside the two passes of the
+    norm backward.  da / dpooled: None for an unused output (its gradient is zero); db: the column sums of dy with ``colsum``, else None;
+    amax: a zeroed slot that receives max |dy|."""
+    N, D, H, W, C = y.shape
+    f32 = dict(dtype=torch.float32, device=y.device)
+    dy = torch.empty_like(y)
+    dgamma, dbeta = torch.empty(C, **f32), torch.empty(C, **f32)
+    db = torch.empty(C, **f32) if colsum else None
+    if da is None:
+        da = torch.zeros(y.shape, **f32)
+    if dpooled is None:
+        dpooled = torch.zeros(idx.shape, **f32)
+    da, ldda = cl_view(_like(da, y), "skip grad")
+    dpooled = dpooled.contiguous()
+    sums = torch.empty(2 * C, **f32)
+    L.call("mi355seg_bn_act_pool_bwd_f32", _p(da), ldda, _p(dpooled), _p(idx), _p(y), C, _p(mean), _p(rstd), _p(gamma), _p(beta), act, slope,
+           sums.data_ptr(), sums.data_ptr() + 4 * C, _p(dgamma), _p(dbeta), _p(dy), C, _p(db), _p(amax), N, D, H, W, C, _p(ws), ws.numel(), _stream())
+    return dy, dgamma, dbeta, db
+
+
 def _act_bwd(dy, lddy, x, ldx, res, rows, C, act, slope, add=None):
     """dx = dy * act'(x [+ res]); add = (tensor, ld): the one-pass form that also sums a second gradient of x in (a NULL tensor adds nothing)."""
     dx = torch.empty(x.shape, dtype=x.dtype, device=x.device)
@@ -743,35 +972,28 @@ class _Conv3d(Function):
                 raise Mi355SegError(f"conv3d: residual {tuple(res.shape)} {res.dtype} does not match the output {tuple(y.shape)} {x.dtype}")
             res = (res, ldres)
         # (a pair without members still says that some pass reads maxima: the backward then measures dy once for its two readers)
-        ctx.amax = _operand_amax(g, x, ldx, w, xa_in, ctx.needs_input_grad[1])
-        xa, wa = ctx.amax or (None, None)
+        amax = _operand_amax(g, x, ldx, w, xa_in, ctx.needs_input_grad[1])
+        xa, wa = amax or (None, None)
         _conv_fwd(L, g, x, ldx, w, b, y, g.Cout, ws, None, xa, wa, res)
         ctx.save_for_backward(x, w)
-        ctx.geom = (g, ldx, b is not None)
+        ctx.layer = _ConvLayer(g, ldx, b is not None, amax)
         ctx.has_res = res is not None
         return y
 
     @staticmethod
     def backward(ctx, dy):
         x, w = ctx.saved_tensors
-        g, ldx, has_b = ctx.geom
+        lay = ctx.layer
         dy, lddy = cl_view(_like(dy, x), "conv3d grad")
         L = lib()
-        ws = workspace(g.ws_bytes(L, x.dtype), x.device)
-        dx = dw = db = None
-        want_dw = ctx.needs_input_grad[1] or (has_b and ctx.needs_input_grad[2])
-        xa, wa = ctx.amax or (None, None)
-        da = _get_amax(dy) if ctx.amax is not None else None
-        if ctx.amax is not None and da is None and ctx.needs_input_grad[0] and want_dw:      # both gradients read dy: measure it once
-            da = _measure_amax(dy, lddy, g.rows_out, g.Cout)
-        if ctx.needs_input_grad[0]:
-            dx = torch.empty(x.shape, dtype=x.dtype, device=x.device)
-            _conv_dgrad(L, g, dy, lddy, w, dx, g.Cin, ws, da, wa)
-        if want_dw:
-            dw = torch.empty_like(w)
-            db = torch.empty(g.Cout, dtype=torch.float32, device=x.device) if has_b else None
-            _conv_wgrad(L, g, dy, lddy, x, ldx, dw, db, ws, da, xa)
-        return dx, dw, db, None, None, (dy if ctx.has_res else None)        # d(conv + res) / d res = dy itself
+        ws = workspace(lay.g.ws_bytes(L, x.dtype), x.device)
+        need_dw = ctx.needs_input_grad[1] or (lay.has_bias and ctx.needs_input_grad[2])
+        da = _get_amax(dy) if lay.amax is not None else None
+        dx, dw, db = _conv_grads(L, lay, dy, lddy, x, w, ctx.needs_input_grad[0], need_dw, ws, da, bias_grad=True)
+        return _grads(_CONV3D_ARGS, x=dx, w=dw, b=db, res=dy if ctx.has_res else None)      # d(conv + res) / d res = dy itself
+
+
+_CONV3D_ARGS = ("x", "w", "b", "stride", "pad", "res")
 
 
 def conv3d(x, weight, bias=None, stride=1, padding=0, residual=None):
@@ -787,6 +1009,17 @@ def conv3d(x, weight, bias=None, stride=1, padding=0, residual=None):
 def _convt_k2s2_ws(L, x, Cout):
     N, D, H, W, Cin = x.shape
     return workspace(L.query("mi355seg_convt3d_k2s2_ws_bytes", N, D, H, W, Cin, Cout), x.device)
+
+
+def _convt_k2s2_fwd(L, x, ldx, w, b, y_ptr, ldy, amax=None):
+    """ConvTranspose3d k2 s2 of x, written at the address y_ptr with voxel pitch ldy (a dense result, or the left channels of a concat
+    buffer); amax (fp32 tensors): a zeroed slot into which the kernel's epilogue max-combines the maximum of what it writes."""
+    N, D, H, W, Cin = x.shape
+    Cout = w.shape[1]
+    ws = _convt_k2s2_ws(L, x, Cout)
+    extra = () if amax is None else (_p(amax),)
+    L.call("mi355seg_convt3d_k2s2_fwd_" + ("ax_f32" if extra else _sfx(x)), _p(x), ldx, _p(w), _p(b), y_ptr, ldy, N, D, H, W, Cin, Cout, *extra,
+           _p(ws), ws.numel(), _stream())
 
 
 def _convt_k2s2_bwd(L, x, ldx, dy, lddy, w, has_b, need_dx, need_dw):
@@ -818,10 +1051,7 @@ class _ConvT3dK2S2(Function):
         Cout = w.shape[1]
         w = w.contiguous()
         y = torch.empty((N, 2 * D, 2 * H, 2 * W, Cout), dtype=x.dtype, device=x.device)
-        L = lib()
-        ws = _convt_k2s2_ws(L, x, Cout)
-        L.call("mi355seg_convt3d_k2s2_fwd_" + _sfx(x), _p(x), ldx, _p(w), _p(b), _p(y), Cout, N, D, H, W, Cin, Cout,
-               _p(ws), ws.numel(), _stream())
+        _convt_k2s2_fwd(lib(), x, ldx, w, b, y.data_ptr(), Cout)
         ctx.save_for_backward(x, w)
         ctx.geom = (ldx, b is not None)
         return y
@@ -849,19 +1079,13 @@ class _ConvT3dK2S2Cat(Function):
         if base is None:
             raise Mi355SegError("conv_transpose3d_k2s2_cat: `skip` is not the right channel slice of a matching concat buffer")
         w = w.contiguous()
-        L = lib()
-        ws = _convt_k2s2_ws(L, x, Cout)
         sa = _get_amax(skip) if _takes_amax(x) else None
+        # max |cat| = max(max |up-convolution| (from that kernel's epilogue), max |skip| (its own scalar, max-combined))
+        ca = _amax_slot(x.device) if sa is not None else None
+        _convt_k2s2_fwd(lib(), x, ldx, w, b, base.data_ptr(), base.shape[-1], ca)
         if sa is not None:
-            # max |cat| = max(max |up-convolution| (from that kernel's epilogue), max |skip| (its own scalar, max-combined))
-            ca = _amax_slot(x.device)
-            L.call("mi355seg_convt3d_k2s2_fwd_ax_f32", _p(x), ldx, _p(w), _p(b), _p(base), base.shape[-1], N, D, H, W, Cin, Cout, _p(ca),
-                   _p(ws), ws.numel(), _stream())
             _measure_amax(sa, 1, 1, 1, ca)
             _set_amax(base, ca)
-        else:
-            L.call("mi355seg_convt3d_k2s2_fwd_" + _sfx(x), _p(x), ldx, _p(w), _p(b), _p(base), base.shape[-1], N, D, H, W, Cin, Cout,
-                   _p(ws), ws.numel(), _stream())
         ctx.save_for_backward(x, w)
         ctx.geom = (Cout, ldx, b is not None)
         return base
@@ -1007,23 +1231,12 @@ class _ConvBnAct(Function):
                 L.query("mi355seg_conv3d_fused_supported_" + _sfx(x), *g, ldx, left_pad + Cout):
             # inference (model.eval() under no_grad, predict.py:79-81,133): eval-mode BatchNorm folded into the packed weights and
             # the bias slot, the activation in the convolution's epilogue -- one pass, nothing saved for a backward
-            fold = torch.empty(2 * Cout, dtype=torch.float32, device=dev)
-            L.call("mi355seg_bn_fold_f32", _p(gamma), _p(beta), _p(rmean), _p(rvar), _p(b), eps, Cout, fold.data_ptr(), fold.data_ptr() + 4 * Cout, _stream())
-            _, a, lda = _concat_out(g.out_shape[:4], left_pad, Cout, x.dtype, dev)
-            L.call("mi355seg_conv3d_fwd_fused_" + _sfx(x), _p(x), ldx, _p(w), fold.data_ptr(), fold.data_ptr() + 4 * Cout, act, slope,
-                   a.data_ptr(), lda, *g, _p(ws), ws.numel(), _stream())
-            return a
-        y = torch.empty(g.out_shape, dtype=x.dtype, device=dev)
-        ax = training and _takes_amax(x)          # f16x3: operand maxima ride along (this layer's input, weights, and its output for the next layer)
-        ctx.amax = None
-        if training:
-            sums = torch.empty(2 * Cout, dtype=torch.float64, device=dev)
-            xa, wa = _operand_amax(g, x, ldx, w, xa_in, True) or (None, None)
-            _conv_fwd(L, g, x, ldx, w, b, y, Cout, ws, sums, xa, wa)
-            if xa is not None or wa is not None:      # (no member: the backward draws no slot for max |dy| either)
-                ctx.amax = (xa, wa)
+            return _conv_fwd_folded(L, g, x, ldx, w, b, gamma, beta, rmean, rvar, eps, act, slope, left_pad, ws)
+        if training:                              # f16x3: operand maxima ride along (this layer's input, weights, and its output for the next layer)
+            y, sums, lay = _conv_stats_fwd(L, g, x, ldx, w, b, ws, xa_in)
             mean, rstd = _stats_from_sums(L, sums, rows, Cout, eps, rmean, rvar, momentum)
         else:
+            y, lay = torch.empty(g.out_shape, dtype=x.dtype, device=dev), _ConvLayer(g, ldx, b is not None)
             _conv_fwd(L, g, x, ldx, w, b, y, Cout, ws)
             mean, rstd = _running_stats(L, rmean, rvar, eps, Cout)
         ctx.cat = 0
@@ -1037,12 +1250,12 @@ class _ConvBnAct(Function):
             # left_pad: the activation lands in the RIGHT channel slice of a wider buffer whose left `left_pad` channels a later
             # up-convolution fills (conv_transpose3d_k2s2_cat): the skip concatenation then costs no copy
             full, a, lda = _concat_out(g.out_shape[:4], left_pad, Cout, x.dtype, dev)
-        aa = _amax_slot(dev) if ax else None
-        _norm_act_fwd(L, y, Cout, mean, rstd, gamma, beta, _NO_RES, a.data_ptr(), lda, rows, 1, Cout, act, slope, aa)
+        lay.out_amax = _amax_slot(dev) if training and _takes_amax(x) else None
+        _norm_act_fwd(L, y, Cout, mean, rstd, gamma, beta, _NO_RES, a.data_ptr(), lda, rows, 1, Cout, act, slope, lay.out_amax)
         if not ctx.cat:
-            _set_amax(a, aa)
+            _set_amax(a, lay.out_amax)
         ctx.save_for_backward(x, w, y, mean, rstd, gamma, beta)
-        ctx.cfg = (g, ldx, b is not None, act, slope, bool(training))
+        ctx.cfg = (lay, act, slope, bool(training))
         if fork:
             ctx.set_materialize_grads(False)
             return a, x_arg.view_as(x_arg)
@@ -1053,39 +1266,31 @@ class _ConvBnAct(Function):
     @staticmethod
     def backward(ctx, da, dpass=None):
         x, w, y, mean, rstd, gamma, beta = ctx.saved_tensors
-        g, ldx, has_b, act, slope, training = ctx.cfg
-        Cin, Cout, rows = g.Cin, g.Cout, g.rows_out
+        lay, act, slope, training = ctx.cfg
+        g, Cout = lay.g, lay.g.Cout
         if not training:
             raise Mi355SegError(_EVAL_BN_BACKWARD)
         if da is None:                       # (fork, only the pass-through was used)
-            return (dpass,) + (None,) * 17
-        if dpass is not None:
-            dpass, lddp = cl_view(_like(dpass, x), "pass-through grad")
+            return _grads(_CONV_BN_ACT_ARGS, x=dpass)
+        add = None if dpass is None else cl_view(_like(dpass, x), "pass-through grad")
         dcat = None
         if ctx.cat:                          # da is the gradient of the whole concat buffer: ours is its left slice, the right one goes back to cat_right
             da = _like(da, x)
             dcat, da = da[..., Cout:], da[..., :Cout]
         da, ldda = cl_view(_like(da, x), "conv+norm grad")
         L = lib()
-        dev = x.device
-        ws = workspace(_conv_norm_ws(L, g, x.dtype, rows, Cout), dev)
-        xa, wa = ctx.amax or (None, None)
-        dya = _amax_slot(dev) if ctx.amax is not None else None       # f16x3: max |dy| from the kernel that writes dy
-        dy, dgamma, dbeta, _, db = _norm_act_bwd(L, da, ldda, y, Cout, mean, rstd, gamma, beta, _NO_RES, rows, 1, Cout, act, slope, ws, has_b, dya)
-        dx = dw = None
-        if ctx.needs_input_grad[0]:
-            dx = torch.empty(x.shape, dtype=x.dtype, device=dev)
-            # input gradient + the pass-through's gradient: bf16 sums in the kernel's epilogue, fp32 by an add of its own
-            res = (dpass, lddp) if dpass is not None and x.dtype == torch.bfloat16 else None
-            _conv_dgrad(L, g, dy, Cout, w, dx, Cin, ws, dya, wa, res)
-            if dpass is not None and res is None:
-                L.call("mi355seg_act_fwd_" + _sfx(x), _p(dx), Cin, _p(dpass), lddp, _p(dx), Cin, g.rows_in, Cin, ACT_NONE, 0.0, _stream())
-        elif dpass is not None:
-            dx = dpass
-        if ctx.needs_input_grad[1]:
-            dw = torch.empty_like(w)
-            _conv_wgrad(L, g, dy, Cout, x, ldx, dw, None, ws, dya, xa)
-        return dx, dw, db, dgamma, dbeta, None, None, None, None, None, None, None, None, None, None, None, None, dcat
+        ws = workspace(_conv_norm_ws(L, g, x.dtype, g.rows_out, Cout), x.device)
+        dya = _amax_slot(x.device) if lay.amax is not None else None       # f16x3: max |dy| from the kernel that writes dy
+        dy, dgamma, dbeta, db = _layer_norm_act_bwd(L, lay, da, ldda, y, mean, rstd, gamma, beta, act, slope, ws, dya)
+        # (the pass-through's gradient is summed into the input gradient; an input that needs none hands it on as it is)
+        dx, dw, _ = _conv_grads(L, lay, dy, Cout, x, w, ctx.needs_input_grad[0], ctx.needs_input_grad[1], ws, dya, add)
+        if dx is None and add is not None:
+            dx = add[0]
+        return _grads(_CONV_BN_ACT_ARGS, x=dx, w=dw, b=db, gamma=dgamma, beta=dbeta, cat_right=dcat)
+
+
+_CONV_BN_ACT_ARGS = ("x", "w", "b", "gamma", "beta", "rmean", "rvar", "stride", "pad", "training", "momentum", "eps", "act", "slope", "left_pad",
+                     "inference", "fork", "cat_right")
 
 
 def conv_in_act(x, conv, norm, act=ACT_NONE, slope=0.01, cat_right=None):
@@ -1127,16 +1332,15 @@ class _DoubleConvBnAct(Function):
     """act(BN2(conv2(act(BN1(conv1(x)))))) -- the double-conv block of unet3d.py:73-104 -- as ONE autograd node (training mode, fp32
     tensors).  Forward is the two fused layers of _ConvBnAct back to back.  Because the activation between the two convolutions
     has exactly one consumer here, the backward can let conv2's input-gradient kernel reduce BN1's two backward column sums in its
-    epilogue (mi355seg_conv3d_dgrad_bnsums_f32) instead of a separate pass over d(act) and y1."""
+    epilogue (_conv_dgrad_bnsums) instead of a separate pass over d(act) and y1."""
 
     @staticmethod
     def forward(ctx, x, w1, b1, g1, be1, rm1, rv1, w2, b2, g2, be2, rm2, rv2, geo1, geo2, mom1, eps1, mom2, eps2, act, slope, left_pad,
                 wh=None, bh=None, pool=False):
-        """wh / bh: the 1x1x1 output head behind the block (unet3d.py:46-48,71).  The node then returns the head's LOGITS: norm2 +
-        activation + head run as one kernel and the block's activation is never written (csrc/bn_head.hip).
-        pool: the MaxPool3d(2, 2) behind an encoder block (unet3d.py:51-58).  The node then returns (pooled, activation): norm2 +
-        activation + pooling are one kernel, and the backward forms d(activation) = d(skip) + pool_backward(d(pooled)) inside the
-        norm backward's two passes."""
+        """wh / bh: the 1x1x1 output head behind the block (unet3d.py:46-48,71).  The node then returns the head's LOGITS
+        (_bn_act_head_fwd); the block's activation is never written.
+        pool: the MaxPool3d(2, 2) behind an encoder block (unet3d.py:51-58).  The node then returns (pooled, activation)
+        (_bn_act_pool_fwd), and the backward forms d(activation) = d(skip) + pool_backward(d(pooled)) inside the norm backward."""
         xa_in = _get_amax(x)
         x, ldx = cl_view(x, "conv3d input")
         L = lib()
@@ -1144,185 +1348,114 @@ class _DoubleConvBnAct(Function):
         ax = _takes_amax(x)           # f16x3: operand maxima ride along
         cg1, w1 = _conv_geom(x, w1, *geo1, "conv3d")
         cg2, w2 = _conv_geom(cg1.out_shape, w2, *geo2, "conv3d")
-
-        def layer(g, inp, ldin, w, b, gm, be, rm, rv, mom, eps, lp, xa, head=None, pool=False, fold=False, pro=None):
-            """conv + batch statistics + (norm + activation).  fold: the norm + activation is NOT applied -- the layer hands back its
-            folded form (al, be) and a bound on the activation's maximum for the next convolution's prologue; pro = (al, be): this
-            convolution's input is the previous layer's RAW output, normalised + activated while its tiles are staged."""
-            N, Do, Ho, Wo, Cout = g.out_shape
-            rows = g.rows_out
-            ws = workspace(_conv_norm_ws(L, g, inp.dtype, rows, Cout), dev)
-            y = torch.empty(g.out_shape, dtype=inp.dtype, device=dev)
-            sums = torch.empty(2 * Cout, dtype=torch.float64, device=dev)
-            aa = None
-            xa, wa = _operand_amax(g, inp, ldin, w, xa, True) or (None, None)
-            ya = _amax_slot(dev) if fold else None
-            if _CHECK_AMAX:
-                _assert_amax(w, wa, "conv weights")
-                if pro is not None:          # the bound on the prologue's output against the activation it stands for
-                    z = inp * pro[0] + pro[1]
-                    _assert_amax(torch.where(z > 0, z, z * (slope if act == ACT_LRELU else 0.0)), xa, "the norm prologue's bound")
-                elif xa is not None:
-                    _assert_amax(inp, xa, "conv input")
-            if pro is not None:
-                L.call("mi355seg_conv3d_fwd_pro_ax_f32", _p(inp), ldin, _p(pro[0]), _p(pro[1]), act, slope, _p(w), _p(b), _p(y), Cout, *g,
-                       *_sums_ptrs(sums, Cout), _p(xa), _p(wa), _p(ws), ws.numel(), _stream())
-            elif fold:
-                L.call("mi355seg_conv3d_fwd_yamax_ax_f32", _p(inp), ldin, _p(w), _p(b), _p(y), Cout, *g,
-                       *_sums_ptrs(sums, Cout), _p(xa), _p(wa), _p(ya), _p(ws), ws.numel(), _stream())
-            else:
-                _conv_fwd(L, g, inp, ldin, w, b, y, Cout, ws, sums, xa, wa)
-            cfg = (g, ldin, b is not None)
-            if fold:                         # statistics + folded normalisation + the bound of the activation's maximum: one small launch
-                mean = torch.empty(Cout, dtype=torch.float32, device=dev)
-                rstd = torch.empty(Cout, dtype=torch.float32, device=dev)
-                alb = torch.empty(2 * Cout, dtype=torch.float32, device=dev)
-                aa = _amax_slot(dev)
-                L.call("mi355seg_norm_fold_f32", *_sums_ptrs(sums, Cout), rows, Cout, eps, _p(gm), _p(be), act,
-                       _p(mean), _p(rstd), _p(rm), _p(rv), mom, _p(ya), alb.data_ptr(), alb.data_ptr() + 4 * Cout, _p(aa), _stream())
-                return y, mean, rstd, (alb[:Cout], alb[Cout:]), cfg, (xa, wa, aa)
-            mean, rstd = _stats_from_sums(L, sums, rows, Cout, eps, rm, rv, mom)
-            if head is not None:             # norm + activation + 1x1x1 head: logits, no activation tensor
-                hw, hb = head
-                K = hw.shape[0]
-                lg = torch.empty((N, Do, Ho, Wo, K), dtype=inp.dtype, device=dev)
-                L.call("mi355seg_bn_act_head_fwd_f32", _p(y), Cout, _p(mean), _p(rstd), _p(gm), _p(be), act, slope, _p(hw), _p(hb),
-                       _p(lg), K, rows, Cout, K, _stream())
-                return y, mean, rstd, lg, cfg, (xa, wa, None)
-            _, a, lda = _concat_out((N, Do, Ho, Wo), lp, Cout, inp.dtype, dev)
-            if ax:
-                aa = _amax_slot(dev)
-            if pool:                         # norm + activation + MaxPool3d(2, 2): the skip tensor, the pooled tensor and the argmax codes
-                pd = torch.empty((N, Do // 2, Ho // 2, Wo // 2, Cout), dtype=inp.dtype, device=dev)
-                idx = torch.empty((N, Do // 2, Ho // 2, Wo // 2, Cout), dtype=torch.uint8, device=dev)
-                L.call("mi355seg_bn_act_pool_fwd_f32", _p(y), Cout, _p(mean), _p(rstd), _p(gm), _p(be), act, slope, a.data_ptr(), lda,
-                       _p(pd), _p(idx), _p(aa), N, Do, Ho, Wo, Cout, _stream())
-                return y, mean, rstd, (a, pd, idx), cfg, (xa, wa, aa)
-            _norm_act_fwd(L, y, Cout, mean, rstd, gm, be, _NO_RES, a.data_ptr(), lda, rows, 1, Cout, act, slope, aa)
-            return y, mean, rstd, a, cfg, (xa, wa, aa)
-
-        head = None
+        C1, C2, rows1, rows2 = cg1.Cout, cg2.Cout, cg1.rows_out, cg2.rows_out
         if wh is not None:
             wh = wh.contiguous()
-            head = (wh, bh)
         # norm1 + activation as a PROLOGUE of conv2 (its forward and its weight gradient read conv1's raw output): where both run the
-        # f16x3 kernels the activation between the two convolutions is never written (mi355seg_conv3d_fwd_pro_ax_f32)
+        # f16x3 kernels the activation between the two convolutions is never written
         fuse1 = ax and not os.environ.get("MI355SEG_NO_PRO_FUSION") and L.query("mi355seg_conv3d_pro_supported_f32", *cg2, act) != 0
-        y1, mean1, rstd1, a1, cfg1, am1 = layer(cg1, x, ldx, w1, b1, g1, be1, rm1, rv1, mom1, eps1, 0, xa_in, fold=fuse1)
-        pro1 = None
+        # layer 1: convolution + statistics, then either the folded norm for conv2's prologue or the activation itself
+        ws = workspace(_conv_norm_ws(L, cg1, x.dtype, rows1, C1), dev)
+        a1 = al1 = bl1 = None
         if fuse1:
-            pro1, a1 = a1, None
-            y2, mean2, rstd2, a2, cfg2, am2 = layer(cg2, y1, cg1.Cout, w2, b2, g2, be2, rm2, rv2, mom2, eps2, left_pad, am1[2], head, pool, pro=pro1)
+            ya1 = _amax_slot(dev)
+            y1, sums1, lay1 = _conv_stats_fwd(L, cg1, x, ldx, w1, b1, ws, xa_in, ya=ya1)
+            mean1, rstd1, al1, bl1, lay1.out_amax = _norm_fold(L, sums1, rows1, C1, eps1, g1, be1, act, rm1, rv1, mom1, ya1)
         else:
-            y2, mean2, rstd2, a2, cfg2, am2 = layer(cg2, a1, a1.shape[-1], w2, b2, g2, be2, rm2, rv2, mom2, eps2, left_pad, am1[2], head, pool)
+            y1, sums1, lay1 = _conv_stats_fwd(L, cg1, x, ldx, w1, b1, ws, xa_in)
+            mean1, rstd1 = _stats_from_sums(L, sums1, rows1, C1, eps1, rm1, rv1, mom1)
+            a1 = torch.empty(cg1.out_shape, dtype=x.dtype, device=dev)
+            lay1.out_amax = _amax_slot(dev) if ax else None
+            _norm_act_fwd(L, y1, C1, mean1, rstd1, g1, be1, _NO_RES, a1.data_ptr(), C1, rows1, 1, C1, act, slope, lay1.out_amax)
+        # layer 2: convolution (of the activation, or of y1 through the prologue) + statistics, then norm + activation (+ head / pool)
+        ws = workspace(_conv_norm_ws(L, cg2, x.dtype, rows2, C2), dev)
+        if fuse1:
+            y2, sums2, lay2 = _conv_stats_fwd(L, cg2, y1, C1, w2, b2, ws, lay1.out_amax, pro=(al1, bl1, act, slope))
+        else:
+            y2, sums2, lay2 = _conv_stats_fwd(L, cg2, a1, C1, w2, b2, ws, lay1.out_amax)
+        mean2, rstd2 = _stats_from_sums(L, sums2, rows2, C2, eps2, rm2, rv2, mom2)
         idx = None
-        if pool:
-            a2, pd, idx = a2
-        ctx.save_for_backward(x, w1, y1, mean1, rstd1, g1, be1, a1, w2, y2, mean2, rstd2, g2, be2, wh, idx,
-                              pro1[0] if fuse1 else None, pro1[1] if fuse1 else None)
-        ctx.cfg = (cfg1, cfg2, act, slope)
-        ctx.amax = (am1, am2)
-        # the prologue form exists under one conv math only: its backward must meet the policy the forward chose (a set_conv_math between
-        # the two would otherwise make the weight gradient's entry point refuse -- the activation it would need was never written)
+        if wh is not None:
+            out = _bn_act_head_fwd(L, y2, mean2, rstd2, g2, be2, act, slope, wh, bh)
+        else:
+            aa = lay2.out_amax = _amax_slot(dev) if ax else None
+            if pool:                         # max |max_pool(a)| <= max |a| (equal for the non-negative outputs of a ReLU)
+                a2, pooled, idx = _bn_act_pool_fwd(L, y2, mean2, rstd2, g2, be2, act, slope, left_pad, aa)
+                out = _set_amax(pooled, aa), _set_amax(a2, aa)
+            else:
+                _, a2, lda2 = _concat_out(cg2.out_shape[:4], left_pad, C2, x.dtype, dev)
+                _norm_act_fwd(L, y2, C2, mean2, rstd2, g2, be2, _NO_RES, a2.data_ptr(), lda2, rows2, 1, C2, act, slope, aa)
+                out = _set_amax(a2, aa)
+        ctx.save_for_backward(x, w1, y1, mean1, rstd1, g1, be1, a1, al1, bl1, w2, y2, mean2, rstd2, g2, be2, wh, idx)
+        ctx.cfg = (lay1, lay2, act, slope)
+        # the math the prologue form ran under: the backward runs under it too (_conv_wgrad_pro exists under no other)
         ctx.math = L.query("mi355seg_get_conv_math") if fuse1 else None
-        ctx.head_bias = head is not None and bh is not None
-        if pool:                             # max |max_pool(a)| <= max |a| (equal for the non-negative outputs of a ReLU)
-            return _set_amax(pd, am2[2]), _set_amax(a2, am2[2])
-        return a2 if head is not None else _set_amax(a2, am2[2])
+        ctx.head_bias = wh is not None and bh is not None
+        return out
 
     @staticmethod
     def backward(ctx, da2, dskip=None):
-        x, w1, y1, mean1, rstd1, g1, be1, a1, w2, y2, mean2, rstd2, g2, be2, wh, idx, al1, bl1 = ctx.saved_tensors
-        (cg1, ldx, has_b1), (cg2, lda1, has_b2), act, slope = ctx.cfg
-        N, D1, H1, W1, Cin1, C1 = cg1.args[:6]
-        _, D2, H2, W2, _, C2 = cg2.args[:6]
-        rows1, rows2 = cg1.rows_out, cg2.rows_out
+        """A prologue-fused block kept no activation between its convolutions, so its backward cannot follow a set_conv_math that came
+        after the forward: ALL of it runs under the forward's math (the maxima in the layer records are that math's), and the policy
+        found is put back."""
+        now = lib().query("mi355seg_get_conv_math") if ctx.math is not None else None
+        if now == ctx.math:
+            return _DoubleConvBnAct._backward(ctx, da2, dskip)
+        lib().call("mi355seg_set_conv_math", ctx.math)
+        try:
+            return _DoubleConvBnAct._backward(ctx, da2, dskip)
+        finally:
+            lib().call("mi355seg_set_conv_math", now)
+
+    @staticmethod
+    def _backward(ctx, da2, dskip):
+        x, w1, y1, mean1, rstd1, g1, be1, a1, al1, bl1, w2, y2, mean2, rstd2, g2, be2, wh, idx = ctx.saved_tensors
+        lay1, lay2, act, slope = ctx.cfg
+        cg1, cg2 = lay1.g, lay2.g
+        C1, C2 = cg1.Cout, cg2.Cout
         L = lib()
         dev = x.device
         if da2 is not None:
             da2, ldda2 = cl_view(_like(da2, x), "conv+norm grad")
-        ws = workspace(max(_conv_norm_ws(L, cg1, x.dtype, rows1, C1), _conv_norm_ws(L, cg2, y1.dtype, rows2, C2),
+        ws = workspace(max(_conv_norm_ws(L, cg1, x.dtype, cg1.rows_out, C1), _conv_norm_ws(L, cg2, y1.dtype, cg2.rows_out, C2),
                            L.query("mi355seg_bn_act_head_ws_bytes", C2, wh.shape[0]) if wh is not None else 0,
                            L.query("mi355seg_bn_act_pool_ws_bytes", C2) if idx is not None else 0), dev)
-        f32 = dict(dtype=torch.float32, device=dev)
-        # layer 2: BatchNorm + activation backward (its dx column sums are conv2's bias gradient)
-        if idx is not None or wh is not None:            # (the plain form's launcher allocates what it returns)
-            dy2 = torch.empty_like(y2)
-            dg2, dbe2 = torch.empty(C2, **f32), torch.empty(C2, **f32)
-            db2 = torch.empty(C2, **f32) if has_b2 else None
-        (xa1, wa1, _), (xa2, wa2, _) = ctx.amax
         # f16x3: the two gradients d(conv output) take their maxima from the norm-backward kernels that write them
-        dya2 = _amax_slot(dev) if (wa2 is not None or xa2 is not None) else None
-        dya1 = _amax_slot(dev) if (wa1 is not None or xa1 is not None) else None
+        dya2 = _amax_slot(dev) if lay2.amax is not None else None
+        dya1 = _amax_slot(dev) if lay1.amax is not None else None
+        xa2, wa2 = lay2.amax or (None, None)
+        # layer 2: norm + activation backward (its dx column sums are conv2's bias gradient); da2 is d(pooled) beside the skip connection's
+        # gradient behind a max-pool, d(logits) behind the head
         dwh = dbh = None
         if idx is not None:
-            # encoder block behind a max-pool: da2 is d(pooled), dskip the skip connection's gradient; d(activation) = dskip +
-            # pool_backward(d(pooled)) exists only inside the two passes of the norm backward
-            if dskip is None:                # (an unused skip output / pooled output: its gradient is zero)
-                dskip = torch.zeros((N, D2, H2, W2, C2), **f32)
-            if da2 is None:
-                da2 = torch.zeros((N, D2 // 2, H2 // 2, W2 // 2, C2), **f32)
-            ds, ldds = cl_view(_like(dskip, x), "skip grad")
-            da2 = da2.contiguous()
-            sp = torch.empty(2 * C2, **f32)
-            L.call("mi355seg_bn_act_pool_bwd_f32", _p(ds), ldds, _p(da2), _p(idx), _p(y2), C2, _p(mean2), _p(rstd2), _p(g2), _p(be2), act, slope,
-                   sp.data_ptr(), sp.data_ptr() + 4 * C2, _p(dg2), _p(dbe2), _p(dy2), C2, _p(db2), _p(dya2), N, D2, H2, W2, C2, _p(ws), ws.numel(), _stream())
+            dy2, dg2, dbe2, db2 = _bn_act_pool_bwd(L, dskip, da2, idx, y2, mean2, rstd2, g2, be2, act, slope, lay2.has_bias, ws, dya2)
         elif wh is not None:
-            # da2 here is d(logits) [rows2, K]: the norm backward's column sums, the head's weight / bias gradients (one pass over
-            # y2 and d(logits)), then dy2 with conv2's bias gradient and its f16x3 maximum (a second pass)
-            K = wh.shape[0]
-            sh = torch.empty(2 * C2, **f32)
-            dwh = torch.empty_like(wh)
-            dbh = torch.empty(K, **f32) if ctx.head_bias else None
-            L.call("mi355seg_bn_act_head_bwd_sums_f32", _p(da2), ldda2, _p(y2), C2, _p(mean2), _p(rstd2), _p(g2), _p(be2), act, slope, _p(wh),
-                   sh.data_ptr(), sh.data_ptr() + 4 * C2, _p(dg2), _p(dbe2), _p(dwh), _p(dbh), rows2, C2, K, _p(ws), ws.numel(), _stream())
-            L.call("mi355seg_bn_act_head_bwd_apply_f32", _p(da2), ldda2, _p(y2), C2, _p(mean2), _p(rstd2), _p(g2), _p(be2), act, slope, _p(wh),
-                   sh.data_ptr(), sh.data_ptr() + 4 * C2, _p(dy2), C2, _p(db2), _p(dya2), rows2, C2, K, _p(ws), ws.numel(), _stream())
+            dy2, dg2, dbe2, db2, dwh, dbh = _bn_act_head_bwd(L, da2, ldda2, y2, mean2, rstd2, g2, be2, act, slope, wh, ctx.head_bias,
+                                                            lay2.has_bias, ws, dya2)
         else:
-            dy2, dg2, dbe2, _, db2 = _norm_act_bwd(L, da2, ldda2, y2, C2, mean2, rstd2, g2, be2, _NO_RES, rows2, 1, C2, act, slope, ws, has_b2, dya2)
-        # conv2 input gradient = d(act1); BN1's two column sums come out of the same kernel
-        da1 = torch.empty((N, D2, H2, W2, C1), dtype=x.dtype, device=dev)
-        s12 = torch.empty(2 * C1, **f32)
-        dg1, dbe1 = torch.empty(C1, **f32), torch.empty(C1, **f32)
-        L.call("mi355seg_conv3d_dgrad_bnsums_ax_f32", _p(dy2), C2, _p(w2), _p(da1), C1, *cg2, _p(y1), C1, _p(mean1), _p(rstd1), _p(g1), _p(be1), act, slope, s12.data_ptr(), s12.data_ptr() + 4 * C1, _p(dg1), _p(dbe1),
-               _p(dya2), _p(wa2), _p(ws), ws.numel(), _stream())
-        dw2 = torch.empty_like(w2)
-        if al1 is not None:                  # conv2 read conv1's raw output through the norm + activation prologue: so does its weight gradient
-            now = L.query("mi355seg_get_conv_math")
-            if now != ctx.math:
-                L.call("mi355seg_set_conv_math", ctx.math)
-            try:
-                L.call("mi355seg_conv3d_wgrad_pro_ax_f32", _p(dy2), C2, _p(y1), C1, _p(al1), _p(bl1), act, slope, _p(dw2), None, *cg2,
-                       0, _p(dya2), _p(xa2), _p(ws), ws.numel(), _stream())
-            finally:
-                if now != ctx.math:
-                    L.call("mi355seg_set_conv_math", now)
+            dy2, dg2, dbe2, db2 = _layer_norm_act_bwd(L, lay2, da2, ldda2, y2, mean2, rstd2, g2, be2, act, slope, ws, dya2)
+        # conv2: its input gradient = d(act1) with BN1's two column sums, then its weight gradient against act1 (written, or the prologue's)
+        da1, s12, dg1, dbe1 = _conv_dgrad_bnsums(L, cg2, dy2, C2, w2, y1, mean1, rstd1, g1, be1, act, slope, ws, dya2, wa2)
+        if al1 is not None:
+            dw2 = _conv_wgrad_pro(L, cg2, dy2, C2, y1, C1, al1, bl1, act, slope, w2, ws, dya2, xa2)
         else:
-            _conv_wgrad(L, cg2, dy2, C2, a1, lda1, dw2, None, ws, dya2, xa2)
+            _, dw2, _ = _conv_grads(L, lay2, dy2, C2, a1, w2, False, True, ws, dya2)
         del dy2
-        # the 1-channel stem whose input needs no gradient (enc1conv1, unet3d.py:80-89): d(conv1 output) has ONE consumer, the stem's weight
-        # gradient, which forms it from d(act1) and y1 on the fly -- the apply pass and the 537-MB tensor it writes are gone
-        if not ctx.needs_input_grad[0] and ctx.needs_input_grad[1] and Cin1 == 1 and \
+        grads = dict(w2=dw2, b2=db2, g2=dg2, be2=dbe2, g1=dg1, be1=dbe1, wh=dwh, bh=dbh)
+        # the 1-channel stem whose input needs no gradient (enc1conv1, unet3d.py:80-89): no apply pass, no d(conv1 output) (537 MB at 128^3)
+        if not ctx.needs_input_grad[0] and ctx.needs_input_grad[1] and cg1.Cin == 1 and \
                 L.query("mi355seg_stem_wgrad_bnbwd_supported_f32", *cg1) != 0:
-            dw1 = torch.empty_like(w1)
-            db1 = torch.empty(C1, **f32) if has_b1 else None
-            L.call("mi355seg_stem_wgrad_bnbwd_f32", _p(da1), C1, _p(y1), C1, _p(mean1), _p(rstd1), _p(g1), _p(be1), act, slope,
-                   s12.data_ptr(), s12.data_ptr() + 4 * C1, _p(x), ldx, _p(dw1), _p(db1), *cg1, _p(ws), ws.numel(), _stream())
-            return (None, dw1, db1, dg1, dbe1, None, None, dw2, db2, dg2, dbe2, None, None) + (None,) * 9 + (dwh, dbh, None)
+            dw1, db1 = _stem_wgrad_bnbwd(L, lay1, da1, y1, mean1, rstd1, g1, be1, act, slope, s12, x, w1, ws)
+            return _grads(_DOUBLE_CONV_BN_ACT_ARGS, w1=dw1, b1=db1, **grads)
         # layer 1: the apply half of the norm backward (+ conv1's bias gradient), then conv1's gradients
-        dy1 = torch.empty_like(y1)
-        db1 = torch.empty(C1, **f32) if has_b1 else None
-        L.call("mi355seg_norm_act_bwd_apply_ax_f32", _p(da1), C1, _p(y1), C1, _p(mean1), _p(rstd1), _p(g1), _p(be1), None, 0,
-               s12.data_ptr(), s12.data_ptr() + 4 * C1, _p(dy1), C1, None, 0, _p(db1), _p(dya1), rows1, 1, C1, act, slope, _p(ws), ws.numel(), _stream())
+        dy1, db1 = _norm_act_bwd_apply(L, da1, C1, y1, mean1, rstd1, g1, be1, s12, act, slope, ws, lay1.has_bias, dya1)
         del da1
-        dx = dw1 = None
-        if ctx.needs_input_grad[0]:
-            dx = torch.empty((N, D1, H1, W1, Cin1), dtype=x.dtype, device=dev)
-            _conv_dgrad(L, cg1, dy1, C1, w1, dx, Cin1, ws, dya1, wa1)
-        if ctx.needs_input_grad[1]:
-            dw1 = torch.empty_like(w1)
-            _conv_wgrad(L, cg1, dy1, C1, x, ldx, dw1, None, ws, dya1, xa1)
-        return (dx, dw1, db1, dg1, dbe1, None, None, dw2, db2, dg2, dbe2, None, None) + (None,) * 9 + (dwh, dbh, None)
+        dx, dw1, _ = _conv_grads(L, lay1, dy1, C1, x, w1, ctx.needs_input_grad[0], ctx.needs_input_grad[1], ws, dya1)
+        return _grads(_DOUBLE_CONV_BN_ACT_ARGS, x=dx, w1=dw1, b1=db1, **grads)
+
+
+_DOUBLE_CONV_BN_ACT_ARGS = ("x", "w1", "b1", "g1", "be1", "rm1", "rv1", "w2", "b2", "g2", "be2", "rm2", "rv2", "geo1", "geo2", "mom1", "eps1", "mom2", "eps2",
+                            "act", "slope", "left_pad", "wh", "bh", "pool")
 
 
 def double_conv_bn_act(x, conv1, bn1, conv2, bn2, act=ACT_NONE, slope=0.01, left_pad=0, head=None, pool=False):

@@ -1,5 +1,6 @@
 """Host logic around the convolution nodes of functional.py (no GPU, the library is never loaded): which Conv3d modules the fused
 entry points refuse, the concat-slot predicate, and the switches that are gone."""
+import inspect
 import os
 import re
 
@@ -67,7 +68,14 @@ def _source(name):
 # norm_stats_from_sums is another entry point, with a launcher of its own (_stats_from_sums)
 LAUNCHERS = {"norm_stats_(?!from_sums)": "_batch_stats", "rstd_from_var": "_running_stats", "norm_act_fwd": "_norm_act_fwd",
              "norm_act_bwd_colsum": "_norm_act_bwd", "maxpool2_fwd": "_maxpool2_fwd", "maxpool2_bwd": "_maxpool2_bwd",
-             "upsample2_bwd": "_upsample2_bwd", "act_bwd_": "_act_bwd"}
+             "upsample2_bwd": "_upsample2_bwd", "act_bwd_": "_act_bwd",
+             # the fused forms of the conv + BatchNorm nodes
+             "conv3d_fwd_pro_ax": "_conv_fwd_pro", "conv3d_fwd_yamax_ax": "_conv_fwd_yamax", "norm_fold_": "_norm_fold",
+             "bn_act_head_fwd": "_bn_act_head_fwd", "bn_act_head_bwd_sums": "_bn_act_head_bwd", "bn_act_head_bwd_apply": "_bn_act_head_bwd",
+             "bn_act_pool_fwd": "_bn_act_pool_fwd", "bn_act_pool_bwd": "_bn_act_pool_bwd",
+             "conv3d_dgrad_bnsums_ax": "_conv_dgrad_bnsums", "conv3d_wgrad_pro_ax": "_conv_wgrad_pro", "stem_wgrad_bnbwd_f32": "_stem_wgrad_bnbwd",
+             "norm_act_bwd_apply_ax": "_norm_act_bwd_apply", "bn_fold_": "_conv_fwd_folded", "conv3d_fwd_fused_": "_conv_fwd_folded",
+             "convt3d_k2s2_fwd": "_convt_k2s2_fwd"}
 
 
 @pytest.mark.parametrize("stem", sorted(LAUNCHERS))
@@ -79,6 +87,16 @@ def test_each_norm_act_pool_entry_is_named_by_its_launcher_alone(stem):
     assert begin < hits[0] < src.index("\n\n\n", begin + 1), f"{pattern} is named outside {LAUNCHERS[stem]}"
     assert not re.search(pattern, _source("custom_ops.py"))
     assert not re.search(r"mi355seg_(norm|maxpool2|upsample2|act)_", _source("custom_ops.py"))
+
+
+@pytest.mark.parametrize("node,names", [(F._Conv3d, F._CONV3D_ARGS), (F._ConvBnAct, F._CONV_BN_ACT_ARGS),
+                                        (F._DoubleConvBnAct, F._DOUBLE_CONV_BN_ACT_ARGS)], ids=lambda v: getattr(v, "__name__", ""))
+def test_backward_results_are_named_after_the_forward_parameters(no_library, node, names):
+    """A node's backward fills its result by parameter name (F._grads): the name list must be forward's parameters after ctx, in order."""
+    assert list(names) == list(inspect.signature(node.forward).parameters)[1:]
+    assert F._grads(names, **{names[0]: 1, names[-1]: 2}) == (1,) + (None,) * (len(names) - 2) + (2,)
+    with pytest.raises(ValueError):
+        F._grads(names, no_such_parameter=1)
 
 
 def test_concat_out_is_the_slice_concat_base_recognises():

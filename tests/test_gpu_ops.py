@@ -1269,3 +1269,152 @@ def test_layer_norm_fork_sums_both_gradients_in_the_norm_backward(seg):
     _, p2 = F.layer_norm_fork(x2, gg.detach(), bg.detach(), 1e-6)
     (p2 * g2.cuda()).sum().backward()
     assert torch.equal(x2.grad.cpu(), g2)
+
+
+# ---- branches of the conv+BatchNorm nodes (functional._ConvBnAct, _DoubleConvBnAct) that no whole-network step reaches
+def _double_block(c0, c1, c2, seed=3):
+    """(conv1, bn1, conv2, bn2, their eight parameters) of a double-conv block in training mode, with non-trivial affine parameters."""
+    from mi355seg.layers import BatchNorm3d, Conv3d
+    torch.manual_seed(seed)
+    conv1, bn1, conv2, bn2 = Conv3d(c0, c1, 3, padding=1).cuda(), BatchNorm3d(c1).cuda(), Conv3d(c1, c2, 3, padding=1).cuda(), BatchNorm3d(c2).cuda()
+    with torch.no_grad():
+        bn1.weight.copy_(1 + 0.3 * torch.randn(c1)); bn1.bias.copy_(0.5 * torch.randn(c1))
+        bn2.weight.copy_(1 + 0.3 * torch.randn(c2)); bn2.bias.copy_(0.2 * torch.randn(c2))
+    return conv1, bn1, conv2, bn2, [conv1.weight, conv1.bias, bn1.weight, bn1.bias, conv2.weight, conv2.bias, bn2.weight, bn2.bias]
+
+
+BLOCK_GRADS = ["x", "w1", "b1", "g1", "be1", "w2", "b2", "g2", "be2"]
+
+
+def _block_backward(params, x, outputs, x_grad=True):
+    """[dx, dw1, db1, dg1, dbe1, dw2, db2, dg2, dbe2] of ``outputs(xi)`` = (tensors, their gradients) for a fresh leaf xi of the values x."""
+    for p in params:
+        p.grad = None
+    xi = x.clone().requires_grad_(x_grad)
+    torch.autograd.backward(*outputs(xi))
+    torch.cuda.synchronize()
+    return [xi.grad.clone() if x_grad else None] + [p.grad.clone() for p in params]
+
+
+@pytest.mark.parametrize("left_pad", [0, 32])
+def test_pooled_double_conv_with_one_output_unused(seg, left_pad, monkeypatch):
+    """double_conv_bn_act(..., pool=True) returns (pooled, skip) from one node.  A backward through one of the two only must give every
+    gradient bit for bit as the same backward with an explicit all-zero gradient for the other output."""
+    F = seg.functional
+    monkeypatch.delenv("MI355SEG_NO_PRO_FUSION", raising=False)
+    N, D, H, W, C = 2, 8, 8, 16, 32
+    assert seg.lib().query("mi355seg_bn_act_pool_supported_f32", N, D, H, W, C, C) != 0
+    conv1, bn1, conv2, bn2, params = _double_block(C, C, C)
+    x = (rnd(N, D, H, W, C, seed=5) * 1.3).cuda()
+    gp, gs = rnd(N, D // 2, H // 2, W // 2, C, seed=6).cuda(), rnd(N, D, H, W, C, seed=7).cuda()
+
+    def run(gp, gs):
+        def outputs(xi):
+            pooled, skip = F.double_conv_bn_act(xi, conv1, bn1, conv2, bn2, F.ACT_RELU, left_pad=left_pad, pool=True)
+            assert pooled.grad_fn is skip.grad_fn and "DoubleConvBnAct" in type(pooled.grad_fn).__name__
+            assert tuple(pooled.shape) == (N, D // 2, H // 2, W // 2, C) and tuple(skip.shape) == (N, D, H, W, C) and skip.stride(3) == left_pad + C
+            used = [(o, g) for o, g in ((pooled, gp), (skip, gs)) if g is not None]
+            return [o for o, _ in used], [g for _, g in used]
+        return _block_backward(params, x, outputs)
+
+    for alone, zeros in ((run(gp, None), run(gp, torch.zeros_like(gs))), (run(None, gs), run(torch.zeros_like(gp), gs))):
+        for name, a, b in zip(BLOCK_GRADS, alone, zeros):
+            assert torch.equal(a, b), name
+
+
+def test_prologue_fused_block_backward_after_a_conv_math_switch(seg, monkeypatch):
+    """The norm-prologue form of the double-conv block exists under f16x3 only and its weight gradient needs the policy its forward ran
+    under, so the node's whole backward runs under it.  set_conv_math("fp32") between forward and backward: every gradient is bit for
+    bit that of the run without the switch, and the library reports fp32 afterwards (the node restores what it found)."""
+    F, L = seg.functional, seg.lib()
+    monkeypatch.delenv("MI355SEG_NO_PRO_FUSION", raising=False)
+    N, D, H, W, C = 2, 8, 8, 16, 32
+    seg.set_conv_math("f16x3")
+    if L.query("mi355seg_conv3d_pro_supported_f32", N, D, H, W, C, C, 3, 1, 1, F.ACT_RELU) == 0:
+        pytest.skip("the library has no norm-prologue convolution for this shape")
+    conv1, bn1, conv2, bn2, params = _double_block(C, C, C)
+    x = (rnd(N, D, H, W, C, seed=5) * 1.3).cuda()
+    g = rnd(N, D, H, W, C, seed=6).cuda()
+
+    def run(switch):
+        def outputs(xi):
+            y = F.double_conv_bn_act(xi, conv1, bn1, conv2, bn2, F.ACT_RELU)
+            if switch:
+                seg.set_conv_math("fp32")
+            return [y], [g]
+        seg.set_conv_math("f16x3")
+        return _block_backward(params, x, outputs)
+
+    try:
+        plain = run(False)
+        switched = run(True)
+        assert seg.get_conv_math() == "fp32"
+    finally:
+        seg.set_conv_math(DEFAULT_MATH)
+    for name, a, b in zip(BLOCK_GRADS, switched, plain):
+        print(f"{name}: max |switched - plain| = {float((a - b).abs().max()):.3e} of max {float(b.abs().max()):.3e}")
+    for name, a, b in zip(BLOCK_GRADS, switched, plain):
+        assert torch.equal(a, b), name
+
+
+def test_double_conv_stem_arm_matches_the_apply_arm(seg, monkeypatch):
+    """A 1-channel first convolution whose input needs no gradient takes mi355seg_stem_wgrad_bnbwd_f32 (the norm backward's apply half
+    inside the weight gradient); with x.requires_grad the block takes norm_act_bwd_apply + the plain gradients.  dw1 / db1 agree within
+    the bounds of test_stem_weight_gradient_with_norm_backward_prologue (its first case is this shape), everything else bit for bit."""
+    F, L = seg.functional, seg.lib()
+    monkeypatch.delenv("MI355SEG_NO_PRO_FUSION", raising=False)
+    N, D, H, W, C = 2, 8, 8, 32, 32
+    assert L.query("mi355seg_stem_wgrad_bnbwd_supported_f32", N, D, H, W, 1, C, 3, 1, 1) == 1
+    conv1, bn1, conv2, bn2, params = _double_block(1, C, C)
+    x = (rnd(N, D, H, W, 1, seed=5) * 1.3).cuda()
+    g = rnd(N, D, H, W, C, seed=6).cuda()
+    block = lambda xi: ([F.double_conv_bn_act(xi, conv1, bn1, conv2, bn2, F.ACT_RELU)], [g])
+    stem = _block_backward(params, x, block, x_grad=False)
+    apply = _block_backward(params, x, block, x_grad=True)
+    # max |d(conv1 output)| from the unfused chain: convolution, norm + activation, then the second layer
+    kept = []
+
+    def chain(xi):
+        y1 = F.conv3d(xi, conv1.weight, conv1.bias, 1, 1)
+        y1.retain_grad()
+        kept.append(y1)
+        a1 = F.batch_norm_act(y1, bn1.weight, bn1.bias, bn1.running_mean, bn1.running_var, True, bn1.momentum, bn1.eps, act=F.ACT_RELU)
+        return [F.conv_bn_act(a1, conv2, bn2, F.ACT_RELU)], [g]
+    _block_backward(params, x, chain)
+    dy_max = float(kept[0].grad.abs().max())
+    named = dict(zip(BLOCK_GRADS, zip(stem, apply)))
+    dw_s, dw_a = named.pop("w1")
+    db_s, db_a = named.pop("b1")
+    named.pop("x")
+    print(f"dw1: {float((dw_s - dw_a).abs().max()):.3e} of {float(dw_a.abs().max()):.3e}; db1: {float((db_s - db_a).abs().max()):.3e}, max |dy| {dy_max:.3e}")
+    assert (dw_s - dw_a).abs().max() < 2e-5 * max(1e-6, float(dw_a.abs().max()))
+    assert (db_s - db_a).abs().max() < 2e-4 * max(1e-6, dy_max) + 1e-5
+    for name, (a, b) in named.items():
+        assert torch.equal(a, b), name
+
+
+def test_conv_bn_act_fork_with_only_the_pass_through_used(seg):
+    """conv_bn_act(..., fork=True) returns (act(bn(conv(x))), x).  When only the pass-through is used the input gradient is the upstream
+    gradient itself and the backward launches nothing of the library's."""
+    import ctypes
+    F, L = seg.functional, seg.lib()
+    from mi355seg.layers import BatchNorm3d, Conv3d
+    torch.manual_seed(3)
+    conv, bn = Conv3d(8, 8, 3, padding=1).cuda(), BatchNorm3d(8).cuda()
+    x = rnd(1, 4, 8, 8, 8, seed=5).cuda().requires_grad_(True)
+    g = rnd(1, 4, 8, 8, 8, seed=6).cuda()
+    a, xp = F.conv_bn_act(x, conv, bn, F.ACT_RELU, fork=True)
+    assert "ConvBnAct" in type(xp.grad_fn).__name__ and xp.grad_fn is a.grad_fn
+    torch.cuda.synchronize()
+    L.call("mi355seg_prof_reset")
+    L.call("mi355seg_prof_enable", 1)
+    try:
+        xp.backward(g)
+        buf = (ctypes.c_double * 32)()
+        L.call("mi355seg_prof_read", buf, 32)
+        rec, n = (ctypes.c_double * (4 * 64))(), ctypes.c_int(-1)
+        L.call("mi355seg_prof_records", rec, 64, ctypes.byref(n))
+    finally:
+        L.call("mi355seg_prof_enable", 0)
+    assert n.value == 0
+    assert torch.equal(x.grad, g) and conv.weight.grad is None and bn.weight.grad is None
