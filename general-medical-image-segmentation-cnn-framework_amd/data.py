@@ -12,6 +12,9 @@ import os
 import numpy as np
 import torch
 
+from .intensity import (NYUL_PERCENTILES, host_masked, landmarks_from_percentiles, normalize_intensity_host, parse_intensity,
+                        refuse_for_training)
+
 
 def _require_device(device, what, option="aug=True resamples with the HIP kernels of csrc/augment.hip"):
     if torch.device(device).type != "cuda":
@@ -222,8 +225,10 @@ class DevicePatchQueue:
     valid patch centres.  With ``sampler="uniform"`` (the default) nothing changes."""
 
     def __init__(self, data_path, gt_path, patch_size, batch_size, iters, device, seed=1234, queue_length=10,
-                 samples_per_volume=10, cache_gb=200.0, aug=False, sampler="uniform", label_probabilities=None):
+                 samples_per_volume=10, cache_gb=200.0, aug=False, sampler="uniform", label_probabilities=None, intensity=None):
         self.aug = bool(aug)
+        refuse_for_training(intensity, self.aug, data_path)
+        self.intensity = intensity
         if sampler not in ("uniform", "label"):
             raise ValueError(f"DevicePatchQueue: unknown sampler='{sampler}' (expected 'uniform' or 'label')")
         self.sampler = sampler
@@ -265,6 +270,12 @@ class DevicePatchQueue:
             raise ValueError(f"{f}: volume {tuple(x.shape[1:])} is smaller than the patch {self.ps}")
         if self.aug:                                      # raw: bias field, z-normalisation and noise ride in the sampling kernel
             x, y = x.contiguous(), y.contiguous()
+        elif self.intensity is not None:                  # config.intensity: percentiles / moments / one map pass (csrc/intensity.hip)
+            if x.is_cuda:
+                from . import functional as F
+                x = F.normalize_intensity(x, self.intensity)
+            else:                                         # CPU plumbing tests only: the same definitions in numpy fp64
+                x = torch.from_numpy(normalize_intensity_host(x.numpy(), self.intensity))
         elif x.is_cuda:                                   # one fused statistics pass + one apply pass (HIP)
             from . import functional as F
             x = F.znormalize(x)
@@ -361,6 +372,8 @@ def make_loader(config, device, in_channels, seed=1234):
     aug = bool(getattr(config, "aug", False))             # conf/config.yaml:27; dataloader.py:69
     sampler = str(getattr(config, "sampler", "uniform"))
     label_probabilities = parse_label_probabilities(getattr(config, "label_probabilities", None))
+    intensity = parse_intensity(config)                   # config.intensity and its companions; None: the z-score of today
+    refuse_for_training(intensity, aug, config.data_path)
     if str(config.data_path) == "synthetic":
         if sampler != "uniform":
             raise ValueError(f"config.sampler={sampler} needs volumes to sample from: with data_path=synthetic every sample is its own "
@@ -369,4 +382,22 @@ def make_loader(config, device, in_channels, seed=1234):
     return DevicePatchQueue(config.data_path, config.gt_path, config.patch_size, config.batch_size, iters, device, seed,
                             queue_length=int(getattr(config, "queue_length", 10)),
                             samples_per_volume=int(getattr(config, "samples_per_volume", 10)), aug=aug, sampler=sampler,
-                            label_probabilities=label_probabilities)
+                            label_probabilities=label_probabilities, intensity=intensity)
+
+
+def train_landmarks(files, mask="none", device="cuda"):
+    """Nyul landmark training for ``config.intensity=histogram`` (tio.HistogramStandardization.train, UNPINNED): per ``.npy`` volume
+    the percentiles (1, 10, 20, ..., 90, 99) of its masked voxels (``mask``: ``none``, ``mean`` or a number, as
+    ``config.intensity_mask``), rescaled affinely so p[0] -> 0 and p[10] -> 100, averaged over the volumes in fp64 -> float64[11].
+    On a cuda device the percentiles come from the radix select (``functional.volume_percentiles``); on ``cpu`` from
+    ``np.percentile`` (plumbing tests)."""
+    per_volume = []
+    for f in files:
+        v = np.ascontiguousarray(np.load(f), dtype=np.float32)
+        if torch.device(device).type == "cuda":
+            from . import functional as F
+            x = F.aligned_contiguous(torch.from_numpy(v).to(device))
+            per_volume.append(F.volume_percentiles(x, NYUL_PERCENTILES, mask))
+        else:
+            per_volume.append(np.percentile(host_masked(v, mask, f"train_landmarks {f}"), np.asarray(NYUL_PERCENTILES)))
+    return landmarks_from_percentiles(per_volume)

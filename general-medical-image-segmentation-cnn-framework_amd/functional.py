@@ -2242,6 +2242,126 @@ def znormalize(x):
     return y
 
 
+PERCENTILES_MAX = 16            # MI355SEG_PERCENTILES_MAX: percentiles per call
+Percentiles = collections.namedtuple("Percentiles", "values order counts")
+
+
+def _mask_args(mask_gt):
+    return (0, 0.0) if mask_gt is None else (1, float(mask_gt))
+
+
+def percentiles(x, qs, mask_gt=None):
+    """Exact percentiles of one volume on the device (csrc/intensity.hip, radix select): ``np.percentile(v, qs)`` (method ``linear``)
+    of v = every voxel of ``x``, or with ``mask_gt`` the voxels with ``x > mask_gt``.  Returns device tensors, without synchronising:
+    ``values`` float64 [nq], the interpolated percentiles; ``order`` float32 [nq, 2], the two order statistics behind each (exact
+    voxel values, at the ranks floor(q / 100 * (m - 1)) and that + 1 clamped to m - 1); ``counts`` int64 [2] = (m, the number of
+    non-finite voxels).  ``x``: float32, contiguous and 16-byte aligned (a misaligned view is refused, not copied), fewer than 2^31
+    elements; at most 16 percentiles per call, each in 0 .. 100."""
+    _require_cuda(x, "percentiles input")
+    if not x.is_contiguous() or x.numel() < 1:
+        raise Mi355SegError(f"percentiles: expected a contiguous, non-empty volume, got shape {tuple(x.shape)} strides {x.stride()}")
+    q = np.ascontiguousarray(np.asarray(qs, dtype=np.float64).reshape(-1))
+    L = lib()
+    ws = workspace(L.query("mi355seg_percentiles_ws_bytes", x.numel()), x.device)
+    values = torch.empty(max(q.size, 1), dtype=torch.float64, device=x.device)
+    order = torch.empty((max(q.size, 1), 2), dtype=torch.float32, device=x.device)
+    counts = torch.empty(2, dtype=torch.int64, device=x.device)
+    use, t = _mask_args(mask_gt)
+    L.call("mi355seg_percentiles_f32", _p(x), x.numel(), q.ctypes.data, int(q.size), use, t, _p(values), _p(order), _p(counts), _p(ws),
+           ws.numel(), _stream())
+    return Percentiles(values, order, counts)
+
+
+def _map_args(imap):
+    kx, ky, slope, lo, hi = imap.f32()
+    return (kx, ky, slope), (kx.ctypes.data, ky.ctypes.data, slope.ctypes.data, int(kx.size), lo, hi)
+
+
+def intensity_moments(x, imap, mask_gt=None, pivot=0.0):
+    """Count, mean and unbiased variance of ``imap(x)`` over the voxels with ``x > mask_gt`` (the RAW x; every voxel without a mask):
+    float64 [4] on the device = (count, mean, variance, sum of imap(x) - pivot), fp64 sums pivoted on ``pivot`` (any value near the
+    mapped data keeps them well conditioned).  ``imap``: an ``intensity.IntensityMap`` (``intensity.IDENTITY`` for the raw voxels)."""
+    _require_cuda(x, "intensity_moments input")
+    if not x.is_contiguous() or x.numel() < 1:
+        raise Mi355SegError(f"intensity_moments: expected a contiguous, non-empty volume, got shape {tuple(x.shape)}")
+    L = lib()
+    ws = workspace(L.query("mi355seg_intensity_moments_ws_bytes", x.numel()), x.device)
+    out = torch.empty(4, dtype=torch.float64, device=x.device)
+    keep, args = _map_args(imap)
+    L.call("mi355seg_intensity_moments_f32", _p(x), x.numel(), *args, *_mask_args(mask_gt), float(pivot), _p(out), _p(ws), ws.numel(), _stream())
+    return out
+
+
+def intensity_map(x, imap, out=None):
+    """``imap`` (an ``intensity.IntensityMap``) applied to every voxel of ``x`` in one streaming pass; ``out=x`` maps in place."""
+    _require_cuda(x, "intensity_map input")
+    if not x.is_contiguous() or x.numel() < 1:
+        raise Mi355SegError(f"intensity_map: expected a contiguous, non-empty volume, got shape {tuple(x.shape)}")
+    y = torch.empty_like(x) if out is None else out
+    if y.shape != x.shape or y.dtype != x.dtype or y.device != x.device or not y.is_contiguous():
+        raise Mi355SegError(f"intensity_map: out must be a contiguous float32 tensor of x's shape on its device, got {tuple(y.shape)} {y.dtype}")
+    keep, args = _map_args(imap)
+    lib().call("mi355seg_intensity_map_f32", _p(x), x.numel(), *args, _p(y), _stream())
+    return y
+
+
+def intensity_mask_gt(x, mask):
+    """``config.intensity_mask`` -> the threshold of the mask ``x > T`` (``None`` for no mask): ``mean`` is the mean of all voxels from
+    a device reduction, rounded to fp32; a number is rounded to fp32."""
+    if mask == "none":
+        return None
+    if mask != "mean":
+        return float(np.float32(mask))
+    from .intensity import IDENTITY
+    x0 = float(x.view(-1)[0])
+    mean = float(intensity_moments(x, IDENTITY, pivot=x0)[1]) if np.isfinite(x0) else float("nan")
+    if not np.isfinite(mean):
+        raise ValueError("intensity: the volume holds non-finite voxels (NaN or infinity); clean the data first")
+    return float(np.float32(mean))
+
+
+def volume_percentiles(x, qs, mask="none"):
+    """``np.percentile`` of the masked voxels of ``x`` (``mask``: ``none``, ``mean`` or a threshold, as ``config.intensity_mask``) as
+    float64 on the HOST (one device-to-host copy per 16 percentiles), after the checks of ``normalize_intensity``: no non-finite
+    voxel, at least two voxels under the mask."""
+    from .intensity import check_counts
+    t = intensity_mask_gt(x, mask)
+    qs = list(qs)
+    vals = []
+    for i in range(0, len(qs), PERCENTILES_MAX):
+        r = percentiles(x, qs[i:i + PERCENTILES_MAX], t)
+        m, nonfinite = (int(c) for c in r.counts.cpu())
+        check_counts(m, nonfinite)
+        vals.append(r.values.cpu().numpy())
+    return np.concatenate(vals)
+
+
+def normalize_intensity(x, spec, landmarks=None):
+    """One volume through ``config.intensity`` on the device: ``spec`` an ``intensity.IntensitySpec`` (``intensity.parse_intensity``;
+    the definitions of every mode and mask are in that module's docstring), ``landmarks`` replaces ``spec.landmarks``.  All elements
+    of ``x`` are one volume, as ``znormalize``.  Percentiles (radix select) and moments come from the device, the map's knots are
+    formed on the host in fp64 (``intensity.build_map``), and ONE streaming pass writes the result.  Raises ``Mi355SegError`` for a CPU
+    tensor and ``ValueError`` for a non-finite voxel, a mask that leaves fewer than two voxels, a zero range or a zero deviation."""
+    from .intensity import IntensitySpec, build_map
+    if not isinstance(spec, IntensitySpec):
+        raise TypeError(f"normalize_intensity: spec must be an intensity.IntensitySpec, got {type(spec).__name__}")
+    _require_cuda(x, "normalize_intensity input")
+    if landmarks is not None:
+        spec = IntensitySpec(spec.mode, spec.percentiles, spec.out, spec.mask, landmarks)
+    x = aligned_contiguous(x.to(torch.float32))
+    if x.numel() < 2:
+        raise ValueError(f"intensity: the volume holds {x.numel()} voxels, the statistics need at least 2")
+    t = intensity_mask_gt(x, spec.mask)
+
+    def moments(imap):
+        pivot = float(imap(float(x.view(-1)[0])))
+        c, mean, var, _ = intensity_moments(x, imap, t, pivot).cpu().tolist()
+        return c, mean, var
+
+    imap = build_map(spec, lambda qs: volume_percentiles(x, qs, "none" if t is None else t), moments)
+    return intensity_map(x, imap)
+
+
 AUG_DESC_WORDS = 64             # MI355SEG_AUG_DESC_WORDS: int32 words of one patch descriptor (layout in include/mi355seg.h)
 
 

@@ -42,6 +42,7 @@ import torch
 from . import functional as F
 from .config import absent as _absent, compose, parse_patch_size
 from .engine import mixed_precision_dtype
+from .intensity import parse_intensity
 from .registry import build_model
 from .models.three_d.IS import set_band_split
 from .utils.metric import metric_from_counts, metric_with_spacing
@@ -435,8 +436,11 @@ def predict(config, model, log=print):
     rows, comp_rows = [], []
     spacing = parse_spacing(config)
     post = parse_postprocess(config)
+    intensity = parse_intensity(config)                  # config.intensity and its companions; None: the z-score of today
+    if intensity is not None:
+        log(f"intensity: {intensity}")
     for name, x, gt in cases:
-        vol = znorm(x.to(device))
+        vol = F.normalize_intensity(x.to(device), intensity) if intensity is not None else znorm(x.to(device))
         mask = sliding_window_predict(model, vol, ps, overlap, batch_size=max(1, int(config.batch_size)), dtype=mixed_precision_dtype(config),
                                       overlap_mode=mode, return_probabilities=save_prob, tta_flips=flips)
         if save_prob:

@@ -841,6 +841,47 @@ int mi355seg_label_index_build_f32(const float* labels, int D, int H, int W, int
 int mi355seg_label_index_select(const float* labels, int D, int H, int W, int pd, int ph, int pw, const void* index,
                                 const long long* picks, int n, int* origins, void* stream);
 
+/* ------------------------------------------------------------------ Intensity normalisation (config.intensity; csrc/intensity.hip)
+ * The reference's dataloader.py:19 imports RescaleIntensity and HistogramStandardization beside ZNormalization and wires neither in.
+ * UNPINNED (torchio is absent and the reference holds no fixture of its data pipeline): the definitions here are the specification.
+ *
+ * mi355seg_percentiles_f32: np.percentile(v, q, method="linear") of the taking-part voxels v of one volume x[n] -- all finite voxels,
+ * or with use_mask != 0 the finite voxels with x > mask_gt (the masks of tio.RescaleIntensity / ZNormalization / HistogramStandardization
+ * are of that form).  With m = their number and s = sort(v): position pos = q / 100 * (m - 1) in fp64, lo = floor(pos),
+ * hi = min(lo + 1, m - 1), t = pos - lo.  Outputs on the DEVICE: order fp32 [nq][2] = (s[lo], s[hi]), EXACT (voxel values; -0.0 is
+ * reported as +0.0); values fp64 [nq] = s[lo] + (s[hi] - s[lo]) * t; counts int64 [2] = (m, the number of non-finite voxels of x,
+ * masked or not).  q: nq doubles on the HOST.  Radix select, four 8-bit passes, integer counts only: exact, and equal inputs give
+ * bitwise equal outputs.  Nine launches (one of them a memset), no synchronisation, no host round trip.  With m == 0 order and values
+ * hold no information; m == 1 gives that voxel.  Refused before any launch: null pointers, n < 1, n >= 2^31, nq outside
+ * 1 .. MI355SEG_PERCENTILES_MAX, a percentile outside 0 .. 100 (NaN included), a NaN mask_gt with use_mask, x not 16-byte aligned, a
+ * workspace below mi355seg_percentiles_ws_bytes.
+ *
+ * The map (tio.RescaleIntensity, the clip + z-score and tio.HistogramStandardization's np.interp all are of this form): a continuous
+ * piecewise-linear function with nk knots, 2 <= nk <= MI355SEG_INTENSITY_KNOTS_MAX, kx ascending (equal neighbours allowed):
+ *   x' = min(max(x, clip_lo), clip_hi);  j = the number of interior knots kx[1 .. nk-2] that are <= x';
+ *   y  = fmaf(x' - kx[j], slope[j], ky[j])                 (fp32; the subtraction rounds once, the multiply-add is fused)
+ * so the first and the last segment extrapolate; clip_lo = -inf / clip_hi = +inf switch the clamp off.  kx[nk], ky[nk], slope[nk-1]
+ * are HOST arrays (computed by the caller in fp64, passed as fp32).
+ * mi355seg_intensity_map_f32: y[i] = map(x[i]) for all n voxels in one streaming pass; y == x allowed.
+ * mi355seg_intensity_moments_f32: over the voxels with x > mask_gt (the RAW x; all voxels with use_mask == 0), with d = map(x) - pivot
+ * in fp64: out fp64 [4] on the DEVICE = (count, pivot + sum d / count, (sum d^2 - (sum d)^2 / count) / (count - 1), sum d) -- the
+ * count, the mean and the unbiased variance of the mapped voxels (variance NaN below two voxels; mean = pivot for none).  pivot: any
+ * value near the data, as znorm pivots on x[0].  Block partials in a fixed order and a one-block finalise: no atomics, bitwise
+ * reproducible.  Two launches.
+ * Both refuse before any launch: null pointers, n < 1, nk outside 2 .. 12, descending knots, a NaN knot / value / slope / pivot /
+ * mask_gt, clip_lo > clip_hi (NaN included), pointers not 16-byte aligned, a workspace below mi355seg_intensity_moments_ws_bytes. */
+#define MI355SEG_PERCENTILES_MAX 16
+#define MI355SEG_INTENSITY_KNOTS_MAX 12
+size_t mi355seg_percentiles_ws_bytes(long long n);
+int mi355seg_percentiles_f32(const float* x, long long n, const double* q, int nq, int use_mask, float mask_gt,
+                             double* values, float* order, long long* counts, void* ws, size_t ws_bytes, void* stream);
+size_t mi355seg_intensity_moments_ws_bytes(long long n);
+int mi355seg_intensity_moments_f32(const float* x, long long n, const float* kx, const float* ky, const float* slope, int nk,
+                                   float clip_lo, float clip_hi, int use_mask, float mask_gt, double pivot, double* out,
+                                   void* ws, size_t ws_bytes, void* stream);
+int mi355seg_intensity_map_f32(const float* x, long long n, const float* kx, const float* ky, const float* slope, int nk,
+                               float clip_lo, float clip_hi, float* y, void* stream);
+
 /* ------------------------------------------------------------------ Frequency-band split of the IS network (train.py:76-88,198-201)
  * low_pass_torch / high_pass_torch at `limit`: the reference masks the spectrum of x [B,C,D,H,W] on its last two axes with the outer
  * product of (|fftfreq(H)| < limit, |rfftfreq(W)| < limit) for the low band and of the two `> limit` masks for the high band.  Per
