@@ -14,6 +14,7 @@ import torch
 
 from .intensity import (NYUL_PERCENTILES, host_masked, landmarks_from_percentiles, normalize_intensity_host, parse_intensity,
                         refuse_for_training)
+from .resample import parse_resample, refuse_for_training as refuse_resample_for_training, resample_host, resample_labels_host
 
 
 def _require_device(device, what, option="aug=True resamples with the HIP kernels of csrc/augment.hip"):
@@ -222,13 +223,22 @@ class DevicePatchQueue:
     (``draw_label_picks``: per patch ``u`` then ``r``, nothing else), one select launch turns them into origins
     (``functional.label_pick``), which are copied to the host once and cut as before.  ``label_probabilities``: ``None`` or
     ``{label: weight}`` (``parse_label_probabilities``).  Labels must have one channel and hold integers 0 .. 15 inside the region of
-    valid patch centres.  With ``sampler="uniform"`` (the default) nothing changes."""
+    valid patch centres.  With ``sampler="uniform"`` (the default) nothing changes.
+
+    ``resample`` (a ``resample.ResampleSpec``, ``config.resample_spacing``; tio.Resample, UNPINNED: the definitions of resample.py):
+    right after the upload image and labels are resampled from the volume's own spacing (``resample.spacings.of(file)``) to the
+    common one on the device (``functional.resample_volume`` at ``resample.order``, ``functional.resample_labels`` with
+    ``resample.labels``), once per cached subject; everything above -- the patch-size check, ``aug``, ``intensity``, the z-score and
+    both samplers -- then sees the resampled volume.  Refused with ``data_path=synthetic``.  With ``None`` nothing changes."""
 
     def __init__(self, data_path, gt_path, patch_size, batch_size, iters, device, seed=1234, queue_length=10,
-                 samples_per_volume=10, cache_gb=200.0, aug=False, sampler="uniform", label_probabilities=None, intensity=None):
+                 samples_per_volume=10, cache_gb=200.0, aug=False, sampler="uniform", label_probabilities=None, intensity=None,
+                 resample=None):
         self.aug = bool(aug)
         refuse_for_training(intensity, self.aug, data_path)
         self.intensity = intensity
+        refuse_resample_for_training(resample, data_path)
+        self.resample = resample                          # a resample.ResampleSpec, or None: the volumes stay on their own grids
         if sampler not in ("uniform", "label"):
             raise ValueError(f"DevicePatchQueue: unknown sampler='{sampler}' (expected 'uniform' or 'label')")
         self.sampler = sampler
@@ -245,6 +255,9 @@ class DevicePatchQueue:
         self.files = sorted(glob.glob(os.path.join(data_path, "*.npy")))
         if not self.files:
             raise FileNotFoundError(f"no .npy volumes under {data_path}")
+        if self.resample is not None:                     # a volume without a spacing is an error of the run, not of its first visit
+            for f in self.files:
+                self.resample.spacings.of(f)
         self.gt_path, self.bs, self.iters, self.device = gt_path, batch_size, iters, device
         self.ps = (patch_size,) * 3 if isinstance(patch_size, int) else tuple(patch_size)
         self.queue_length, self.spv = int(queue_length), int(samples_per_volume)
@@ -266,8 +279,17 @@ class DevicePatchQueue:
         y = torch.from_numpy(np.ascontiguousarray(np.load(os.path.join(self.gt_path, os.path.basename(f))), dtype=np.float32)).to(self.device)
         x = x[None] if x.dim() == 3 else x
         y = y[None] if y.dim() == 3 else y
+        if self.resample is not None:                     # config.resample_spacing: image and labels to the common grid, once
+            rs, sp = self.resample, self.resample.spacings.of(f)
+            if x.is_cuda:
+                from . import functional as F
+                x, y = F.resample_volume(x, sp, rs.target, rs.order), F.resample_labels(y, sp, rs.target, rs.labels)
+            else:                                         # CPU plumbing tests only: the same definitions in numpy fp64
+                x = torch.from_numpy(resample_host(x.numpy(), sp, rs.target, rs.order))
+                y = torch.from_numpy(resample_labels_host(y.numpy(), sp, rs.target, rs.labels))
         if any(s < p for s, p in zip(x.shape[1:], self.ps)):
-            raise ValueError(f"{f}: volume {tuple(x.shape[1:])} is smaller than the patch {self.ps}")
+            how = f" (resampled from spacing {sp} to {rs.target})" if self.resample is not None else ""
+            raise ValueError(f"{f}: volume {tuple(x.shape[1:])}{how} is smaller than the patch {self.ps}")
         if self.aug:                                      # raw: bias field, z-normalisation and noise ride in the sampling kernel
             x, y = x.contiguous(), y.contiguous()
         elif self.intensity is not None:                  # config.intensity: percentiles / moments / one map pass (csrc/intensity.hip)
@@ -374,6 +396,8 @@ def make_loader(config, device, in_channels, seed=1234):
     label_probabilities = parse_label_probabilities(getattr(config, "label_probabilities", None))
     intensity = parse_intensity(config)                   # config.intensity and its companions; None: the z-score of today
     refuse_for_training(intensity, aug, config.data_path)
+    resample = parse_resample(config)                     # config.resample_spacing and its companions; None: off
+    refuse_resample_for_training(resample, config.data_path)
     if str(config.data_path) == "synthetic":
         if sampler != "uniform":
             raise ValueError(f"config.sampler={sampler} needs volumes to sample from: with data_path=synthetic every sample is its own "
@@ -382,7 +406,7 @@ def make_loader(config, device, in_channels, seed=1234):
     return DevicePatchQueue(config.data_path, config.gt_path, config.patch_size, config.batch_size, iters, device, seed,
                             queue_length=int(getattr(config, "queue_length", 10)),
                             samples_per_volume=int(getattr(config, "samples_per_volume", 10)), aug=aug, sampler=sampler,
-                            label_probabilities=label_probabilities, intensity=intensity)
+                            label_probabilities=label_probabilities, intensity=intensity, resample=resample)
 
 
 def train_landmarks(files, mask="none", device="cuda"):

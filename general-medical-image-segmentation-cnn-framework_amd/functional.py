@@ -2362,6 +2362,162 @@ def normalize_intensity(x, spec, landmarks=None):
     return intensity_map(x, imap)
 
 
+# ----------------------------------------------------------------------------- resampling to a target spacing (csrc/resample.hip)
+from .resample import resample_axis_table, resampled_shape  # noqa: E402,F401  (host-only, numpy fp64; part of this module's interface)
+
+RESAMPLE_ORDERS = (0, 1, 3)
+RESAMPLE_LABEL_MODES = ("nearest", "linear")    # MI355SEG_RESAMPLE_LABELS_NEAREST / _LINEAR
+RESAMPLE_MAX_CLASSES = 16                       # MI355SEG_RESAMPLE_MAX_CLASSES
+
+
+class ResampleTables:
+    """The three per-axis tables of one resampling, packed z, y, x: ``base`` int32 and ``frac`` float32 on the device (each
+    Do + Ho + Wo long), ``base_host`` the numpy copy the library validates, ``in_shape`` / ``out_shape`` = (D, H, W) / (Do, Ho, Wo)."""
+
+    def __init__(self, in_shape, out_shape, ratios, order, device):
+        self.in_shape, self.out_shape, self.order = tuple(int(n) for n in in_shape), tuple(int(n) for n in out_shape), order
+        if len(self.in_shape) != 3 or len(self.out_shape) != 3:
+            raise Mi355SegError(f"resample: expected (D, H, W) shapes, got {in_shape} -> {out_shape}")
+        tabs = [resample_axis_table(n, no, r, order) for n, no, r in zip(self.in_shape, self.out_shape, ratios)]
+        self.base_host = np.ascontiguousarray(np.concatenate([t[0] for t in tabs]), dtype=np.int32)
+        self.frac_host = np.ascontiguousarray(np.concatenate([t[1] for t in tabs]), dtype=np.float32)
+        self.base = torch.from_numpy(self.base_host).to(device)
+        self.frac = torch.from_numpy(self.frac_host).to(device)
+
+    def args(self):
+        return _p(self.base), _p(self.frac), self.base_host.ctypes.data
+
+
+def _volume4(t, what, dtype=torch.float32):
+    """[D,H,W] or [C,D,H,W] device tensor -> (contiguous [C,D,H,W], had a channel axis)"""
+    if not t.is_cuda:
+        raise Mi355SegError(f"{what}: expected a tensor on an MI355X (cuda/HIP) device, got {t.device}; there is no CPU fallback in this package")
+    if t.dtype != dtype:
+        raise Mi355SegError(f"{what}: expected {dtype}, got {t.dtype}")
+    if t.dim() not in (3, 4) or t.numel() == 0:
+        raise Mi355SegError(f"{what}: expected a non-empty volume [D,H,W] or [C,D,H,W], got {tuple(t.shape)}")
+    return (t[None] if t.dim() == 3 else t).contiguous(), t.dim() == 4
+
+
+def bspline3_prefilter(x, out=None, axis=None):
+    """Cubic B-spline coefficients of ``x`` ([D,H,W] or [C,D,H,W], float32) per channel: scipy.ndimage.spline_filter(order=3,
+    mode='mirror') along W, H and D (mi355seg_bspline3_prefilter_f32; fp32, bitwise reproducible).  ``out=x`` filters in place;
+    ``axis`` = 0 | 1 | 2 runs the one pass along D | H | W only."""
+    x4, _ = _volume4(x, "bspline3_prefilter input")
+    y = torch.empty_like(x4) if out is None else out
+    if y.dtype != x4.dtype or y.device != x4.device or y.numel() != x4.numel() or not y.is_contiguous():
+        raise Mi355SegError(f"bspline3_prefilter: out must be a contiguous float32 tensor of x's shape on its device, got {tuple(y.shape)} {y.dtype}")
+    if out is not None and out.data_ptr() == x.data_ptr() and x4.data_ptr() != x.data_ptr():
+        raise Mi355SegError("bspline3_prefilter: in place needs a contiguous input")
+    C, D, H, W = x4.shape
+    L = lib()
+    ws = workspace(L.query("mi355seg_bspline3_prefilter_ws_bytes", C, D, H, W), x.device)
+    if axis is None:
+        L.call("mi355seg_bspline3_prefilter_f32", _p(x4), C, D, H, W, _p(y), _p(ws), ws.numel(), _stream())
+    else:
+        L.call("mi355seg_bspline3_prefilter_axis_f32", _p(x4), C, D, H, W, int(axis), _p(y), _p(ws), ws.numel(), _stream())
+    return y.view(x.shape) if out is None else out
+
+
+def resample3d(x, tables, order=None):
+    """``x`` [C,D,H,W] or [D,H,W] through ``tables`` (a ``ResampleTables`` of x's spatial shape) at ``order`` 0 | 1 | 3 (default: the
+    tables' own) in one launch (mi355seg_resample3d_f32).  At order 3 ``x`` must hold the coefficients of ``bspline3_prefilter``."""
+    order = tables.order if order is None else order
+    x4, had_c = _volume4(x, "resample3d input")
+    if tuple(x4.shape[1:]) != tables.in_shape:
+        raise Mi355SegError(f"resample3d: the tables are for a volume {tables.in_shape}, got {tuple(x4.shape[1:])}")
+    C = x4.shape[0]
+    y = torch.empty((C,) + tables.out_shape, dtype=torch.float32, device=x.device)
+    lib().call("mi355seg_resample3d_f32", _p(x4), C, *tables.in_shape, int(order), *tables.args(), _p(y), *tables.out_shape, _stream())
+    return y if had_c else y[0]
+
+
+def resample3d_labels(y, tables, mode):
+    """Label volume ``y`` ([C,D,H,W] or [D,H,W]; float32 holding integers, or int64) through ``tables`` (order 0 for ``nearest``,
+    order 1 for ``linear``) -> (labels of y's dtype, ``bad``: device int64 [1], the number of output voxels that read a value that is
+    no integer in 0 .. 15).  No synchronisation."""
+    if mode not in RESAMPLE_LABEL_MODES:
+        raise ValueError(f"resample labels: mode must be one of {RESAMPLE_LABEL_MODES}, got {mode!r}")
+    if y.dtype not in (torch.float32, torch.int64):
+        raise Mi355SegError(f"resample labels: expected float32 or int64 labels, got {y.dtype}")
+    y4, had_c = _volume4(y, "resample labels", y.dtype)
+    if tuple(y4.shape[1:]) != tables.in_shape or tables.order != RESAMPLE_LABEL_MODES.index(mode):
+        raise Mi355SegError(f"resample labels: the tables are order {tables.order} for a volume {tables.in_shape}, got mode {mode} and "
+                            f"{tuple(y4.shape[1:])}")
+    C = y4.shape[0]
+    L = lib()
+    ws = workspace(L.query("mi355seg_resample3d_labels_ws_bytes"), y.device)
+    out = torch.empty((C,) + tables.out_shape, dtype=y.dtype, device=y.device)
+    bad = torch.empty(1, dtype=torch.int64, device=y.device)
+    L.call("mi355seg_resample3d_labels_" + ("f32" if y.dtype == torch.float32 else "i64"), _p(y4), C, *tables.in_shape,
+           RESAMPLE_LABEL_MODES.index(mode), *tables.args(), _p(out), *tables.out_shape, _p(bad), _p(ws), ws.numel(), _stream())
+    return (out if had_c else out[0]), bad
+
+
+def _spacings(spacing, target):
+    from .resample import _triple
+    return _triple(spacing, "spacing"), _triple(target, "target spacing")
+
+
+def resample_volume(x, spacing, target, order=1):
+    """``x`` ([C,D,H,W] or [D,H,W], float32) at voxel ``spacing`` (sz, sy, sx) -> the volume at ``target`` spacing, shape
+    ``resampled_shape``; ``order`` 0 (nearest, exact), 1 (trilinear) or 3 (cubic B-spline: prefilter + gather).  Definitions:
+    include/mi355seg.h, "Resampling".  Equal spacings return ``x`` itself."""
+    if order not in RESAMPLE_ORDERS:
+        raise ValueError(f"resample_volume: order must be one of {RESAMPLE_ORDERS}, got {order!r}")
+    spacing, target = _spacings(spacing, target)
+    _volume4(x, "resample_volume input")
+    if spacing == target:
+        return x
+    shape = tuple(x.shape[-3:])
+    tables = ResampleTables(shape, resampled_shape(shape, spacing, target), [t / s for s, t in zip(spacing, target)], order, x.device)
+    return resample3d(bspline3_prefilter(x) if order == 3 else x, tables)
+
+
+def _checked_labels(out, bad, what):
+    n = int(bad.cpu()[0])                                    # the one device-to-host copy
+    if n:
+        raise ValueError(f"{what}: {n} resampled voxels read a label that is not an integer in 0 .. {RESAMPLE_MAX_CLASSES - 1}")
+    return out
+
+
+def resample_labels(y, spacing, target, mode="linear"):
+    """Label volume ``y`` at ``spacing`` -> ``target`` spacing: ``nearest`` (order 0, tio.Resample's rule) or ``linear`` (the class of
+    largest trilinear weight, lowest class on ties: the argmax of the resampled one-hot volume without that volume).  Raises
+    ``ValueError`` when a label read is no integer in 0 .. 15 (one device counter, read once)."""
+    spacing, target = _spacings(spacing, target)
+    shape = tuple(y.shape[-3:])
+    tables = ResampleTables(shape, resampled_shape(shape, spacing, target), [t / s for s, t in zip(spacing, target)],
+                            RESAMPLE_LABEL_MODES.index(mode) if mode in RESAMPLE_LABEL_MODES else 1, y.device)
+    return _checked_labels(*resample3d_labels(y, tables, mode), "resample_labels")
+
+
+def resample_back_labels(mask, shape, spacing, target, mode="linear"):
+    """The way back of a label mask: ``mask`` (int64 or float32, [C,D',H',W'] or [D',H',W']) on the grid of ``target`` spacing -> the
+    original grid ``shape`` = (D, H, W) of ``spacing``, with the rule of ``resample_labels``."""
+    spacing, target = _spacings(spacing, target)
+    tables = ResampleTables(tuple(mask.shape[-3:]), shape, [s / t for s, t in zip(spacing, target)],
+                            RESAMPLE_LABEL_MODES.index(mode) if mode in RESAMPLE_LABEL_MODES else 1, mask.device)
+    return _checked_labels(*resample3d_labels(mask, tables, mode), "resample_back_labels")
+
+
+def resample_back_argmax(prob, shape, spacing, target, return_probabilities=False):
+    """The way back of a blended prediction: ``prob`` float32 [K,D',H',W'] (K <= 16) on the grid of ``target`` spacing -> int64 labels
+    [1,D,H,W] on the original grid ``shape`` of ``spacing``: trilinear per class and the argmax (lowest class on ties) in one launch
+    (mi355seg_resample3d_argmax_f32); with ``return_probabilities`` also the interpolated float32 [K,D,H,W]."""
+    spacing, target = _spacings(spacing, target)
+    _require_cuda(prob, "resample_back_argmax input")
+    if prob.dim() != 4 or prob.numel() == 0:
+        raise Mi355SegError(f"resample_back_argmax: expected probabilities [K,D,H,W], got {tuple(prob.shape)}")
+    prob = prob.contiguous()
+    K = prob.shape[0]
+    tables = ResampleTables(tuple(prob.shape[1:]), shape, [s / t for s, t in zip(spacing, target)], 1, prob.device)
+    labels = torch.empty((1,) + tables.out_shape, dtype=torch.int64, device=prob.device)
+    out = torch.empty((K,) + tables.out_shape, dtype=torch.float32, device=prob.device) if return_probabilities else None
+    lib().call("mi355seg_resample3d_argmax_f32", _p(prob), K, *tables.in_shape, *tables.args(), _p(labels), _p(out), *tables.out_shape, _stream())
+    return (labels, out) if return_probabilities else labels
+
+
 AUG_DESC_WORDS = 64             # MI355SEG_AUG_DESC_WORDS: int32 words of one patch descriptor (layout in include/mi355seg.h)
 
 

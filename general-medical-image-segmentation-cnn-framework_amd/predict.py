@@ -30,6 +30,13 @@ not have (its predict.py:133 calls the model once per patch): every patch is pre
 un-mirrored and averaged, and the argmax comes last.  The mirrors happen inside the gather and accumulate launches (csrc/api.hip,
 csrc/aggregate.hip); in a blending mode the flips are the outer loop over the grid, in crop mode they are averaged per patch before
 its labels are pasted.  Output files and their columns do not change.
+
+``config.resample_spacing=tz,ty,tx`` (optional; the keys and definitions are in resample.py) resamples every image to that spacing
+on the device (csrc/resample.hip) before it is normalised, runs the sliding window on the resampled grid and brings the result back
+to the ORIGINAL grid before components, saving and metrics: in crop mode the mask through the label resampler
+(``config.resample_labels``), in a blending mode the class probabilities by trilinear interpolation with the argmax in the same
+launch.  ``config.spacing_file=/abs/spacings.csv`` (lines ``file,sz,sy,sx``) gives every volume its own spacing, for the resampling
+and for the metrics; with it and without ``resample_spacing`` the volumes are still graded each with its own spacing.
 """
 import csv
 import glob
@@ -43,6 +50,7 @@ from . import functional as F
 from .config import absent as _absent, compose, parse_patch_size
 from .engine import mixed_precision_dtype
 from .intensity import parse_intensity
+from .resample import parse_resample, parse_spacing_source
 from .registry import build_model
 from .models.three_d.IS import set_band_split
 from .utils.metric import metric_from_counts, metric_with_spacing
@@ -439,12 +447,31 @@ def predict(config, model, log=print):
     intensity = parse_intensity(config)                  # config.intensity and its companions; None: the z-score of today
     if intensity is not None:
         log(f"intensity: {intensity}")
+    resample = parse_resample(config)                    # config.resample_spacing and its companions; None: off
+    source = resample.spacings if resample is not None else parse_spacing_source(config)
+    if resample is not None:
+        log(f"resample: {resample}")
     for name, x, gt in cases:
-        vol = F.normalize_intensity(x.to(device), intensity) if intensity is not None else znorm(x.to(device))
+        xd = x.to(device)
+        if source is not None and source.table is not None:                  # config.spacing_file: every volume is graded with its own spacing
+            spacing = source.of(name)
+        if resample is not None:                         # forward: the image to the common grid, before the normalisation
+            grid, own = tuple(xd.shape[1:]), source.of(name)
+            xd = F.resample_volume(xd, own, resample.target, resample.order)
+        vol = F.normalize_intensity(xd, intensity) if intensity is not None else znorm(xd)
+        want_prob = save_prob or (resample is not None and mode != "crop")
         mask = sliding_window_predict(model, vol, ps, overlap, batch_size=max(1, int(config.batch_size)), dtype=mixed_precision_dtype(config),
-                                      overlap_mode=mode, return_probabilities=save_prob, tta_flips=flips)
-        if save_prob:
+                                      overlap_mode=mode, return_probabilities=want_prob, tta_flips=flips)
+        if want_prob:
             mask, prob = mask
+        if resample is not None:                         # the way back: everything below sees the original grid
+            if mode == "crop":
+                mask = F.resample_back_labels(mask, grid, own, resample.target, resample.labels)
+            elif save_prob:
+                mask, prob = F.resample_back_argmax(prob, grid, own, resample.target, return_probabilities=True)
+            else:
+                mask = F.resample_back_argmax(prob, grid, own, resample.target)
+        if save_prob:
             np.save(os.path.join(config.hydra_path, f"{name}_prob.npy"), prob.cpu().numpy())
         if post:
             mask, stats = F.filter_components(mask, min_voxels=post[1], keep_largest=post[0], connectivity=post[2], inplace=True)

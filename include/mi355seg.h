@@ -882,6 +882,76 @@ int mi355seg_intensity_moments_f32(const float* x, long long n, const float* kx,
 int mi355seg_intensity_map_f32(const float* x, long long n, const float* kx, const float* ky, const float* slope, int nk,
                                float clip_lo, float clip_hi, float* y, void* stream);
 
+/* ------------------------------------------------------------------ Resampling to a target voxel spacing (config.resample_spacing; csrc/resample.hip)
+ * The reference's dataloader.py:10 imports tio.Resample and never wires it in.  UNPINNED (torchio and SimpleITK are absent and the
+ * reference holds no fixture of its data pipeline): the definitions here are the specification, scipy.ndimage in fp64 the oracle.
+ *
+ * Geometry: axis-aligned and corner-aligned, per axis independently.  With input spacing s, target spacing t, input length n and
+ * r = t / s: output length n' = max(1, ceil(n * s / t - 1e-6)); output index o reads the input coordinate
+ * c(o) = clamp((o + 0.5) * r - 0.5, 0, n - 1).  The way back uses r = s / t and is GIVEN its output length.  The caller forms one
+ * table per axis in fp64 (functional.resample_axis_table) and packs them z, y, x: `base` int32 [Do + Ho + Wo] and `frac` fp32
+ * [Do + Ho + Wo] on the device, `base_host` the host copy of `base`.  Order 0: base = floor(c + 0.5) (half up), frac unused (may be
+ * NULL).  Orders 1 and 3: base = floor(c), frac = c - base.  No coordinate arithmetic happens on the device.  The wrappers validate
+ * `base_host` (the kernels trust `base` to hold the same numbers): 0 <= base < n on every axis, and for order 3 ascending per axis.
+ *
+ * mi355seg_bspline3_prefilter_f32: x [C,D,H,W] -> cubic B-spline coefficients y [C,D,H,W], scipy.ndimage.spline_filter(order=3,
+ * mode='mirror') per channel: along W, then H, then D the recursive filter with pole z = sqrt(3) - 2, gain 6 and a
+ * whole-sample-symmetric boundary; per line s[0 .. n-1]
+ *   c+[0] = g0 * sum_{k < K} z^k s[m(k)],   c+[i] = z c+[i-1] + 6 s[i],
+ *   c[n-1] = (z c+[n-2] + c+[n-1]) * z / (z^2 - 1),   c[i] = z * (c[i+1] - c+[i])
+ * (the running value of both recursions is a pair of floats, value + rounding residual, all fp32 arithmetic; the residuals of c+ wait
+ * in the workspace, one float per element: ws >= mi355seg_bspline3_prefilter_ws_bytes) where for n >= MI355SEG_BSPLINE_INIT_TERMS the sum is truncated, K = 14, g0 = 6 (|z|^14 < 2^-25), and below that it is the exact
+ * mirrored period: K = 2n - 2, m(k) = k < n ? k : 2n - 2 - k, g0 = 6 / (1 - z^(2n-2)).  An axis of length 1 is the identity.  No
+ * bound on any axis: lines along W go through LDS in chunks of 64 columns with the causal carry passed on in order.  fp32, FMA
+ * in a fixed order: equal inputs give bitwise equal outputs; y == x allowed, with bitwise the same result.  Up to three launches.
+ * mi355seg_bspline3_prefilter_axis_f32: ONE of the three passes (axis 0 = D, 1 = H, 2 = W; its length must be at least 2); the three
+ * in the order 2, 1, 0 are mi355seg_bspline3_prefilter_f32 bitwise.
+ * Both refuse: null or misaligned pointers, non-positive sizes, 2^31 elements or more, an axis outside 0 .. 2 or of length 1, a
+ * workspace too small.
+ *
+ * mi355seg_resample3d_f32: x [C,D,H,W] -> y [C,Do,Ho,Wo] in one launch.
+ *   order 0: y = x[base_z, base_y, base_x], exact.
+ *   order 1: trilinear over the corners (base, min(base + 1, n - 1)) per axis: corner weight (wz * wy) * wx with w = (1 - frac, frac),
+ *            summed by an FMA chain in the corner order zyx = 000, 001, ... 111.
+ *   order 3: x must hold the COEFFICIENTS of mi355seg_bspline3_prefilter_f32.  Taps base - 1 .. base + 2 per axis, mirrored into the
+ *            source (whole-sample symmetric), weights of t = frac: ((1-t)^3 / 6, t^2 (t/2 - 1) + 2/3, (1-t)^2 ((1-t)/2 - 1) + 2/3,
+ *            t^3 / 6), formed in fp64 from the fp32 fraction and used as pairs of floats; the sum is nested x, then y, then z,
+ *            every level carrying its rounding errors along (a pair of floats, fp32 arithmetic).  With the prefilter this is
+ *            scipy.ndimage.map_coordinates(order=3, mode='mirror') on the clamped coordinates.
+ * Refused: an order outside {0, 1, 3}, null or misaligned pointers (frac may be NULL at order 0), y == x, non-positive sizes, 2^31
+ * elements or more on either side, a base outside the source, a descending table at order 3.
+ *
+ * mi355seg_resample3d_labels_f32 / _i64: label volumes (fp32 holding integers, or int64) [C,D,H,W] -> [C,Do,Ho,Wo].
+ *   MI355SEG_RESAMPLE_LABELS_NEAREST: the order-0 table, tio.Resample's rule for label maps.
+ *   MI355SEG_RESAMPLE_LABELS_LINEAR: the order-1 table; the weight of class k is the sum of the corner weights (as order 1 above)
+ *   whose corner holds k, added in the corner order; the class of largest weight wins, the LOWEST class on a tie -- the argmax of the
+ *   trilinearly resampled one-hot volume (nnU-Net's way) in one pass, without that volume.
+ * bad[0] (int64, device): the number of output voxels that read a value that is no integer in 0 .. 15; such a value takes part as
+ * itself.  Block partials in a fixed order and a one-block finalise: no atomics.  Two launches; ws >= mi355seg_resample3d_labels_ws_bytes.
+ * Refused: a mode outside {0, 1}, what mi355seg_resample3d_f32 refuses, a null `bad` or workspace, a workspace too small.
+ *
+ * mi355seg_resample3d_argmax_f32: the way back of a blending mode.  prob [K,D,H,W] (class probabilities or logits on the resampled
+ * grid), the order-1 tables -> labels int64 [Do,Ho,Wo]: per class the order-1 value above, the first maximum wins (lowest class on
+ * ties, class 0 if nothing compares greater); prob_out, when not NULL, receives the K interpolated volumes [K,Do,Ho,Wo], and the
+ * labels are bitwise the same with and without it.  One launch.  Refused: K outside 1 .. MI355SEG_RESAMPLE_MAX_CLASSES, and what
+ * order 1 of mi355seg_resample3d_f32 refuses. */
+#define MI355SEG_BSPLINE_INIT_TERMS 14
+#define MI355SEG_RESAMPLE_MAX_CLASSES 16
+#define MI355SEG_RESAMPLE_LABELS_NEAREST 0
+#define MI355SEG_RESAMPLE_LABELS_LINEAR 1
+size_t mi355seg_bspline3_prefilter_ws_bytes(int C, int D, int H, int W);
+int mi355seg_bspline3_prefilter_f32(const float* x, int C, int D, int H, int W, float* y, void* ws, size_t ws_bytes, void* stream);
+int mi355seg_bspline3_prefilter_axis_f32(const float* x, int C, int D, int H, int W, int axis, float* y, void* ws, size_t ws_bytes, void* stream);
+int mi355seg_resample3d_f32(const float* x, int C, int D, int H, int W, int order, const int* base, const float* frac, const int* base_host,
+                            float* y, int Do, int Ho, int Wo, void* stream);
+size_t mi355seg_resample3d_labels_ws_bytes(void);
+int mi355seg_resample3d_labels_f32(const float* x, int C, int D, int H, int W, int mode, const int* base, const float* frac, const int* base_host,
+                                   float* y, int Do, int Ho, int Wo, long long* bad, void* ws, size_t ws_bytes, void* stream);
+int mi355seg_resample3d_labels_i64(const long long* x, int C, int D, int H, int W, int mode, const int* base, const float* frac, const int* base_host,
+                                   long long* y, int Do, int Ho, int Wo, long long* bad, void* ws, size_t ws_bytes, void* stream);
+int mi355seg_resample3d_argmax_f32(const float* prob, int K, int D, int H, int W, const int* base, const float* frac, const int* base_host,
+                                   long long* labels, float* prob_out, int Do, int Ho, int Wo, void* stream);
+
 /* ------------------------------------------------------------------ Frequency-band split of the IS network (train.py:76-88,198-201)
  * low_pass_torch / high_pass_torch at `limit`: the reference masks the spectrum of x [B,C,D,H,W] on its last two axes with the outer
  * product of (|fftfreq(H)| < limit, |rfftfreq(W)| < limit) for the low band and of the two `> limit` masks for the high band.  Per
