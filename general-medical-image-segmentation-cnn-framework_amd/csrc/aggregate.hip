@@ -36,10 +36,7 @@ namespace seg {
 constexpr int kAggThreads = 256;
 constexpr int kAggMaxK = 16;
 
-static int agg_grid(long long items) {
-    long long b = (items + kAggThreads - 1) / kAggThreads;
-    return (int)(b < 1 ? 1 : (b > 8192 ? 8192 : b));
-}
+static int agg_grid(long long items) { return stream_grid(items, kAggThreads, 8192); }
 
 struct AggGeom {
     int K, first, count, pd, ph, pw, D, H, W;

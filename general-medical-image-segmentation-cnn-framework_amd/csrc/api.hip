@@ -371,10 +371,7 @@ int mi355seg_ndhwc_bf16_to_ncdhw_f32(const mi355seg_bf16* src, int ldsrc, float*
     SEG_CHECK_LAUNCH();
     return MI355SEG_OK;
 }
-static int rows_grid(long long total) {
-    long long b = (total + 255) / 256;
-    return (int)(b < 1 ? 1 : (b > 4096 ? 4096 : b));
-}
+static int rows_grid(long long total) { return stream_grid(total, 256, 4096); }
 int mi355seg_gather_patches_f32(const float* vol, int C, int D, int H, int W, const int* table, int first, int count,
                                 int pd, int ph, int pw, float* out, void* stream) {
     SEG_CHECK_ARG(vol && table && out && C > 0 && count > 0 && first >= 0 && pd > 0 && ph > 0 && pw > 0 && pd <= D && ph <= H && pw <= W,

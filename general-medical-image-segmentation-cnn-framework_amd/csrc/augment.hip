@@ -18,6 +18,7 @@
 namespace seg {
 
 constexpr int kAugThreads = 256;
+static_assert(kAugThreads == kReduceThreads, "the block size of reduce.h");
 constexpr int kAugMaxBlocks = 1024;
 constexpr int kAugWords = MI355SEG_AUG_DESC_WORDS;      // int32 words per patch descriptor
 constexpr int kAugCp = 343;                             // 7 * 7 * 7 control points
@@ -66,23 +67,6 @@ __device__ __forceinline__ float aug_value(float x, float b, float mu, float rho
     return __fadd_rn(__fmul_rn(__fsub_rn(__fmul_rn(x, b), mu), rho), __fmul_rn(sigma, g));
 }
 
-template <int NV>
-__device__ __forceinline__ void aug_block_sum(double (&v)[NV], double* sh) {     // result valid in thread 0; sh: 4 * NV doubles
-    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-#pragma unroll
-    for (int j = 0; j < NV; ++j) v[j] = wave_sum(v[j]);
-    __syncthreads();
-    if (lane == 0) {
-#pragma unroll
-        for (int j = 0; j < NV; ++j) sh[wid * NV + j] = v[j];
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-#pragma unroll
-        for (int j = 0; j < NV; ++j) v[j] = ((sh[j] + sh[NV + j]) + sh[2 * NV + j]) + sh[3 * NV + j];
-    }
-}
-
 struct AugVol { const float* x; long long n, S; int C, D, H, W; float r0, r1, r2; };
 
 // the pivot of the sums: x * b at element 0 (keeps sum d^2 - (sum d)^2 / n well conditioned for CT-like offsets, as znorm_sums_kernel)
@@ -114,7 +98,6 @@ __device__ __forceinline__ void aug_for_each(const AugVol& v, const AugBias& co,
 
 template <int VEC>
 __global__ __launch_bounds__(kAugThreads) void aug_sums_kernel(AugVol v, AugBias co, double* __restrict__ part) {
-    __shared__ double sh[8];
     const float pv = aug_pivot(v, co);
     double acc[2] = {0.0, 0.0};
     aug_for_each<VEC>(v, co, [&](long long, float x, float b) {
@@ -122,22 +105,17 @@ __global__ __launch_bounds__(kAugThreads) void aug_sums_kernel(AugVol v, AugBias
         acc[0] += (double)d;
         acc[1] += (double)d * (double)d;
     });
-    aug_block_sum<2>(acc, sh);
+    block_sum(acc);
     if (threadIdx.x == 0) { part[2 * blockIdx.x] = acc[0]; part[2 * blockIdx.x + 1] = acc[1]; }
 }
 
 // (mu, rho) from the block partials, fixed order; every thread of the block gets the same two floats
 __device__ __forceinline__ void aug_mu_rho(const double* __restrict__ part, int nblk, float pv, long long n, float& mu, float& rho) {
-    __shared__ double sh[8];
     __shared__ float mr[2];
     double acc[2] = {0.0, 0.0};
-    for (int i = threadIdx.x; i < nblk; i += kAugThreads) { acc[0] += part[2 * i]; acc[1] += part[2 * i + 1]; }
-    aug_block_sum<2>(acc, sh);
-    if (threadIdx.x == 0) {
-        const double md = acc[0] / (double)n, var = (acc[1] - acc[0] * md) / (double)(n - 1);
-        mr[0] = (float)((double)pv + md);
-        mr[1] = (float)(1.0 / sqrt(var));
-    }
+    partials_reduce<OpSum>(part, nblk, acc);
+    block_sum(acc);
+    if (threadIdx.x == 0) pivoted_mean_rstd((double)pv, acc[0], acc[1], n, mr[0], mr[1]);
     __syncthreads();
     mu = mr[0]; rho = mr[1];
 }
@@ -145,33 +123,25 @@ __device__ __forceinline__ void aug_mu_rho(const double* __restrict__ part, int 
 template <int VEC>
 __global__ __launch_bounds__(kAugThreads) void aug_min_kernel(AugVol v, AugBias co, const double* __restrict__ part, int nblk_sums,
                                                               float sigma, unsigned k0, unsigned k1, float* __restrict__ minpart) {
-    __shared__ float shm[4];
     float mu, rho;
     aug_mu_rho(part, nblk_sums, aug_pivot(v, co), v.n, mu, rho);
     float m = INFINITY;
     aug_for_each<VEC>(v, co, [&](long long e, float x, float b) { m = fminf(m, aug_value(x, b, mu, rho, sigma, aug_gauss(k0, k1, e))); });
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) m = fminf(m, __shfl_xor(m, o, 64));
-    if ((threadIdx.x & 63) == 0) shm[threadIdx.x >> 6] = m;
-    __syncthreads();
-    if (threadIdx.x == 0) minpart[blockIdx.x] = fminf(fminf(shm[0], shm[1]), fminf(shm[2], shm[3]));
+    m = block_reduce_one<OpMin>(m);
+    if (threadIdx.x == 0) minpart[blockIdx.x] = m;
 }
 
 __global__ __launch_bounds__(kAugThreads) void aug_finalize_kernel(AugVol v, AugBias co, const double* __restrict__ part, int nblk_sums,
                                                                    const float* __restrict__ minpart, int nblk_min, float sigma,
                                                                    float* __restrict__ stats) {
-    __shared__ float shm[4];
     float mu, rho;
     aug_mu_rho(part, nblk_sums, aug_pivot(v, co), v.n, mu, rho);
-    float m = INFINITY;
-    for (int i = threadIdx.x; i < nblk_min; i += kAugThreads) m = fminf(m, minpart[i]);
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) m = fminf(m, __shfl_xor(m, o, 64));
-    if ((threadIdx.x & 63) == 0) shm[threadIdx.x >> 6] = m;
-    __syncthreads();
+    float m[1] = {INFINITY};
+    partials_reduce<OpMin>(minpart, nblk_min, m);
+    block_reduce<OpMin>(m);
     if (threadIdx.x == 0) {
         stats[0] = mu; stats[1] = rho;
-        stats[2] = fminf(fminf(shm[0], shm[1]), fminf(shm[2], shm[3]));
+        stats[2] = m[0];
         stats[3] = sigma;
     }
 }
@@ -307,11 +277,6 @@ __global__ __launch_bounds__(kAugThreads) void aug_sample_kernel(const int* __re
     }
 }
 
-static int aug_grid(long long items) {
-    const long long b = (items + kAugThreads - 1) / kAugThreads;
-    return (int)(b < 1 ? 1 : (b > kAugMaxBlocks ? kAugMaxBlocks : b));
-}
-
 }  // namespace seg
 
 using namespace seg;
@@ -340,7 +305,7 @@ int mi355seg_augment_stats_f32(const float* x, int C, int D, int H, int W, const
     for (int i = 0; i < 20; ++i) co.c[i] = bias_host[i];
     const unsigned k0 = (unsigned)((unsigned long long)seed & 0xffffffffull), k1 = (unsigned)((unsigned long long)seed >> 32);
     const bool vec = (W % 4 == 0) && ((uintptr_t)x % 16 == 0);
-    const int nblk = aug_grid(vec ? n / 4 : n);
+    const int nblk = stream_grid(vec ? n / 4 : n, kAugThreads, kAugMaxBlocks);
     if (vec) {
         hipLaunchKernelGGL(aug_sums_kernel<4>, dim3(nblk), dim3(kAugThreads), 0, st, v, co, part);
         SEG_CHECK_LAUNCH();

@@ -6,6 +6,7 @@
 #include <stdarg.h>
 #include <type_traits>
 #include "../../include/mi355seg.h"
+#include "reduce.h"     // wave_sum and the block / partials reductions
 
 namespace seg {
 
@@ -169,23 +170,6 @@ struct ProfScope {
     ProfScope(int family, double flops, double bytes, hipStream_t s) : st(s), on((g_prof_mask >> family) & 1u) { if (on) prof_begin(family, flops, bytes, s); }
     ~ProfScope() { if (on) prof_end(st); }
 };
-
-// Sum across the 64 lanes of a wavefront (result valid in every lane).
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-__device__ __forceinline__ long long wave_sum(long long v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
 
 // max-combine a workgroup's non-negative value into a device scalar (compare of the bit patterns: order-independent, so the result
 // is reproducible).  Every thread of the workgroup must call it (block size a multiple of 64, at most 1024).

@@ -23,6 +23,7 @@ namespace seg {
 
 constexpr int kCcTZ = 8, kCcTY = 8, kCcTX = 64;         // the tile, z x y x x: 4096 voxels, 32 KiB of LDS
 constexpr int kCcThreads = 256;
+static_assert(kCcThreads == kReduceThreads, "the block size of reduce.h");
 constexpr int kCcWaves = kCcThreads / kWave;
 constexpr int kCcRows = kCcTZ * kCcTY;                  // rows of kCcTX = 64 voxels: one wave owns a row at a time
 constexpr int kCcRowsPerWave = kCcRows / kCcWaves;
@@ -31,10 +32,7 @@ constexpr long long kCcMaxVoxels = (1ll << 31) - 2;     // root + 1 must fit an 
 static_assert(kCcTX == kWave, "a wave owns one row of the tile");
 static_assert(kCcRows % kCcWaves == 0, "rows divide among the waves");
 
-static int cc_grid(long long items) {
-    long long b = (items + kCcThreads - 1) / kCcThreads;
-    return (int)(b < 1 ? 1 : (b > 4096 ? 4096 : b));
-}
+static int cc_grid(long long items) { return stream_grid(items, kCcThreads, 4096); }
 
 // ---- union-find on an int array in LDS (workgroup scope) or in global memory (agent scope).
 // Every access is an atomic of that scope.  In global memory this is what makes the merge kernel correct across XCDs: the per-XCD
@@ -287,79 +285,50 @@ __device__ __forceinline__ unsigned long long cc_key(int size, long long slot) {
     return size > 0 ? ((unsigned long long)(unsigned)size << 32) | (0xFFFFFFFFull - (unsigned long long)(slot + 1)) : 0ull;
 }
 
+// foreground voxels and components are summed, the key takes the maximum: one pass for the three
+struct OpCcInfo {
+    static __device__ __forceinline__ unsigned long long apply(unsigned long long a, unsigned long long b, int j) {
+        return j < 2 ? a + b : (b > a ? b : a);
+    }
+};
+
 // part[block][3] = foreground voxels, components, max key over this block's share of sizes[]
 __global__ __launch_bounds__(kCcThreads) void components_info_kernel(const int* __restrict__ sizes, long long numel,
         unsigned long long* __restrict__ part) {
-    unsigned long long fg = 0, ncomp = 0, key = 0;
+    unsigned long long acc[3] = {0, 0, 0};      // foreground voxels, components, max key
     const long long quads = numel / 4;
     for (long long q = (long long)blockIdx.x * blockDim.x + threadIdx.x; q < quads; q += (long long)gridDim.x * blockDim.x) {
         const int4 c = *reinterpret_cast<const int4*>(sizes + 4 * q);
         const int cv[4] = {c.x, c.y, c.z, c.w};
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
-            fg += (unsigned)cv[j];
-            ncomp += cv[j] > 0;
+            acc[0] += (unsigned)cv[j];
+            acc[1] += cv[j] > 0;
             const unsigned long long k = cc_key(cv[j], 4 * q + j);
-            key = k > key ? k : key;
+            acc[2] = k > acc[2] ? k : acc[2];
         }
     }
     if (blockIdx.x == 0 && threadIdx.x < (int)(numel - 4 * quads)) {
         const long long v = 4 * quads + threadIdx.x;
         const int c = sizes[v];
-        fg += (unsigned)c;
-        ncomp += c > 0;
+        acc[0] += (unsigned)c;
+        acc[1] += c > 0;
         const unsigned long long k = cc_key(c, v);
-        key = k > key ? k : key;
+        acc[2] = k > acc[2] ? k : acc[2];
     }
-    for (int o = kWave / 2; o > 0; o >>= 1) {
-        fg += __shfl_xor(fg, o, kWave);
-        ncomp += __shfl_xor(ncomp, o, kWave);
-        const unsigned long long k = __shfl_xor(key, o, kWave);
-        key = k > key ? k : key;
-    }
-    __shared__ unsigned long long sh[kCcWaves][3];
-    if ((threadIdx.x & (kWave - 1)) == 0) {
-        sh[threadIdx.x / kWave][0] = fg; sh[threadIdx.x / kWave][1] = ncomp; sh[threadIdx.x / kWave][2] = key;
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        for (int w = 1; w < kCcWaves; ++w) {
-            fg += sh[w][0]; ncomp += sh[w][1];
-            key = sh[w][2] > key ? sh[w][2] : key;
-        }
-        part[(long long)blockIdx.x * 3 + 0] = fg;
-        part[(long long)blockIdx.x * 3 + 1] = ncomp;
-        part[(long long)blockIdx.x * 3 + 2] = key;
-    }
+    block_reduce<OpCcInfo>(acc);
+    if (threadIdx.x == 0) for (int j = 0; j < 3; ++j) part[(long long)blockIdx.x * 3 + j] = acc[j];
 }
 
 __global__ __launch_bounds__(kCcThreads) void components_info_finalize_kernel(const unsigned long long* __restrict__ part, int nblk,
         int64_t* __restrict__ info) {
-    unsigned long long fg = 0, ncomp = 0, key = 0;
-    for (int i = threadIdx.x; i < nblk; i += kCcThreads) {
-        fg += part[(long long)i * 3];
-        ncomp += part[(long long)i * 3 + 1];
-        const unsigned long long k = part[(long long)i * 3 + 2];
-        key = k > key ? k : key;
-    }
-    for (int o = kWave / 2; o > 0; o >>= 1) {
-        fg += __shfl_xor(fg, o, kWave);
-        ncomp += __shfl_xor(ncomp, o, kWave);
-        const unsigned long long k = __shfl_xor(key, o, kWave);
-        key = k > key ? k : key;
-    }
-    __shared__ unsigned long long sh[kCcWaves][3];
-    if ((threadIdx.x & (kWave - 1)) == 0) {
-        sh[threadIdx.x / kWave][0] = fg; sh[threadIdx.x / kWave][1] = ncomp; sh[threadIdx.x / kWave][2] = key;
-    }
-    __syncthreads();
+    unsigned long long acc[3] = {0, 0, 0};
+    partials_reduce<OpCcInfo>(part, nblk, acc);
+    block_reduce<OpCcInfo>(acc);
     if (threadIdx.x == 0) {
-        for (int w = 1; w < kCcWaves; ++w) {
-            fg += sh[w][0]; ncomp += sh[w][1];
-            key = sh[w][2] > key ? sh[w][2] : key;
-        }
-        info[0] = (int64_t)fg;
-        info[1] = (int64_t)ncomp;
+        const unsigned long long key = acc[2];
+        info[0] = (int64_t)acc[0];
+        info[1] = (int64_t)acc[1];
         info[2] = (int64_t)(key >> 32);
         info[3] = key ? (int64_t)(0xFFFFFFFFull - (key & 0xFFFFFFFFull)) : 0;
     }
@@ -381,7 +350,6 @@ __global__ __launch_bounds__(kCcThreads) void components_filter_kernel(const int
         const int* __restrict__ sizes, long long numel, int min_voxels, const int* __restrict__ keep_labels, int n_keep,
         int64_t* out, unsigned long long* __restrict__ removed) {
     __shared__ int keep[16];
-    __shared__ long long sh[kCcWaves];
     if (threadIdx.x < 16) keep[threadIdx.x] = (int)threadIdx.x < n_keep ? keep_labels[threadIdx.x] : -1;
     __syncthreads();
     long long gone = 0;
@@ -406,13 +374,8 @@ __global__ __launch_bounds__(kCcThreads) void components_filter_kernel(const int
             out[i] = m;
         }
     }
-    gone = wave_sum(gone);
-    if ((threadIdx.x & (kWave - 1)) == 0) sh[threadIdx.x / kWave] = gone;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        for (int w = 1; w < kCcWaves; ++w) gone += sh[w];
-        if (gone) atomicAdd(removed, (unsigned long long)gone);         // one per workgroup; integer, so order-independent
-    }
+    gone = block_reduce_one<OpSum>(gone);
+    if (threadIdx.x == 0 && gone) atomicAdd(removed, (unsigned long long)gone);      // one per workgroup; integer, so order-independent
 }
 
 static size_t cc_parent_bytes(long long numel) { return align_up((size_t)numel * sizeof(int), 256); }

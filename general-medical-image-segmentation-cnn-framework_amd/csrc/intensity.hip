@@ -31,6 +31,7 @@
 namespace seg {
 
 constexpr int kIntThreads = 256;
+static_assert(kIntThreads == kReduceThreads, "the block size of reduce.h");
 constexpr int kSelMaxBlocks = 1024;          // every workgroup flushes up to 32 * 256 bins: four workgroups per CU is all it takes
 constexpr int kSelBins = 256;
 constexpr int kSelUnroll = 4;                // 16-byte loads in flight per thread
@@ -40,10 +41,7 @@ constexpr int kSelMaxRanks = 2 * kSelMaxQ;
 constexpr int kMomMaxBlocks = 2048;
 static_assert(kSelMaxRanks == 32 && kSelBins == 256, "four bins per lane in the scan; 32 KB of LDS per histogram workgroup, one filter entry per thread");
 
-static int int_grid(long long items, int cap) {
-    long long b = (items + kIntThreads - 1) / kIntThreads;
-    return (int)(b < 1 ? 1 : (b > cap ? cap : b));
-}
+static int int_grid(long long items, int cap) { return stream_grid(items, kIntThreads, cap); }
 
 // ------------------------------------------------------------------------------------------------ (a) radix select
 __device__ __forceinline__ unsigned sel_key(float v) {
@@ -294,17 +292,6 @@ __global__ __launch_bounds__(kIntThreads) void intensity_map_kernel(const float*
 }
 
 // ------------------------------------------------------------------------------------------------ (b) moments
-// block-wide sum of three doubles; result valid in thread 0
-__device__ __forceinline__ void int_block_sum3(double (&v)[3], double* sh) {
-    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-#pragma unroll
-    for (int j = 0; j < 3; ++j) v[j] = wave_sum(v[j]);
-    if (lane == 0) { sh[wid * 3] = v[0]; sh[wid * 3 + 1] = v[1]; sh[wid * 3 + 2] = v[2]; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        for (int w = 1; w < (int)(blockDim.x >> 6); ++w) { v[0] += sh[w * 3]; v[1] += sh[w * 3 + 1]; v[2] += sh[w * 3 + 2]; }
-    }
-}
 template <int NK>
 __device__ __forceinline__ void mom_add(float x, const MapParams& P, int use_mask, float mask_gt, double pivot, double (&acc)[3]) {
     if (use_mask && !(x > mask_gt)) return;
@@ -314,7 +301,6 @@ __device__ __forceinline__ void mom_add(float x, const MapParams& P, int use_mas
 template <int NK>
 __global__ __launch_bounds__(kIntThreads) void intensity_moments_kernel(const float* __restrict__ x, MapParams P, long long n, int use_mask, float mask_gt,
                                                                          double pivot, double* __restrict__ part) {
-    __shared__ double sh[12];
     double acc[3] = {0.0, 0.0, 0.0};
     const long long n4 = n / 4;
     for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (long long)gridDim.x * blockDim.x) {
@@ -323,15 +309,14 @@ __global__ __launch_bounds__(kIntThreads) void intensity_moments_kernel(const fl
         mom_add<NK>(v.z, P, use_mask, mask_gt, pivot, acc); mom_add<NK>(v.w, P, use_mask, mask_gt, pivot, acc);
     }
     if (blockIdx.x == 0 && threadIdx.x < (n & 3)) mom_add<NK>(x[n4 * 4 + threadIdx.x], P, use_mask, mask_gt, pivot, acc);
-    int_block_sum3(acc, sh);
+    block_sum(acc);
     if (threadIdx.x == 0) { part[3 * blockIdx.x] = acc[0]; part[3 * blockIdx.x + 1] = acc[1]; part[3 * blockIdx.x + 2] = acc[2]; }
 }
 // out: count, mean, unbiased variance (NaN below two voxels), sum of (map(x) - pivot)
 __global__ __launch_bounds__(kIntThreads) void intensity_moments_finalize_kernel(const double* __restrict__ part, int nblk, double pivot, double* __restrict__ out) {
-    __shared__ double sh[12];
     double acc[3] = {0.0, 0.0, 0.0};
-    for (int i = threadIdx.x; i < nblk; i += kIntThreads) { acc[0] += part[3 * i]; acc[1] += part[3 * i + 1]; acc[2] += part[3 * i + 2]; }
-    int_block_sum3(acc, sh);
+    partials_reduce<OpSum>(part, nblk, acc);
+    block_sum(acc);
     if (threadIdx.x == 0) {
         const double c = acc[0], md = c > 0.0 ? acc[1] / c : 0.0;
         out[0] = c;

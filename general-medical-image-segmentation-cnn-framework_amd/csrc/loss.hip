@@ -7,47 +7,18 @@
 // pred.argmax(dim=1, keepdim=True) train.py:204; metric() utils/metric.py:20-75;
 // DiceLoss / BinaryDiceLoss / DiceLossss loss_function.py:61-185.
 #include "common.h"
+#include "loss_math.h"
 
 namespace seg {
 
 constexpr int kLossThreads = 256;
+static_assert(kLossThreads == kReduceThreads, "the block size of reduce.h");
 constexpr int kLossMaxBlocks = 2048;
 
-static int loss_grid(long long items) {
-    long long b = (items + kLossThreads - 1) / kLossThreads;
-    return (int)(b < 1 ? 1 : (b > kLossMaxBlocks ? kLossMaxBlocks : b));
-}
-
-// block-wide sum of NV doubles; result valid in thread 0
-template <int NV, typename T>
-__device__ __forceinline__ void block_sum(T (&v)[NV], T* sh) {
-    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-#pragma unroll
-    for (int j = 0; j < NV; ++j) v[j] = wave_sum(v[j]);
-    if (lane == 0) {
-#pragma unroll
-        for (int j = 0; j < NV; ++j) sh[wid * NV + j] = v[j];
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        const int nw = blockDim.x >> 6;
-#pragma unroll
-        for (int j = 0; j < NV; ++j) {
-            T s = sh[j];
-            for (int w = 1; w < nw; ++w) s += sh[w * NV + j];
-            v[j] = s;
-        }
-    }
-}
-
-__device__ __forceinline__ float bce_term(float x, float t) {
-    // max(x,0) - x*t + log1p(exp(-|x|))
-    return fmaxf(x, 0.f) - x * t + log1pf(expf(-fabsf(x)));
-}
+static int loss_grid(long long items) { return stream_grid(items, kLossThreads, kLossMaxBlocks); }
 
 __global__ __launch_bounds__(kLossThreads) void bce_fwd_kernel(const float* __restrict__ x, const float* __restrict__ t,
                                                                 long long numel, double* __restrict__ part) {
-    __shared__ double sh[4];
     double acc[1] = {0.0};
     const long long n4 = numel / 4;
     float local = 0.f;
@@ -61,15 +32,14 @@ __global__ __launch_bounds__(kLossThreads) void bce_fwd_kernel(const float* __re
         long long i = n4 * 4 + threadIdx.x;
         acc[0] += (double)bce_term(x[i], t[i]);
     }
-    block_sum<1>(acc, sh);
+    block_sum(acc);
     if (threadIdx.x == 0) part[blockIdx.x] = acc[0];
 }
 
 __global__ __launch_bounds__(256) void bce_finalize_kernel(const double* __restrict__ part, int nblk, double numel, float* __restrict__ loss) {
-    __shared__ double sh[4];
     double acc[1] = {0.0};
-    for (int i = threadIdx.x; i < nblk; i += 256) acc[0] += part[i];
-    block_sum<1>(acc, sh);
+    partials_reduce<OpSum>(part, nblk, acc);
+    block_sum(acc);
     if (threadIdx.x == 0) loss[0] = (float)(acc[0] / numel);
 }
 
@@ -81,21 +51,17 @@ __global__ __launch_bounds__(256) void bce_bwd_kernel(const float* __restrict__ 
         float4 a = reinterpret_cast<const float4*>(x)[i];
         float4 b = reinterpret_cast<const float4*>(t)[i];
         float4 o;
-        o.x = (1.f / (1.f + expf(-a.x)) - b.x) * sc;
-        o.y = (1.f / (1.f + expf(-a.y)) - b.y) * sc;
-        o.z = (1.f / (1.f + expf(-a.z)) - b.z) * sc;
-        o.w = (1.f / (1.f + expf(-a.w)) - b.w) * sc;
+        o.x = (sigmoid(a.x) - b.x) * sc;
+        o.y = (sigmoid(a.y) - b.y) * sc;
+        o.z = (sigmoid(a.z) - b.z) * sc;
+        o.w = (sigmoid(a.w) - b.w) * sc;
         reinterpret_cast<float4*>(dx)[i] = o;
     }
     if (blockIdx.x == 0 && threadIdx.x < (numel & 3)) {
         long long i = n4 * 4 + threadIdx.x;
-        dx[i] = (1.f / (1.f + expf(-x[i])) - t[i]) * sc;
+        dx[i] = (sigmoid(x[i]) - t[i]) * sc;
     }
 }
-
-// torch.argmax's order: the first maximum in scan order wins and a NaN beats every number (the first NaN wins), as
-// maxpool2_fwd_kernel (pool.hip) does for its window
-__device__ __forceinline__ bool nan_first_gt(float v, float best) { return v > best || (v != v && best == best); }
 
 __global__ __launch_bounds__(256) void argmax_kernel(const float* __restrict__ x, long long N, int K, long long S,
                                                       int64_t* __restrict__ mask) {
@@ -111,24 +77,14 @@ __global__ __launch_bounds__(256) void argmax_kernel(const float* __restrict__ x
 
 __global__ __launch_bounds__(kLossThreads) void dice_counts_kernel(const int64_t* __restrict__ gt, const int64_t* __restrict__ pr,
                                                                     long long numel, long long* __restrict__ part) {
-    __shared__ long long sh[16];
     long long acc[4] = {0, 0, 0, 0};
     for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < numel; i += (long long)gridDim.x * blockDim.x) {
         long long g = gt[i], p = pr[i];
         acc[0] += g; acc[1] += p;
         acc[2] += ((g & p) != 0); acc[3] += ((g | p) != 0);
     }
-    block_sum<4>(acc, sh);
+    block_sum(acc);
     if (threadIdx.x == 0) for (int j = 0; j < 4; ++j) part[(long long)blockIdx.x * 4 + j] = acc[j];
-}
-
-__global__ __launch_bounds__(256) void counts_finalize_kernel(const long long* __restrict__ part, int nblk, int64_t* __restrict__ counts) {
-    __shared__ long long sh[16];
-    long long acc[4] = {0, 0, 0, 0};
-    for (int i = threadIdx.x; i < nblk; i += 256)
-        for (int j = 0; j < 4; ++j) acc[j] += part[(long long)i * 4 + j];
-    block_sum<4>(acc, sh);
-    if (threadIdx.x == 0) for (int j = 0; j < 4; ++j) counts[j] = acc[j];
 }
 
 // train.py:190-193: gt_back = (gt == 0); gt = cat([gt_back, gt], dim=1) as float, one pass
@@ -145,8 +101,6 @@ __global__ __launch_bounds__(256) void two_channel_gt_kernel(const float* __rest
 // one pass over logits + one-hot targets: BCE sum, argmax(pred), argmax(gt), Dice counters
 __global__ __launch_bounds__(kLossThreads) void bce_argmax_dice_kernel(const float* __restrict__ x, const float* __restrict__ t,
         long long N, int K, long long S, int64_t* __restrict__ mask, double* __restrict__ lpart, long long* __restrict__ cpart) {
-    __shared__ double shd[4];
-    __shared__ long long shc[16];
     double lacc[1] = {0.0};
     long long acc[4] = {0, 0, 0, 0};
     const long long total = N * S;
@@ -167,8 +121,8 @@ __global__ __launch_bounds__(kLossThreads) void bce_argmax_dice_kernel(const flo
         acc[0] += it; acc[1] += ix;
         acc[2] += ((it & ix) != 0); acc[3] += ((it | ix) != 0);
     }
-    block_sum<1>(lacc, shd);
-    block_sum<4>(acc, shc);
+    block_sum(lacc);
+    block_sum(acc);
     if (threadIdx.x == 0) {
         lpart[blockIdx.x] = lacc[0];
         for (int j = 0; j < 4; ++j) cpart[(long long)blockIdx.x * 4 + j] = acc[j];
@@ -177,24 +131,15 @@ __global__ __launch_bounds__(kLossThreads) void bce_argmax_dice_kernel(const flo
 
 __global__ __launch_bounds__(kLossThreads) void dice_sums_kernel(const float* __restrict__ x, const float* __restrict__ t,
         long long numel, int apply_sigmoid, double* __restrict__ part) {
-    __shared__ double sh[20];
     double acc[5] = {0, 0, 0, 0, 0};
     for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < numel; i += (long long)gridDim.x * blockDim.x) {
         float a = x[i], b = t[i];
-        if (apply_sigmoid) a = 1.f / (1.f + expf(-a));
+        if (apply_sigmoid) a = sigmoid(a);
         acc[0] += (double)(a * b); acc[1] += (double)a; acc[2] += (double)b;
         acc[3] += (double)(a * a); acc[4] += (double)(b * b);
     }
-    block_sum<5>(acc, sh);
+    block_sum(acc);
     if (threadIdx.x == 0) for (int j = 0; j < 5; ++j) part[(long long)blockIdx.x * 5 + j] = acc[j];
-}
-__global__ __launch_bounds__(256) void sums_finalize5_kernel(const double* __restrict__ part, int nblk, double* __restrict__ out) {
-    __shared__ double sh[20];
-    double acc[5] = {0, 0, 0, 0, 0};
-    for (int i = threadIdx.x; i < nblk; i += 256)
-        for (int j = 0; j < 5; ++j) acc[j] += part[(long long)i * 5 + j];
-    block_sum<5>(acc, sh);
-    if (threadIdx.x == 0) for (int j = 0; j < 5; ++j) out[j] = acc[j];
 }
 
 __global__ __launch_bounds__(256) void dice_sums_bwd_kernel(const float* __restrict__ x, const float* __restrict__ t,
@@ -202,7 +147,7 @@ __global__ __launch_bounds__(256) void dice_sums_bwd_kernel(const float* __restr
     const float g0 = (float)g5[0], g1 = (float)g5[1], g3 = (float)g5[3];
     for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < numel; i += (long long)gridDim.x * blockDim.x) {
         float a = x[i], d = 1.f;
-        if (apply_sigmoid) { a = 1.f / (1.f + expf(-a)); d = a * (1.f - a); }
+        if (apply_sigmoid) { a = sigmoid(a); d = a * (1.f - a); }
         dx[i] = (g0 * t[i] + g1 + 2.f * g3 * a) * d;
     }
 }
@@ -215,14 +160,13 @@ __device__ __forceinline__ float dpow_p(float a, float p) {     // d a^p / da, t
     return p == 2.f ? 2.f * a : (p == 1.f ? 1.f : (p == 0.f ? 0.f : p * powf(a, p - 1.f)));
 }
 __device__ __forceinline__ void dice_acc(double (&acc)[5], float a, float b, int apply_sigmoid, float p) {
-    if (apply_sigmoid) a = 1.f / (1.f + expf(-a));
+    if (apply_sigmoid) a = sigmoid(a);
     acc[0] += (double)(a * b); acc[1] += (double)a; acc[2] += (double)b;
     acc[3] += (double)pow_p(a, p); acc[4] += (double)pow_p(b, p);
 }
 // grid = (blocks per row, R); part[(row * gridDim.x + block) * 5 + j]
 __global__ __launch_bounds__(kLossThreads) void dice_rows_kernel(const float* __restrict__ x, const float* __restrict__ t,
         long long L, int apply_sigmoid, float p, int vec, double* __restrict__ part) {
-    __shared__ double sh[20];
     double acc[5] = {0, 0, 0, 0, 0};
     const float* xr = x + (long long)blockIdx.y * L;
     const float* tr = t + (long long)blockIdx.y * L;
@@ -238,18 +182,8 @@ __global__ __launch_bounds__(kLossThreads) void dice_rows_kernel(const float* __
     } else {
         for (long long i = first; i < L; i += stride) dice_acc(acc, xr[i], tr[i], apply_sigmoid, p);
     }
-    block_sum<5>(acc, sh);
+    block_sum(acc);
     if (threadIdx.x == 0) for (int j = 0; j < 5; ++j) part[((long long)blockIdx.y * gridDim.x + blockIdx.x) * 5 + j] = acc[j];
-}
-// one block per row, fixed order
-__global__ __launch_bounds__(256) void dice_rows_finalize_kernel(const double* __restrict__ part, int nblk, double* __restrict__ out) {
-    __shared__ double sh[20];
-    double acc[5] = {0, 0, 0, 0, 0};
-    const double* pr = part + (long long)blockIdx.x * nblk * 5;
-    for (int i = threadIdx.x; i < nblk; i += 256)
-        for (int j = 0; j < 5; ++j) acc[j] += pr[(long long)i * 5 + j];
-    block_sum<5>(acc, sh);
-    if (threadIdx.x == 0) for (int j = 0; j < 5; ++j) out[(long long)blockIdx.x * 5 + j] = acc[j];
 }
 // dx[r][i] = (g[r][0]*t + g[r][1] + g[r][3] * d(a^p)/da) * da/dx
 __global__ __launch_bounds__(256) void dice_rows_bwd_kernel(const float* __restrict__ x, const float* __restrict__ t,
@@ -259,7 +193,7 @@ __global__ __launch_bounds__(256) void dice_rows_bwd_kernel(const float* __restr
     const long long base = (long long)blockIdx.y * L;
     for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < L; i += (long long)gridDim.x * blockDim.x) {
         float a = x[base + i], d = 1.f;
-        if (apply_sigmoid) { a = 1.f / (1.f + expf(-a)); d = a * (1.f - a); }
+        if (apply_sigmoid) { a = sigmoid(a); d = a * (1.f - a); }
         dx[base + i] = (g0 * t[base + i] + g1 + g3 * dpow_p(a, p)) * d;
     }
 }
@@ -268,7 +202,6 @@ __global__ __launch_bounds__(256) void dice_rows_bwd_kernel(const float* __restr
 // Sums of d = x - x[0] and d^2 in fp64 (the pivot keeps sum d^2 - (sum d)^2 / n well conditioned for CT-like offsets),
 // two-stage and fixed-order; the apply pass turns them into mean and 1 / std.
 __global__ __launch_bounds__(kLossThreads) void znorm_sums_kernel(const float* __restrict__ x, long long n, double* __restrict__ part) {
-    __shared__ double sh[8];
     const float pv = x[0];
     double acc[2] = {0.0, 0.0};
     const long long n4 = n / 4;
@@ -279,19 +212,14 @@ __global__ __launch_bounds__(kLossThreads) void znorm_sums_kernel(const float* _
         acc[1] += (double)a * a + (double)b * b + (double)c * c + (double)d * d;
     }
     if (blockIdx.x == 0 && threadIdx.x < (n & 3)) { const float a = x[n4 * 4 + threadIdx.x] - pv; acc[0] += a; acc[1] += (double)a * a; }
-    block_sum<2>(acc, sh);
+    block_sum(acc);
     if (threadIdx.x == 0) { part[2 * blockIdx.x] = acc[0]; part[2 * blockIdx.x + 1] = acc[1]; }
 }
 __global__ __launch_bounds__(256) void znorm_finalize_kernel(const double* __restrict__ part, int nblk, const float* __restrict__ x, long long n, float* __restrict__ mr) {
-    __shared__ double sh[8];
     double acc[2] = {0.0, 0.0};
-    for (int i = threadIdx.x; i < nblk; i += 256) { acc[0] += part[2 * i]; acc[1] += part[2 * i + 1]; }
-    block_sum<2>(acc, sh);
-    if (threadIdx.x == 0) {
-        const double md = acc[0] / (double)n, var = (acc[1] - acc[0] * md) / (double)(n - 1);
-        mr[0] = (float)((double)x[0] + md);
-        mr[1] = (float)(1.0 / sqrt(var));
-    }
+    partials_reduce<OpSum>(part, nblk, acc);
+    block_sum(acc);
+    if (threadIdx.x == 0) pivoted_mean_rstd((double)x[0], acc[0], acc[1], n, mr[0], mr[1]);
 }
 __global__ __launch_bounds__(256) void znorm_apply_kernel(const float* __restrict__ x, const float* __restrict__ mr, long long n, float* __restrict__ y) {
     const float m = mr[0], r = mr[1];
@@ -337,7 +265,6 @@ __global__ __launch_bounds__(256) void softmax_ch_bwd_kernel(const float* __rest
 // without a device-side flag and a synchronising read of it, and no label value ever indexes the logits or the class weights.
 __global__ __launch_bounds__(kLossThreads) void ce3d_fwd_kernel(const float* __restrict__ x, const int64_t* __restrict__ lab,
         const float* __restrict__ w, long long N, int K, long long S, double* __restrict__ part) {
-    __shared__ double sh[4];
     double acc[1] = {0.0};
     const long long total = N * S;
     for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
@@ -353,7 +280,7 @@ __global__ __launch_bounds__(kLossThreads) void ce3d_fwd_kernel(const float* __r
             acc[0] += (double)(w ? w[l] * nll : nll);
         }
     }
-    block_sum<1>(acc, sh);
+    block_sum(acc);
     if (threadIdx.x == 0) part[blockIdx.x] = acc[0];
 }
 __global__ __launch_bounds__(256) void ce3d_bwd_kernel(const float* __restrict__ x, const int64_t* __restrict__ lab, const float* __restrict__ w,
@@ -429,7 +356,7 @@ int mi355seg_dice_counts_i64(const int64_t* gt, const int64_t* pred, long long n
     hipStream_t st = (hipStream_t)stream;
     hipLaunchKernelGGL(dice_counts_kernel, dim3(nblk), dim3(kLossThreads), 0, st, gt, pred, numel, (long long*)ws);
     SEG_CHECK_LAUNCH();
-    hipLaunchKernelGGL(counts_finalize_kernel, dim3(1), dim3(256), 0, st, (const long long*)ws, nblk, counts);
+    launch_sums_finalize<4>((const long long*)ws, nblk, (long long*)counts, st);
     SEG_CHECK_LAUNCH();
     return MI355SEG_OK;
 }
@@ -456,7 +383,7 @@ int mi355seg_bce_argmax_dice_f32(const float* logits, const float* target, long 
     SEG_CHECK_LAUNCH();
     hipLaunchKernelGGL(bce_finalize_kernel, dim3(1), dim3(256), 0, st, lpart, nblk, (double)(N * K * S), loss);
     SEG_CHECK_LAUNCH();
-    hipLaunchKernelGGL(counts_finalize_kernel, dim3(1), dim3(256), 0, st, cpart, nblk, counts);
+    launch_sums_finalize<4>((const long long*)cpart, nblk, (long long*)counts, st);
     SEG_CHECK_LAUNCH();
     return MI355SEG_OK;
 }
@@ -470,7 +397,7 @@ int mi355seg_dice_sums_f32(const float* x, const float* t, long long numel, int 
     hipStream_t st = (hipStream_t)stream;
     hipLaunchKernelGGL(dice_sums_kernel, dim3(nblk), dim3(kLossThreads), 0, st, x, t, numel, apply_sigmoid, (double*)ws);
     SEG_CHECK_LAUNCH();
-    hipLaunchKernelGGL(sums_finalize5_kernel, dim3(1), dim3(256), 0, st, (const double*)ws, nblk, out5);
+    launch_sums_finalize<5>((const double*)ws, nblk, out5, st);
     SEG_CHECK_LAUNCH();
     return MI355SEG_OK;
 }
@@ -504,7 +431,7 @@ int mi355seg_dice_rows_f32(const float* x, const float* t, long long rows, long 
     hipStream_t st = (hipStream_t)stream;
     hipLaunchKernelGGL(dice_rows_kernel, dim3(nblk, (unsigned)rows), dim3(kLossThreads), 0, st, x, t, len, apply_sigmoid, p, vec, (double*)ws);
     SEG_CHECK_LAUNCH();
-    hipLaunchKernelGGL(dice_rows_finalize_kernel, dim3((unsigned)rows), dim3(256), 0, st, (const double*)ws, nblk, out);
+    launch_sums_finalize<5>((const double*)ws, nblk, out, st, (unsigned)rows);          // one block per row
     SEG_CHECK_LAUNCH();
     return MI355SEG_OK;
 }

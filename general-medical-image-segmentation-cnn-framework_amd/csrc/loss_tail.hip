@@ -8,10 +8,12 @@
 // pred.argmax(dim=1, keepdim=True) train.py:204; metric() utils/metric.py:20-75.  Focal (Lin et al.) and Tversky (Salehi et al.)
 // are the project's own definitions.
 #include "common.h"
+#include "loss_math.h"
 
 namespace seg {
 
 constexpr int kTailThreads = 256;
+static_assert(kTailThreads == kReduceThreads, "the block size of reduce.h");
 constexpr int kTailMaxBlocks = 2048;
 constexpr int kTailMaxClasses = 16;
 constexpr double kTailEps = 1e-5;            // DiceLoss.eplison, loss_function.py:119
@@ -19,17 +21,8 @@ constexpr double kTailEps = 1e-5;            // DiceLoss.eplison, loss_function.
 enum { TAIL_V_NONE = 0, TAIL_V_BCE = 1, TAIL_V_FOCAL = 2, TAIL_V_CE = 3 };
 enum { TAIL_R_NONE = 0, TAIL_R_DICE = 1, TAIL_R_TVERSKY = 2 };
 
-static int tail_grid(long long items) {
-    long long b = (items + kTailThreads - 1) / kTailThreads;
-    return (int)(b < 1 ? 1 : (b > kTailMaxBlocks ? kTailMaxBlocks : b));
-}
+static int tail_grid(long long items) { return stream_grid(items, kTailThreads, kTailMaxBlocks); }
 
-__device__ __forceinline__ float tail_bce_term(float x, float t) {      // loss.hip's bce_term
-    return fmaxf(x, 0.f) - x * t + log1pf(expf(-fabsf(x)));
-}
-__device__ __forceinline__ float tail_sigmoid(float x) { return 1.f / (1.f + expf(-x)); }
-// torch.argmax's order (loss.hip's nan_first_gt): the first maximum wins, a NaN beats every number, the first NaN wins
-__device__ __forceinline__ bool tail_gt(float v, float best) { return v > best || (v != v && best == best); }
 // q^g for g = 1, 2 (exact products) or any g >= 1
 __device__ __forceinline__ float tail_pow(float q, float g) { return g == 1.f ? q : (g == 2.f ? q * q : powf(q, g)); }
 // q^(g-1), g >= 1
@@ -46,18 +39,6 @@ __device__ __forceinline__ void tail_load(const float* __restrict__ p, float (&v
     }
 }
 
-// block-wide sum of one value, usable repeatedly (sh: one slot per wavefront); the result is valid in thread 0
-template <typename T>
-__device__ __forceinline__ T tail_block_sum(T v, T* sh) {
-    v = wave_sum(v);
-    __syncthreads();                                  // the previous round's reads of sh are done
-    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
-    __syncthreads();
-    T s = sh[0];
-    for (int w = 1; w < (int)(blockDim.x >> 6); ++w) s += sh[w];
-    return s;
-}
-
 // KT: the compile-time class capacity (K == KT for KT <= 4, K <= KT above); V: voxels per thread and trip (4: 16-byte loads, needs
 // S % 4 == 0 and aligned pointers).  part: per block 1 + 5 * K doubles (voxel-term sum; per class I, P, T, sum a^2, sum t^2);
 // cpart: per block the four counters.
@@ -65,8 +46,6 @@ template <int KT, int V>
 __global__ __launch_bounds__(kTailThreads) void loss_tail_fwd_kernel(const float* __restrict__ x, const float* __restrict__ t,
         long long N, int Krt, long long S, int vmode, float gamma, int64_t* __restrict__ mask,
         double* __restrict__ part, long long* __restrict__ cpart) {
-    __shared__ double shd[4];
-    __shared__ long long shc[4];
     const int K = KT <= 4 ? KT : Krt;
     double vacc = 0.0;
     double sacc[KT][5];
@@ -95,17 +74,17 @@ __global__ __launch_bounds__(kTailThreads) void loss_tail_fwd_kernel(const float
                 if (k < K) {
                     const float a = xv[k][j], b = tv[k][j];
                     if (k > 0) {
-                        if (tail_gt(a, bx)) { bx = a; ix = k; }
-                        if (tail_gt(b, bt)) { bt = b; it = k; }
+                        if (nan_first_gt(a, bx)) { bx = a; ix = k; }
+                        if (nan_first_gt(b, bt)) { bt = b; it = k; }
                     }
-                    const float p = tail_sigmoid(a);
+                    const float p = sigmoid(a);
                     sacc[k][0] += (double)(p * b); sacc[k][1] += (double)p; sacc[k][2] += (double)b;
                     sacc[k][3] += (double)(p * p); sacc[k][4] += (double)(b * b);
                     if (vmode == TAIL_V_BCE) {
-                        l += tail_bce_term(a, b);
+                        l += bce_term(a, b);
                     } else if (vmode == TAIL_V_FOCAL) {
                         const float q = p + b - 2.f * p * b;
-                        l += tail_pow(q, gamma) * tail_bce_term(a, b);
+                        l += tail_pow(q, gamma) * bce_term(a, b);
                     }
                 }
             if (vmode == TAIL_V_CE) {
@@ -130,20 +109,20 @@ __global__ __launch_bounds__(kTailThreads) void loss_tail_fwd_kernel(const float
     }
     const int R = 1 + 5 * K;
     double* prow = part + (long long)blockIdx.x * R;
-    double s = tail_block_sum(vacc, shd);
+    double s = block_reduce_one<OpSum, true>(vacc);
     if (threadIdx.x == 0) prow[0] = s;
 #pragma unroll
     for (int k = 0; k < KT; ++k)
         if (k < K) {
 #pragma unroll
             for (int j = 0; j < 5; ++j) {
-                s = tail_block_sum(sacc[k][j], shd);
+                s = block_reduce_one<OpSum, true>(sacc[k][j]);
                 if (threadIdx.x == 0) prow[1 + 5 * k + j] = s;
             }
         }
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
-        const long long c = tail_block_sum(cacc[j], shc);
+        const long long c = block_reduce_one<OpSum, true>(cacc[j]);
         if (threadIdx.x == 0) cpart[(long long)blockIdx.x * 4 + j] = c;
     }
 }
@@ -264,7 +243,7 @@ __global__ __launch_bounds__(kTailThreads) void loss_tail_bwd_kernel(const float
                 for (int k = 0; k < KT; ++k)
                     if (k < K) {
                         mm = fmaxf(mm, xv[k][j]);
-                        if (k > 0 && tail_gt(tv[k][j], bt)) { bt = tv[k][j]; it = k; }
+                        if (k > 0 && nan_first_gt(tv[k][j], bt)) { bt = tv[k][j]; it = k; }
                     }
                 float sum = 0.f;
 #pragma unroll
@@ -280,13 +259,13 @@ __global__ __launch_bounds__(kTailThreads) void loss_tail_bwd_kernel(const float
 #pragma unroll
                 for (int j = 0; j < V; ++j) {
                     const float a = xv[k][j], b = tv[k][j];
-                    const float p = tail_sigmoid(a), dp = p * (1.f - p);
+                    const float p = sigmoid(a), dp = p * (1.f - p);
                     float d = 0.f;
                     if (vmode == TAIL_V_BCE) {
                         d = (p - b) * sv;
                     } else if (vmode == TAIL_V_FOCAL) {
                         const float q = p + b - 2.f * p * b;
-                        d = (gamma * tail_pow_m1(q, gamma) * (1.f - 2.f * b) * dp * tail_bce_term(a, b) + tail_pow(q, gamma) * (p - b)) * sv;
+                        d = (gamma * tail_pow_m1(q, gamma) * (1.f - 2.f * b) * dp * bce_term(a, b) + tail_pow(q, gamma) * (p - b)) * sv;
                     } else if (vmode == TAIL_V_CE) {
                         d = sv * (expf(a - m[j]) * inv[j] - (k == lab[j] ? 1.f : 0.f));
                     }

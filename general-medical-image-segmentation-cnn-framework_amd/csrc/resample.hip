@@ -37,6 +37,7 @@
 namespace seg {
 
 constexpr int kRsThreads = 256;
+static_assert(kRsThreads == kReduceThreads, "the block size of reduce.h");
 constexpr int kRsMaxBlocks = 4096;                           // of the label kernel: one partial count each
 constexpr float kPole = -0.26794919243112270647f;            // sqrt(3) - 2
 constexpr float kAntiInit = 0.28867513459481288225f;         // z / (z^2 - 1)
@@ -339,7 +340,6 @@ template <typename T>
 __global__ __launch_bounds__(kRsThreads) void resample_labels_kernel(const T* __restrict__ x, int D, int H, int W, const int* __restrict__ base,
                                                                      const float* __restrict__ frac, int linear, T* __restrict__ y, int Do, int Ho,
                                                                      int Wo, unsigned total, long long* __restrict__ block_bad) {
-    __shared__ long long sh_bad[kRsThreads / 64];
     long long bad = 0;
     for (unsigned i = blockIdx.x * (unsigned)kRsThreads + threadIdx.x; i < total; i += gridDim.x * (unsigned)kRsThreads) {
         const unsigned ox = i % (unsigned)Wo, r1 = i / (unsigned)Wo, oy = r1 % (unsigned)Ho, r2 = r1 / (unsigned)Ho, oz = r2 % (unsigned)Do, c = r2 / (unsigned)Do;
@@ -370,25 +370,8 @@ __global__ __launch_bounds__(kRsThreads) void resample_labels_kernel(const T* __
         bad += ok ? 0 : 1;
         y[i] = best;
     }
-    bad = wave_sum(bad);
-    if ((threadIdx.x & 63) == 0) sh_bad[threadIdx.x >> 6] = bad;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        for (int w = 1; w < kRsThreads / 64; ++w) bad += sh_bad[w];
-        block_bad[blockIdx.x] = bad;
-    }
-}
-__global__ __launch_bounds__(kRsThreads) void resample_bad_finalize_kernel(const long long* __restrict__ block_bad, int nblk, long long* __restrict__ out) {
-    __shared__ long long sh_bad[kRsThreads / 64];
-    long long bad = 0;
-    for (int i = threadIdx.x; i < nblk; i += kRsThreads) bad += block_bad[i];
-    bad = wave_sum(bad);
-    if ((threadIdx.x & 63) == 0) sh_bad[threadIdx.x >> 6] = bad;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        for (int w = 1; w < kRsThreads / 64; ++w) bad += sh_bad[w];
-        out[0] = bad;
-    }
+    bad = block_reduce_one<OpSum>(bad);
+    if (threadIdx.x == 0) block_bad[blockIdx.x] = bad;
 }
 
 // ------------------------------------------------------------------------------------------------ (d) way back
@@ -458,11 +441,10 @@ static int resample_labels_launch(const char* who, const T* x, int C, int D, int
     hipStream_t st = (hipStream_t)stream;
     const unsigned total = (unsigned)((long long)C * Do * Ho * Wo);
     ProfScope ps(PF_POOL, 0.0, (double)sizeof(T) * ((double)C * D * H * W + total), st);
-    int nblk = cdiv(total, kRsThreads);
-    nblk = nblk > kRsMaxBlocks ? kRsMaxBlocks : nblk;
+    const int nblk = stream_grid(total, kRsThreads, kRsMaxBlocks);
     hipLaunchKernelGGL(resample_labels_kernel<T>, dim3(nblk), dim3(kRsThreads), 0, st, x, D, H, W, base, frac, mode, y, Do, Ho, Wo, total, (long long*)ws);
     SEG_CHECK_LAUNCH();
-    hipLaunchKernelGGL(resample_bad_finalize_kernel, dim3(1), dim3(kRsThreads), 0, st, (const long long*)ws, nblk, bad);
+    launch_sums_finalize<1>((const long long*)ws, nblk, bad, st);
     SEG_CHECK_LAUNCH();
     return MI355SEG_OK;
 }

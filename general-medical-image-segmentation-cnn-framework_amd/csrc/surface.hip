@@ -11,11 +11,9 @@
 namespace seg {
 
 constexpr int kSurfThreads = 256;
+static_assert(kSurfThreads == kReduceThreads, "the block size of reduce.h");
 
-static int surf_grid(long long items) {
-    long long b = (items + kSurfThreads - 1) / kSurfThreads;
-    return (int)(b < 1 ? 1 : (b > 4096 ? 4096 : b));
-}
+static int surf_grid(long long items) { return stream_grid(items, kSurfThreads, 4096); }
 
 // info[8] = n_edge(gt), n_edge(pred), box lo z, y, x, box hi z, y, x (hi exclusive) of edge(gt) | edge(pred); an empty union leaves
 // lo = extent and hi = 0
@@ -27,14 +25,10 @@ __global__ void edge_info_init_kernel(long long* __restrict__ info, int D, int H
     }
 }
 
-template <typename T>
-__device__ __forceinline__ T wave_reduce(T v, bool take_min, bool take_max) {
-    for (int o = kWave / 2; o > 0; o >>= 1) {
-        T u = __shfl_xor(v, o, kWave);
-        v = take_min ? (u < v ? u : v) : take_max ? (u > v ? u : v) : v + u;
-    }
-    return v;
-}
+// the operation per entry of info: counts add, the box's low corner takes the minimum, its high corner the maximum
+struct OpEdgeInfo {
+    static __device__ __forceinline__ long long apply(long long a, long long b, int j) { return j < 2 ? a + b : j < 5 ? (b < a ? b : a) : (b > a ? b : a); }
+};
 
 // edge(m) = m & ~erode6(m): a foreground voxel with a background face neighbour, outside the array = background
 // (scipy.ndimage.binary_erosion(m) ^ m, default cross, border_value = 0).  One pass: both edge maps, their counts, the joint box.
@@ -64,23 +58,26 @@ __global__ __launch_bounds__(kSurfThreads) void mask_edges_kernel(const int64_t*
             hi[0] = max(hi[0], z + 1); hi[1] = max(hi[1], y + 1); hi[2] = max(hi[2], x + 1);
         }
     }
-    // integer reductions: any order gives the same result.  Wave, then block through LDS, then one set of atomics per block
-    __shared__ long long sh[kSurfThreads / kWave][8];
-    for (int m = 0; m < 2; ++m) cnt[m] = wave_reduce(cnt[m], false, false);
-    for (int a = 0; a < 3; ++a) { lo[a] = wave_reduce(lo[a], true, false); hi[a] = wave_reduce(hi[a], false, true); }
-    if ((threadIdx.x & (kWave - 1)) == 0) {
-        long long* row = sh[threadIdx.x / kWave];
-        row[0] = cnt[0]; row[1] = cnt[1];
-        for (int a = 0; a < 3; ++a) { row[2 + a] = lo[a]; row[5 + a] = hi[a]; }
-    }
-    __syncthreads();
-    if (threadIdx.x < 8) {
+    // integer reductions: any order gives the same result.  The eight values of info in one pass, then one set of atomics per block
+    for (int m = 0; m < 2; ++m) cnt[m] = wave_sum(cnt[m]);
+    for (int a = 0; a < 3; ++a) { lo[a] = wave_reduce<OpMin>(lo[a]); hi[a] = wave_reduce<OpMax>(hi[a]); }      // (as ints)
+    long long v[8] = {cnt[0], cnt[1], lo[0], lo[1], lo[2], hi[0], hi[1], hi[2]};
+    block_combine<OpEdgeInfo>(v);
+    // lane j of the first wave commits entry j: the eight entries share a cache line, and eight lanes of one instruction are one
+    // request to it where eight instructions of thread 0 are eight (every block's atomics queue on that line)
+    if (threadIdx.x < kWave) {
+        long long mine = 0;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            // thread 0's value through the scalar unit (the whole first wave is here, so its first lane is thread 0)
+            const unsigned long long t0 = ((unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((int)(v[j] >> 32)) << 32) |
+                                          (unsigned)__builtin_amdgcn_readfirstlane((int)v[j]);
+            if ((int)threadIdx.x == j) mine = (long long)t0;
+        }
         const int j = threadIdx.x;
-        long long v = sh[0][j];
-        for (int w = 1; w < kSurfThreads / kWave; ++w) v = j < 2 ? v + sh[w][j] : j < 5 ? min(v, sh[w][j]) : max(v, sh[w][j]);
-        if (j < 2) { if (v) atomicAdd((unsigned long long*)&info[j], (unsigned long long)v); }
-        else if (j < 5) atomicMin(&info[j], v);       // a block without edge voxels holds lo = extent, hi = 0: no effect
-        else atomicMax(&info[j], v);
+        if (j < 2) { if (mine) atomicAdd((unsigned long long*)&info[j], (unsigned long long)mine); }
+        else if (j < 5) atomicMin(&info[j], mine);       // a block without edge voxels holds lo = extent, hi = 0: no effect
+        else if (j < 8) atomicMax(&info[j], mine);
     }
 }
 
@@ -247,29 +244,8 @@ __global__ __launch_bounds__(kSurfThreads) void confusion_counts_kernel(const in
         acc[6] += (g - p < 1) ? 0 : g;
         acc[7] += 1 - (g | p);
     }
-    __shared__ long long sh[kSurfThreads / kWave][8];
-    for (int j = 0; j < 8; ++j) acc[j] = wave_reduce(acc[j], false, false);
-    if ((threadIdx.x & (kWave - 1)) == 0) for (int j = 0; j < 8; ++j) sh[threadIdx.x / kWave][j] = acc[j];
-    __syncthreads();
-    if (threadIdx.x < 8) {
-        long long v = 0;
-        for (int w = 0; w < kSurfThreads / kWave; ++w) v += sh[w][threadIdx.x];
-        part[(long long)blockIdx.x * 8 + threadIdx.x] = v;
-    }
-}
-
-__global__ __launch_bounds__(kSurfThreads) void confusion_finalize_kernel(const long long* __restrict__ part, int nblk, int64_t* __restrict__ counts) {
-    __shared__ long long sh[kSurfThreads / 8][8];
-    const int j = threadIdx.x % 8, q = threadIdx.x / 8;
-    long long v = 0;
-    for (int i = q; i < nblk; i += kSurfThreads / 8) v += part[(long long)i * 8 + j];
-    sh[q][j] = v;
-    __syncthreads();
-    if (threadIdx.x < 8) {
-        long long t = 0;
-        for (int w = 0; w < kSurfThreads / 8; ++w) t += sh[w][threadIdx.x];
-        counts[threadIdx.x] = t;
-    }
+    block_sum(acc);
+    if (threadIdx.x == 0) for (int j = 0; j < 8; ++j) part[(long long)blockIdx.x * 8 + j] = acc[j];
 }
 
 template <typename InT>
@@ -363,7 +339,7 @@ int mi355seg_confusion_counts_i64(const int64_t* gt, const int64_t* pred, long l
     SEG_CHECK_WS(mi355seg_confusion_counts_ws_bytes(numel), ws_bytes);
     hipLaunchKernelGGL(confusion_counts_kernel, dim3(nblk), dim3(kSurfThreads), 0, st, gt, pred, numel, (long long*)ws);
     SEG_CHECK_LAUNCH();
-    hipLaunchKernelGGL(confusion_finalize_kernel, dim3(1), dim3(kSurfThreads), 0, st, (const long long*)ws, nblk, counts);
+    launch_sums_finalize<8>((const long long*)ws, nblk, (long long*)counts, st);
     SEG_CHECK_LAUNCH();
     return MI355SEG_OK;
 }

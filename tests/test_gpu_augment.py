@@ -103,7 +103,13 @@ def _corners(shape, ps):
 
 
 # ----------------------------------------------------------------------------- statistics
-@pytest.mark.parametrize("C,shape,offset,scale", [(3, (41, 67, 53), -300.0, 1.0), (1, (45, 51, 64), 0.0, 1.0), (4, (33, 40, 37), 40.0, 12.0)])
+# the block regimes of the two-stage reduction (256 threads, at most 1024 blocks; the 16-byte path has a quarter of the work items):
+# one block with fewer than 64 live threads, more than 256 blocks (the finalize's ragged second trip), past the cap with a ragged tail
+STATS_REGIMES = [(1, (3, 4, 5), 0.0, 1.0), (1, (3, 4, 8), 0.0, 1.0), (1, (41, 41, 41), 0.0, 1.0), (1, (64, 64, 68), 0.0, 1.0),
+                 (1, (65, 65, 65), 0.0, 1.0), (1, (104, 104, 104), 0.0, 1.0)]
+
+
+@pytest.mark.parametrize("C,shape,offset,scale", [(3, (41, 67, 53), -300.0, 1.0), (1, (45, 51, 64), 0.0, 1.0), (4, (33, 40, 37), 40.0, 12.0)] + STATS_REGIMES)
 def test_statistics_against_fp64(seg, C, shape, offset, scale):
     """mu, rho and min V of a visit: odd sizes (scalar path) and W % 4 == 0 (16-byte path), several channels, a CT-like offset (mean
     -300, std 1); two runs bitwise equal."""

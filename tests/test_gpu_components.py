@@ -283,6 +283,17 @@ def test_filter_components_equals_numpy_on_scipy_labels(seg, conn, density):
     assert got.data_ptr() == alias.data_ptr()
 
 
+@pytest.mark.parametrize("shape,conn,density", [((65, 64, 65), 26, 0.31), ((130, 180, 180), 6, 0.10)], ids=["65x64x65", "130x180x180"])
+def test_statistics_and_filter_past_one_trip_of_the_finalize_and_past_the_grid_cap(seg, shape, conn, density):
+    """the statistics pass runs ceil(voxels / 1024) blocks, at most 4096: 265 blocks (the finalize's second trip over the partials is
+    ragged) and 4114 -> 4096 (the grid-stride walk makes a ragged second trip); the filter's removed count, one block per 512
+    voxels, runs 529 blocks and 8227 -> 4096.  The one-block regime is in SHAPES."""
+    m = bernoulli(shape, density, 7)
+    o = check(seg.functional, m, conn, f"bernoulli {density}")
+    _check_filter(seg.functional, o, _dev(m), conn, 3, 0)
+    _check_filter(seg.functional, o, _dev(m), conn, 0, 2)
+
+
 def test_filter_entry_point_with_out_aliasing_mask_and_odd_alignment(seg):
     """the C entry point itself: out == mask, and a mask that starts 8 bytes off a 16-byte boundary (the scalar path)"""
     F = seg.functional

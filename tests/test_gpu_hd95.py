@@ -149,6 +149,16 @@ def test_confusion_counts_equal_the_reference_fixture(seg):
         assert c[:4] == g[n + "/counts"].tolist() and [float(v) for v in c[4:]] == g[n + "/tp_fp_fn_tn"].tolist(), n
 
 
+@pytest.mark.parametrize("numel", [37, 70001, 1100003])
+def test_confusion_counts_equal_torch_in_every_block_regime(seg, numel):
+    """the grid is ceil(numel / 256) blocks, at most 4096: one block with fewer than 64 live threads; 274 blocks, so the finalize
+    makes a ragged second trip over the partials; past the cap with a ragged grid-stride tail.  Integers: equal to torch on the CPU."""
+    gen = torch.Generator().manual_seed(numel)
+    g, p = (torch.randint(0, 2, (numel,), generator=gen, dtype=torch.int64) for _ in range(2))
+    want = [g.sum(), p.sum(), ((g & p) != 0).sum(), ((g | p) != 0).sum(), (g & p).sum(), (p * (p - g >= 1)).sum(), (g * (g - p >= 1)).sum(), (1 - (g | p)).sum()]
+    assert seg.functional.confusion_counts(g.cuda(), p.cuda()).cpu().tolist() == [int(v) for v in want]
+
+
 def test_metric_without_spacing_is_untouched(seg):
     from mi355seg.utils.metric import metric
     g = np.load(os.path.join(GOLDEN, "metric.npz"))

@@ -247,9 +247,11 @@ def grade(tag, got, ref, bound):
 
 
 # ---------------------------------------------------------------------------------------------- moments
-@pytest.mark.parametrize("n,offset", [(7, 0.0), (1021, 0.0), (100003, 1000.0), (4428244, 1000.0), (1025 * 33, -300.0)])
+@pytest.mark.parametrize("n,offset", [(7, 0.0), (1021, 0.0), (100003, 1000.0), (4428244, 1000.0), (1025 * 33, -300.0), (300003, 1000.0), (2200003, 1000.0)])
 def test_moments_exact_maps(seg, n, offset):
-    """identity and clamp, with and without a mask: count exact, mean and std within the summation bound of the file's docstring"""
+    """identity and clamp, with and without a mask: count exact, mean and std within the summation bound of the file's docstring.
+    The grid is ceil((n / 4 + 1) / 256) blocks, at most 2048: n = 7 is one block with fewer than 64 live threads, 300003 gives 293
+    blocks (the finalize's ragged second trip over the partials), 2200003 passes the cap with a ragged tail and n % 4 = 3."""
     F = seg.functional
     from mi355seg import intensity as I
     x = gauss(n, 19 + n) + np.float32(offset)

@@ -373,7 +373,7 @@ ROWS = ([(R, L) for R in (1, 2, 7) for L in (1, 3, 4, 1023, 4097, 70001)] + [(20
 @pytest.mark.parametrize("R,L", ROWS, ids=[f"R{r}_L{l}" for r, l in ROWS])
 def test_dice_rows(seg, R, L):
     """dice_rows_kernel (float4 path; the scalar path for R > 1 with L % 4 != 0; one block per row when R > 2048; slices of
-    65,535 rows), dice_rows_finalize and dice_rows_bwd for p in {1, 2, 3, 1.5}, with and without the sigmoid, under a full random
+    65,535 rows), its one-block-per-row finalize and dice_rows_bwd for p in {1, 2, 3, 1.5}, with and without the sigmoid, under a full random
     fp64 upstream [R, 5] (columns 2 and 4 ignored by the gradient)."""
     F = seg.functional
     x0 = _randn((R, L), 23 + R + L)

@@ -251,6 +251,21 @@ def test_labels_exact_tie_gives_the_lowest_class_and_bad_labels_raise(seg):
         assert int(bad) == 1
 
 
+@pytest.mark.parametrize("shape", [(3, 3, 5), (41, 41, 41), (104, 101, 100)], ids=lambda s: "x".join(map(str, s)))
+def test_bad_label_count_in_every_block_regime(seg, shape):
+    """the label kernel runs one block per 256 output voxels, at most 4096, and the count is reduced in two stages: one block with
+    fewer than 64 live threads, 270 blocks (the finalize's ragged second trip), 4104 -> 4096 (a ragged grid-stride tail).  Bad labels
+    at the first, the last and one interior voxel: exactly 3, and the volume itself comes back."""
+    F = seg.functional
+    y = label_volume("blocks16", shape, 4)
+    y[0, 0, 0], y[-1, -1, -1], y[shape[0] // 2, shape[1] // 3, 1] = 16.0, -1.0, 17.0
+    same = F.ResampleTables(shape, shape, (1.0, 1.0, 1.0), 0, torch.device("cuda", 0))
+    for t in (torch.float32, torch.int64):
+        yd = dev(y).to(t)
+        got, bad = F.resample3d_labels(yd, same, "nearest")
+        assert int(bad) == 3 and torch.equal(got, yd)
+
+
 def blob(shape):
     z, y, x = np.meshgrid(*[np.arange(n, dtype=np.float64) for n in shape], indexing="ij")
     r = ((z - 13.3) / 9.0) ** 2 + ((y - 15.6) / 11.0) ** 2 + ((x - 14.2) / 7.5) ** 2 + 0.08 * np.sin(0.9 * x) * np.cos(0.7 * y)
