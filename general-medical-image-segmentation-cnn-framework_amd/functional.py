@@ -2217,6 +2217,144 @@ def loss_tail(logits, target, spec):
     return loss_tail_full(logits, target, spec)[:4]
 
 
+# ----------------------------------------------------------------------------- soft-clDice (config.cldice_weight; csrc/cldice.hip)
+CLDICE_ITERS, CLDICE_SMOOTH = 3, 1.0
+MAX_SKEL_ITERS = 32
+
+
+def checked_skel_iters(iters, what):
+    """The C entry points' refusal of ``iters``, as ValueError before anything reaches the device."""
+    if isinstance(iters, bool) or not isinstance(iters, (int, np.integer)) or not 1 <= iters <= MAX_SKEL_ITERS:
+        raise ValueError(f"{what}: iters must be an integer in 1..{MAX_SKEL_ITERS}, got {iters!r}")
+    return int(iters)
+
+
+def _skel_volume(x, what):
+    _require_cuda(x, what)
+    if x.dim() != 5:
+        raise Mi355SegError(f"{what}: expected [N,C,D,H,W], got {tuple(x.shape)}")
+    return x.contiguous()
+
+
+def _skel_forward(x, iters):
+    """Levels 0 .. iters over the contiguous volume x: (level stack, skeleton).  The stack (E_1 .. E_{iters+1} and the skeleton after
+    every level) is what the backward reads; the skeleton is a view of its last slot, which the backward does not read."""
+    L = lib()
+    N, C, D, H, W = x.shape
+    nbytes = L.query("mi355seg_soft_skel_ws_bytes", N * C, D, H, W, iters)
+    stack = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=x.device)
+    for j in range(iters + 1):
+        L.call("mi355seg_soft_skel_step_fwd_f32", _p(x), N * C, D, H, W, iters, j, _p(stack), nbytes, _stream())
+    slot = nbytes // (2 * (iters + 1))
+    return stack, stack[(2 * iters + 1) * slot:][:x.numel() * 4].view(torch.float32).view(x.shape)
+
+
+def _skel_backward(x, stack, iters, g):
+    """d(sum g * soft_skel(x)) / dx: levels iters .. 0, one launch each; the two gradients ping-pong between two buffers each."""
+    L = lib()
+    N, C, D, H, W = x.shape
+    ge, gs = (torch.empty_like(x), torch.empty_like(x)), (torch.empty_like(x), torch.empty_like(x))
+    g_skel, g_next = g, None
+    for j in range(iters, -1, -1):
+        out_e, out_s = ge[j & 1], (gs[j & 1] if j else None)
+        L.call("mi355seg_soft_skel_step_bwd_f32", _p(x), _p(g_skel), _p(g_next), _p(out_e), _p(out_s), N * C, D, H, W, iters, j,
+               _p(stack), stack.numel(), _stream())
+        g_skel, g_next = out_s, out_e
+    return g_next
+
+
+class _SoftSkeleton(Function):
+    @staticmethod
+    def forward(ctx, x, iters):
+        x = _skel_volume(x, "soft_skeleton input")
+        stack, skel = _skel_forward(x, iters)
+        if not ctx.needs_input_grad[0]:
+            return skel.clone()                  # (nothing to keep: the stack goes)
+        ctx.save_for_backward(x, stack)
+        ctx.iters = iters
+        return skel
+
+    @staticmethod
+    def backward(ctx, g):
+        x, stack = ctx.saved_tensors
+        return _skel_backward(x, stack, ctx.iters, g.contiguous().to(torch.float32)), None
+
+
+def soft_skeleton(x, iters=CLDICE_ITERS):
+    """The soft skeleton of clDice (Shit et al., CVPR 2021) of a float32 volume [N,C,D,H,W] on the device, one launch per level
+    forward and one backward: E_{j+1} = erode(E_j), delta = relu(E_j - dilate(E_{j+1})), skel += relu(delta - skel * delta) for
+    j = 0 .. iters.  The forward has the bits of the ATen fp32 composition; at ties the backward routes a minimum's or maximum's
+    gradient to the candidate with the lowest raster index."""
+    return _SoftSkeleton.apply(x, checked_skel_iters(iters, "soft_skeleton"))
+
+
+class _SoftClDice(Function):
+    """(cldice fp32 scalar, fp64[3] = cldice, tprec, tsens).  The coefficients of the backward stay on the device (coef), as
+    _LossTail's do: capturable in a HIP graph."""
+
+    @staticmethod
+    def forward(ctx, logits, target, iters, smooth):
+        _require_cuda(logits, "soft_cldice input")
+        logits, target = logits.contiguous(), target.to(torch.float32).contiguous()
+        if logits.shape != target.shape:
+            raise ValueError(f"Target size ({tuple(target.shape)}) must be the same as input size ({tuple(logits.shape)})")
+        if logits.dim() != 5:
+            raise Mi355SegError(f"soft_cldice: expected [N,K,D,H,W], got {tuple(logits.shape)}")
+        N, K = logits.shape[:2]
+        S = logits[0, 0].numel()
+        dev = logits.device
+        L = lib()
+        shape = (N, K - (1 if K > 1 else 0)) + tuple(logits.shape[2:])
+        P, T = torch.empty(shape, dtype=torch.float32, device=dev), torch.empty(shape, dtype=torch.float32, device=dev)
+        L.call("mi355seg_cldice_probs_f32", _p(logits), _p(target), N, K, S, _p(P), _p(T), _stream())
+        stack, skel_p = _skel_forward(P, iters)
+        skel_t = _skel_forward(T, iters)[1].clone()           # (the target's skeleton has no backward: its stack goes)
+        n = P.numel()
+        ws = workspace(L.query("mi355seg_cldice_ws_bytes", n), dev)
+        loss = torch.empty((), dtype=torch.float32, device=dev)
+        parts, coef = torch.empty(3, dtype=torch.float64, device=dev), torch.empty(3, dtype=torch.float64, device=dev)
+        L.call("mi355seg_cldice_sums_f32", _p(skel_p), _p(skel_t), _p(P), _p(T), n, _p(ws), ws.numel(), _stream())
+        L.call("mi355seg_cldice_finalize", _p(ws), ws.numel(), n, smooth, _p(loss), _p(parts), _p(coef), _stream())
+        ctx.save_for_backward(P, T, skel_t, stack, coef)
+        ctx.iters, ctx.dims = iters, (N, K, S)
+        ctx.mark_non_differentiable(parts)
+        ctx.set_materialize_grads(False)
+        return loss, parts
+
+    @staticmethod
+    def backward(ctx, g, _gparts):
+        if g is None:
+            return None, None, None, None
+        P, T, skel_t, stack, coef = ctx.saved_tensors
+        N, K, S = ctx.dims
+        L = lib()
+        g = g.contiguous().to(torch.float32)
+        g_skel = torch.empty_like(P)
+        L.call("mi355seg_cldice_bwd_head_f32", _p(T), _p(coef), P.numel(), _p(g_skel), _stream())
+        g_p = _skel_backward(P, stack, ctx.iters, g_skel)
+        d = torch.empty((N, K) + tuple(P.shape[2:]), dtype=torch.float32, device=P.device)
+        L.call("mi355seg_cldice_bwd_tail_f32", _p(g_p), _p(skel_t), _p(P), _p(coef), _p(g), N, K, S, _p(d), _stream())
+        return d, None, None, None
+
+
+def soft_cldice_full(logits, target, iters=CLDICE_ITERS, smooth=CLDICE_SMOOTH):
+    """soft_cldice with the term itself in fp64: (cldice fp32 scalar with the autograd edge, fp64[3] = cldice, tprec, tsens)."""
+    iters = checked_skel_iters(iters, "soft_cldice")
+    if isinstance(smooth, bool) or not isinstance(smooth, (int, float)) or not smooth > 0:
+        raise ValueError(f"soft_cldice: smooth must be a number > 0, got {smooth!r}")
+    return _SoftClDice.apply(logits, target, iters, float(smooth))
+
+
+def soft_cldice(logits, target, iters=CLDICE_ITERS, smooth=CLDICE_SMOOTH):
+    """The soft-clDice term on logits and target [N,K,D,H,W]: (cldice, parts).  With P = sigmoid(logits[:, 1:]), T = target[:, 1:]
+    (the single channel when K = 1), S_P = soft_skeleton(P, iters), S_T = soft_skeleton(T, iters): tprec = (sum S_P T + smooth) /
+    (sum S_P + smooth), tsens = (sum S_T P + smooth) / (sum S_T + smooth), cldice = 1 - 2 tprec tsens / (tprec + tsens), sums over
+    batch, channels and voxels.  ``cldice`` is a float32 scalar carrying the autograd edge to ``logits``; ``parts`` is fp64[2] =
+    (tprec, tsens), non-differentiable."""
+    loss, parts = soft_cldice_full(logits, target, iters, smooth)
+    return loss, parts[1:]
+
+
 def two_channel_gt(gt):
     """train.py:190-193 as one kernel: cat([(gt == 0), gt], dim=1) as float for a single-channel label volume."""
     if not gt.is_cuda:

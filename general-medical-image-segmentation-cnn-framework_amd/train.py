@@ -23,13 +23,15 @@ from .registry import build_model
 from .models.three_d.IS import set_band_split
 
 
-LOSS_KEYS = ("loss_weights", "focal_gamma", "tversky_alpha", "tversky_beta")
+LOSS_KEYS = ("loss_weights", "focal_gamma", "tversky_alpha", "tversky_beta", "cldice_weight", "cldice_iters", "cldice_smooth")
 
 
 def parse_loss(config):
     """``config.loss`` -> the criterion of the run: None (the live BCE path of train.py:115, engine.train_step's default) when the key
     is absent, empty or "bce"; otherwise a utils.loss_function.CompoundLoss built from ``config.loss_weights=wv,wr``,
-    ``config.focal_gamma``, ``config.tversky_alpha`` and ``config.tversky_beta`` (each only with a mode that has that term)."""
+    ``config.focal_gamma``, ``config.tversky_alpha`` and ``config.tversky_beta`` (each only with a mode that has that term), and the
+    soft-clDice term's ``config.cldice_weight`` (>= 0; 0 = no term), ``config.cldice_iters`` (1..32) and ``config.cldice_smooth``
+    (> 0), which go with any compound mode."""
     from .utils.loss_function import CompoundLoss
     get = lambda k: config.get(k) if hasattr(config, "get") else getattr(config, k, None)
     mode = get("loss")
@@ -40,8 +42,10 @@ def parse_loss(config):
     given = {k: get(k) for k in LOSS_KEYS if not _absent(get(k))}
     has = {"loss_weights": mode is not None, "focal_gamma": mode in ("focal", "dice_focal"),
            "tversky_alpha": mode == "tversky", "tversky_beta": mode == "tversky"}
-    needs = {"loss_weights": "a compound mode (" + ", ".join(F.LOSS_MODES) + ")", "focal_gamma": "focal or dice_focal",
-             "tversky_alpha": "tversky", "tversky_beta": "tversky"}
+    compound = "a compound mode (" + ", ".join(F.LOSS_MODES) + ")"
+    needs = {"loss_weights": compound, "focal_gamma": "focal or dice_focal", "tversky_alpha": "tversky", "tversky_beta": "tversky"}
+    for k in ("cldice_weight", "cldice_iters", "cldice_smooth"):
+        has[k], needs[k] = mode is not None, compound
     for k, v in given.items():
         if not has[k]:
             raise ValueError(f"config.{k} must be given only with config.loss = {needs[k]}, got {v!r} with config.loss={mode or 'bce'}")
@@ -76,6 +80,19 @@ def parse_loss(config):
     for k in ("tversky_alpha", "tversky_beta"):
         if k in given:
             kw[k] = number(k, "a number >= 0", lambda v: v >= 0)
+    if "cldice_weight" in given:
+        kw["cldice_weight"] = number("cldice_weight", "a number >= 0", lambda v: v >= 0)
+    if "cldice_smooth" in given:
+        kw["cldice_smooth"] = number("cldice_smooth", "a number > 0", lambda v: v > 0)
+    if "cldice_iters" in given:
+        v = given["cldice_iters"]
+        try:
+            v = int(v) if isinstance(v, str) else v
+        except ValueError:
+            v = None
+        if isinstance(v, bool) or not isinstance(v, int) or not 1 <= v <= F.MAX_SKEL_ITERS:
+            raise ValueError(f"config.cldice_iters must be an integer in 1..{F.MAX_SKEL_ITERS}, got {given['cldice_iters']!r}")
+        kw["cldice_iters"] = v
     if mode == "tversky":
         a, b = kw.get("tversky_alpha", F.TVERSKY_ALPHA), kw.get("tversky_beta", F.TVERSKY_BETA)
         if not a + b > 0:
@@ -168,8 +185,11 @@ def train(config, model, logger):
             dice_meter.update(out["dice"], x.size(0))
             if scalars:
                 row = {"iteration": iteration, "Training/Loss": loss_meter.val, "Training/dice": dice_meter.val}
-                if criterion is not None:                       # a compound loss: its two terms, unweighted
-                    row["Training/loss_voxel"], row["Training/loss_region"] = out["loss_terms"].tolist()
+                if criterion is not None:                       # a compound loss: its terms, unweighted
+                    terms = out["loss_terms"].tolist()
+                    row["Training/loss_voxel"], row["Training/loss_region"] = terms[:2]
+                    if len(terms) > 2:                          # config.cldice_weight > 0
+                        row["Training/loss_cldice"] = terms[2]
                 scalars.write(json.dumps(row) + "\n")
                 scalars.flush()
             logger.info(f"\nEpoch: {epoch} Batch: {i}, train time: {time.time() - t0:.3f}s\nLoss: {loss_meter.val}\nDice: {dice_meter.val}\n")

@@ -111,18 +111,37 @@ class CompoundLoss(nn.Module):
     DiceLoss (loss_function.py:121-130); focal (Lin et al., exponent ``focal_gamma``, no alpha balancing) and tversky (Salehi et
     al., ``tversky_alpha`` on false positives, ``tversky_beta`` on false negatives, per class over the batch) are the project's
     own.  ``weights`` = (voxel, region).  ``forward`` returns the scalar loss (an ordinary criterion); ``tail`` returns (loss,
-    mask, counts, terms), which engine.train_step uses in place of criterion + two argmaxes + dice_counts."""
+    mask, counts, terms), which engine.train_step uses in place of criterion + two argmaxes + dice_counts.
+    ``cldice_weight`` > 0 adds the soft-clDice term (functional.soft_cldice with ``cldice_iters`` and ``cldice_smooth``; DESIGN.md
+    4.20): loss = tail loss + cldice_weight * cldice and ``terms`` gains a third entry, the unweighted cldice.  With the weight 0
+    the object is what it is without the three arguments: the same launches and the same bits."""
 
-    def __init__(self, mode, weights=(1, 1), focal_gamma=2.0, tversky_alpha=0.3, tversky_beta=0.7):
+    def __init__(self, mode, weights=(1, 1), focal_gamma=2.0, tversky_alpha=0.3, tversky_beta=0.7,
+                 cldice_weight=0.0, cldice_iters=F.CLDICE_ITERS, cldice_smooth=F.CLDICE_SMOOTH):
         super().__init__()
         self.mode = mode
         self.spec = F.LossSpec.from_mode(mode, weights, focal_gamma, tversky_alpha, tversky_beta)
+        number = lambda v: not isinstance(v, bool) and isinstance(v, (int, float))
+        if not number(cldice_weight) or not cldice_weight >= 0:
+            raise ValueError(f"cldice_weight must be a number >= 0, got {cldice_weight!r}")
+        if not number(cldice_smooth) or not cldice_smooth > 0:
+            raise ValueError(f"cldice_smooth must be a number > 0, got {cldice_smooth!r}")
+        self.cldice_weight, self.cldice_smooth = float(cldice_weight), float(cldice_smooth)
+        self.cldice_iters = F.checked_skel_iters(cldice_iters, "cldice_iters")
 
     def tail(self, pred, target):
-        return F.loss_tail(pred, target, self.spec)
+        out = F.loss_tail(pred, target, self.spec)
+        if not self.cldice_weight > 0:
+            return out
+        loss, mask, counts, terms = out
+        cl, parts = F.soft_cldice_full(pred, target, self.cldice_iters, self.cldice_smooth)
+        return loss + self.cldice_weight * cl, mask, counts, torch.cat([terms, parts[:1]])
 
     def forward(self, pred, target):
         return self.tail(pred, target)[0]
 
     def extra_repr(self):
-        return f"mode={self.mode!r}, spec={tuple(self.spec)!r}"
+        s = f"mode={self.mode!r}, spec={tuple(self.spec)!r}"
+        if self.cldice_weight > 0:
+            s += f", cldice=(weight={self.cldice_weight!r}, iters={self.cldice_iters!r}, smooth={self.cldice_smooth!r})"
+        return s

@@ -594,6 +594,54 @@ int mi355seg_loss_tail_bwd_f32(const float* logits, const float* target, const d
                                long long N, int K, long long S, int voxel_term, int region_term, float gamma,
                                float* dlogits, void* stream);
 
+/* Soft-clDice loss term (csrc/cldice.hip; no reference line in this project's model: the official clDice of Shit
+ * et al., CVPR 2021 -- soft_skeleton.py's soft_erode / soft_dilate / soft_open / soft_skel and cldice.py's soft_cldice).
+ * Volumes are [NC, D, H, W] fp32, W fastest, at most 2^31 - 1 voxels per call; iters in 1..32.
+ *
+ * The soft skeleton (replaces soft_skel's chain of max_pool3d, minima, subtractions and ReLUs) is iters + 1 levels j = 0 .. iters:
+ *   E_{j+1} = erode(E_j) (minimum over the voxel and its 6 face neighbours), delta = relu(E_j - dilate(E_{j+1})) (dilate: maximum
+ *   over the 3x3x3 box), skel = skel + relu(delta - skel * delta), with E_0 = x and skel = 0; voxels outside the volume never take
+ *   part.  The forward has the bits of that composition in ATen fp32 (no FMA contraction).
+ * mi355seg_soft_skel_ws_bytes: the size of the level stack the caller keeps from the forward to the backward, 2 (iters + 1) volumes
+ *   (E_1 .. E_{iters+1}, then the skeleton after each level; each slot rounded up to 256 bytes; 0 for bad arguments).  The finished
+ *   skeleton is the LAST slot, at byte offset (2 iters + 1) * slot.
+ * mi355seg_soft_skel_step_fwd_f32: level j, one launch: reads E_j (x for j = 0) and the skeleton so far (taken as zero for j = 0:
+ *   no memset), writes E_{j+1} and the new skeleton into the stack.  Call it for j = 0, 1, .., iters.
+ * mi355seg_soft_skel_step_bwd_f32: level j of the backward, one launch in gather form, called for j = iters, .., 1, 0:
+ *   g_skel_out = the gradient of the skeleton after level j, g_e_next = the gradient later levels sent to E_{j+1} (NULL: zero, as at
+ *   j = iters); writes g_e = the gradient of E_j and g_skel_in = the gradient of the skeleton before level j (not written and may be
+ *   NULL at j = 0).  Arg-max and arg-min are recomputed from the stack; a tie routes the whole gradient to the candidate with the
+ *   lowest raster index (z, then y, then x) -- what ATen does for the 27-maximum, not what it does for the minimum of three pools.
+ *   An output must not alias an input.
+ * mi355seg_cldice_probs_f32: P = sigmoid(logits[:, c0:]), T = target[:, c0:] as contiguous [N, K - c0, S], c0 = 1 for K > 1 (the
+ *   background channel is left out), 0 for K = 1 (replaces y_pred[:, 1:] / y_true[:, 1:] of soft_dice_cldice).
+ * mi355seg_cldice_sums_f32: sum S_P T, sum S_P, sum S_T P, sum S_T over n elements as fp64 partials in fixed order, one pass
+ *   (replaces the four torch.sum of soft_cldice); ws of mi355seg_cldice_ws_bytes(n).
+ * mi355seg_cldice_finalize: one block: tprec = (sum S_P T + smooth) / (sum S_P + smooth), tsens = (sum S_T P + smooth) /
+ *   (sum S_T + smooth), cldice = 1 - 2 tprec tsens / (tprec + tsens); loss fp32[1] = cldice, parts fp64[3] = (cldice, tprec, tsens),
+ *   coef fp64[3] = (a, b, c) of the backward, all on the device (nothing passes through the host: capturable in a HIP graph).
+ * mi355seg_cldice_bwd_head_f32: g_skel = a T + b, the gradient of cldice with respect to S_P.
+ * mi355seg_cldice_bwd_tail_f32: dlogits[:, c0:] = gscale[0] (g_p + c S_T) P (1 - P) with g_p the gradient that the skeleton's
+ *   backward returned for P; channel 0 (K > 1) gets zeros.  dlogits is [N, K, S].
+ * Refused before any launch, with mi355seg_last_error: null pointers, non-positive extents, more than 2^31 - 1 elements, iters
+ * outside 1..32, j outside 0..iters, smooth <= 0, a workspace that is too small. */
+size_t mi355seg_soft_skel_ws_bytes(long long NC, int D, int H, int W, int iters);
+int mi355seg_soft_skel_step_fwd_f32(const float* x, long long NC, int D, int H, int W, int iters, int j,
+                                    void* ws, size_t ws_bytes, void* stream);
+int mi355seg_soft_skel_step_bwd_f32(const float* x, const float* g_skel_out, const float* g_e_next, float* g_e, float* g_skel_in,
+                                    long long NC, int D, int H, int W, int iters, int j,
+                                    const void* ws, size_t ws_bytes, void* stream);
+int mi355seg_cldice_probs_f32(const float* logits, const float* target, long long N, int K, long long S,
+                              float* P, float* T, void* stream);
+size_t mi355seg_cldice_ws_bytes(long long n);
+int mi355seg_cldice_sums_f32(const float* skel_p, const float* skel_t, const float* P, const float* T, long long n,
+                             void* ws, size_t ws_bytes, void* stream);
+int mi355seg_cldice_finalize(const void* ws, size_t ws_bytes, long long n, float smooth,
+                             float* loss, double* parts, double* coef, void* stream);
+int mi355seg_cldice_bwd_head_f32(const float* T, const double* coef, long long n, float* g_skel, void* stream);
+int mi355seg_cldice_bwd_tail_f32(const float* g_p, const float* skel_t, const float* P, const double* coef, const float* gscale,
+                                 long long N, int K, long long S, float* dlogits, void* stream);
+
 /* Sum-type reductions for the library losses (loss_function.py:61-185):
  * out[0]=sum(a*b) out[1]=sum(a) out[2]=sum(b) out[3]=sum(a*a) out[4]=sum(b*b), a = sigmoid(x) if
  * apply_sigmoid else x.  Deterministic wavefront-shuffle + two-stage reduce. */
