@@ -133,6 +133,8 @@ __device__ __forceinline__ float ld1(const float* p) { return *p; }
 __device__ __forceinline__ float ld1(const bf16* p) { return (float)*p; }
 __device__ __forceinline__ void st1(float* p, float v) { *p = v; }
 __device__ __forceinline__ void st1(bf16* p, float v) { *p = (bf16)v; }
+// the value a store of v leaves in a tensor of storage type T, as a float (T = float: v itself)
+template <typename T> __device__ __forceinline__ float as_stored(float v) { return (float)(T)v; }
 // x = h + m + l with three bf16 parts (24 mantissa bits): the operand split of the bf16x6 convolutions
 __device__ __forceinline__ void split3(float v, bf16& h, bf16& m, bf16& l) {
     h = (bf16)v;

@@ -304,7 +304,7 @@ __global__ __launch_bounds__(256) void norm_act_fwd_kernel(const T* __restrict__
     const bool active = rsub < rpi;
     if (!active && !amax_out) return;
     const long long rbase = (long long)g * rows;
-    float amax = 0.f;                   // max |y| of this thread's outputs (amax_out: the f16x3 scale of the convolution that reads y)
+    float amax = 0.f;                   // max |y| of this thread's outputs AS STORED (amax_out: the f16x3 scale of the convolution that reads y)
     for (int cc = threadIdx.x % lanes; active && cc < cw; cc += lanes) {
         const int c = cc * NJ;
         float al[NJ], be[NJ];
@@ -332,7 +332,7 @@ __global__ __launch_bounds__(256) void norm_act_fwd_kernel(const T* __restrict__
                         o.z = act_apply(fmaf(v[u].z, al[NJ > 1 ? 2 : 0], be[NJ > 1 ? 2 : 0]) + rr[u].z, ACTV, slope);
                         o.w = act_apply(fmaf(v[u].w, al[NJ > 1 ? 3 : 0], be[NJ > 1 ? 3 : 0]) + rr[u].w, ACTV, slope);
                         stf4(y + (rbase + r + u) * ldy + c, o);
-                        amax = fmaxf(amax, fmaxf(fmaxf(fabsf(o.x), fabsf(o.y)), fmaxf(fabsf(o.z), fabsf(o.w))));
+                        amax = fmaxf(amax, fmaxf(fmaxf(fabsf(as_stored<T>(o.x)), fabsf(as_stored<T>(o.y))), fmaxf(fabsf(as_stored<T>(o.z)), fabsf(as_stored<T>(o.w)))));
                     }
             }
             continue;
@@ -343,7 +343,7 @@ __global__ __launch_bounds__(256) void norm_act_fwd_kernel(const T* __restrict__
                 const float rv = res ? ld1(res + row * ldres + c) : 0.f;
                 const float o = act_apply(fmaf(ld1(x + row * ldx + c), al[0], be[0]) + rv, ACTV, slope);
                 st1(y + row * ldy + c, o);
-                amax = fmaxf(amax, fabsf(o));
+                amax = fmaxf(amax, fabsf(as_stored<T>(o)));
             }
         }
     }
@@ -397,7 +397,7 @@ __global__ __launch_bounds__(256) void norm_act_bwd_apply_kernel(const T* __rest
     const int rsub = threadIdx.x / lanes;
     const bool active = rsub < rpi;
     if (!active && !dxpart && !amax_out) return;
-    float amax = 0.f;                   // max |dx| of this thread's outputs
+    float amax = 0.f;                   // max |dx| of this thread's outputs as stored
     const long long rbase = (long long)g * rows;
     const float invM = 1.f / (float)rows;
     float colsum[NJ];
@@ -435,7 +435,7 @@ __global__ __launch_bounds__(256) void norm_act_bwd_apply_kernel(const T* __rest
                 oz[j] = dz;
                 od[j] = ga[j] * rs[j] * (dz - k1[j] - xh * k2[j]);
                 colsum[j] += od[j];
-                amax = fmaxf(amax, fabsf(od[j]));
+                amax = fmaxf(amax, fabsf(as_stored<T>(od[j])));
             }
             if (VEC) {
                 stf4(dx + row * lddx + c, make_float4(od[0], od[NJ > 1 ? 1 : 0], od[NJ > 1 ? 2 : 0], od[NJ > 1 ? 3 : 0]));
@@ -469,9 +469,10 @@ __global__ __launch_bounds__(256) void norm_act_bwd_apply_kernel(const T* __rest
 template <typename T, bool VEC, bool BWD, int ACT = -1>
 __global__ __launch_bounds__(256) void act_kernel(const T* __restrict__ dy, int lddy, const T* __restrict__ x, int ldx,
         const T* __restrict__ res, int ldres, T* __restrict__ out, int ldo, long long rows, int C, int lanes, int rpi,
-        int act, float slope, const float* __restrict__ slope_c) {
+        int act, float slope, const float* __restrict__ slope_c, const T* __restrict__ addend = nullptr, int ldadd = 0) {
     const int ACTV = ACT >= 0 ? ACT : act;            // (a compile-time constant in the per-activation instantiations: the per-element switch folds)
     // slope_c != null: PReLU -- the leaky slope of channel c is slope_c[c] (act = LRELU)
+    // addend != null (BWD): out = addend + dy * act'(z), stored once (the product is rounded before the sum, never fused into it)
     const int cw = VEC ? C / 4 : C;
     const int rsub = threadIdx.x / lanes;
     if (rsub >= rpi) return;
@@ -491,6 +492,11 @@ __global__ __launch_bounds__(256) void act_kernel(const T* __restrict__ dy, int 
                     float4 d = ldf4(dy + r * lddy + c);
                     o = make_float4(d.x * act_grad(v.x, ACTV, sl.x), d.y * act_grad(v.y, ACTV, sl.y),
                                     d.z * act_grad(v.z, ACTV, sl.z), d.w * act_grad(v.w, ACTV, sl.w));
+                    if (addend) {
+#pragma clang fp contract(off)
+                        const float4 q = ldf4(addend + r * ldadd + c);
+                        o.x = o.x + q.x; o.y = o.y + q.y; o.z = o.z + q.z; o.w = o.w + q.w;
+                    }
                 } else {
                     o = make_float4(act_apply(v.x, ACTV, sl.x), act_apply(v.y, ACTV, sl.y),
                                     act_apply(v.z, ACTV, sl.z), act_apply(v.w, ACTV, sl.w));
@@ -498,7 +504,12 @@ __global__ __launch_bounds__(256) void act_kernel(const T* __restrict__ dy, int 
                 stf4(out + r * ldo + c, o);
             } else {
                 float v = ld1(x + r * ldx + c) + (res ? ld1(res + r * ldres + c) : 0.f);
-                st1(out + r * ldo + c, BWD ? ld1(dy + r * lddy + c) * act_grad(v, ACTV, sl.x) : act_apply(v, ACTV, sl.x));
+                float o = BWD ? ld1(dy + r * lddy + c) * act_grad(v, ACTV, sl.x) : act_apply(v, ACTV, sl.x);
+                if (BWD && addend) {
+#pragma clang fp contract(off)
+                    o = o + ld1(addend + r * ldadd + c);
+                }
+                st1(out + r * ldo + c, o);
             }
         }
     }
@@ -600,6 +611,25 @@ static bool vec_ok(int C, std::initializer_list<int> lds) {
     if (C % 4) return false;
     for (int l : lds) if (l % 4) return false;
     return true;
+}
+
+// dx = [addend +] dy * act'(x [+ res]) on the 4-wide / scalar kernel: mi355seg_act_bwd_* and what mi355seg_act_bwd_add_* falls back to
+// off its 8-wide geometry -- one pass and one store either way (as two passes, a bf16 dx was rounded twice)
+template <typename T>
+static int act_bwd_rows(const T* dy, int lddy, const T* x, int ldx, const T* res, int ldres, const T* addend, int ldadd,
+                        T* dx, int lddx, long long rows, int C, int act, float slope, hipStream_t st) {
+    bool v = vec_ok(C, {lddy, ldx, lddx, res ? ldres : 4, addend ? ldadd : 4});
+    RowMap rm = ew_map(C, v);
+    dim3 grid(row_grid(rows, rm.rpi));
+    ProfScope ps(PF_NORM, 0.0, (double)sizeof(T) * rows * C * (3.0 + (res ? 1.0 : 0.0) + (addend ? 1.0 : 0.0)), st);
+    if (v)
+        act_host_dispatch(act, [&](auto A_) { hipLaunchKernelGGL((act_kernel<T, true, true, decltype(A_)::value>), grid, dim3(256), 0, st, dy, lddy, x, ldx,
+                           res, ldres, dx, lddx, rows, C, rm.lanes, rm.rpi, act, slope, (const float*)nullptr, addend, ldadd); });
+    else
+        act_host_dispatch(act, [&](auto A_) { hipLaunchKernelGGL((act_kernel<T, false, true, decltype(A_)::value>), grid, dim3(256), 0, st, dy, lddy, x,
+                           ldx, res, ldres, dx, lddx, rows, C, rm.lanes, rm.rpi, act, slope, (const float*)nullptr, addend, ldadd); });
+    SEG_CHECK_LAUNCH();
+    return MI355SEG_OK;
 }
 
 // channel sums of a [rows, C] matrix as doubles (used for dbias and conv-epilogue stats

@@ -296,7 +296,7 @@ int FN(act_fwd)(const TT* x, int ldx, const TT* res, int ldres, TT* y, int ldy,
 
 // dx = addend + dy * act'(x + res): the activation's backward together with the sum of a second gradient of the same tensor (a residual
 // fork: x feeds the activation AND, unchanged, a later sum).  addend NULL: mi355seg_act_bwd.  Eight channels per thread where the geometry
-// allows (C % 8, pitches % 8, 16-byte pointers), else the activation backward followed by an in-place sum.
+// allows (C % 8, pitches % 8, 16-byte pointers), else the 4-wide / scalar activation backward with the sum inside it: one store of dx.
 int FN(act_bwd_add)(const TT* dy, int lddy, const TT* x, int ldx, const TT* res, int ldres, const TT* addend, int ldadd,
                              TT* dx, int lddx, long long rows, int C, int act, float slope, void* stream) {
     SEG_CHECK_ARG(dy && x && dx && rows > 0 && C > 0 && act >= 0 && act <= 4, "act_bwd_add: bad arguments");
@@ -310,9 +310,7 @@ int FN(act_bwd_add)(const TT* dy, int lddy, const TT* x, int ldx, const TT* res,
         SEG_CHECK_LAUNCH();
         return MI355SEG_OK;
     }
-    int rc = FN(act_bwd)(dy, lddy, x, ldx, res, ldres, dx, lddx, rows, C, act, slope, stream);
-    if (rc || !addend) return rc;
-    return FN(act_fwd)(dx, lddx, addend, ldadd, dx, lddx, rows, C, MI355SEG_ACT_NONE, 0.f, stream);
+    return act_bwd_rows(dy, lddy, x, ldx, res, ldres, addend, ldadd, dx, lddx, rows, C, act, slope, (hipStream_t)stream);
 }
 
 int FN(act_bwd)(const TT* dy, int lddy, const TT* x, int ldx, const TT* res, int ldres,
@@ -321,17 +319,6 @@ int FN(act_bwd)(const TT* dy, int lddy, const TT* x, int ldx, const TT* res, int
     if (sizeof(TT) == 2 && vec8_ok(C, {lddy, ldx, lddx, res ? ldres : 8}) && ((uintptr_t)dy % 16) == 0 && ((uintptr_t)x % 16) == 0 && ((uintptr_t)dx % 16) == 0 &&
         (!res || ((uintptr_t)res % 16) == 0))
         return FN(act_bwd_add)(dy, lddy, x, ldx, res, ldres, nullptr, 0, dx, lddx, rows, C, act, slope, stream);      // bf16: 16-byte accesses
-    bool v = vec_ok(C, {lddy, ldx, lddx, res ? ldres : 4});
-    RowMap rm = ew_map(C, v);
-    dim3 grid(row_grid(rows, rm.rpi));
-    ProfScope ps(PF_NORM, 0.0, (double)sizeof(TT) * rows * C * (res ? 4.0 : 3.0), (hipStream_t)stream);
-    if (v)
-        act_host_dispatch(act, [&](auto A_) { hipLaunchKernelGGL((act_kernel<TT, true, true, decltype(A_)::value>), grid, dim3(256), 0, (hipStream_t)stream, dy, lddy, x, ldx,
-                           res, ldres, dx, lddx, rows, C, rm.lanes, rm.rpi, act, slope, (const float*)nullptr); });
-    else
-        act_host_dispatch(act, [&](auto A_) { hipLaunchKernelGGL((act_kernel<TT, false, true, decltype(A_)::value>), grid, dim3(256), 0, (hipStream_t)stream, dy, lddy, x,
-                           ldx, res, ldres, dx, lddx, rows, C, rm.lanes, rm.rpi, act, slope, (const float*)nullptr); });
-    SEG_CHECK_LAUNCH();
-    return MI355SEG_OK;
+    return act_bwd_rows(dy, lddy, x, ldx, res, ldres, (const TT*)nullptr, 0, dx, lddx, rows, C, act, slope, (hipStream_t)stream);
 }
 
