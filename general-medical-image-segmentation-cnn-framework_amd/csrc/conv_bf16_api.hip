@@ -100,6 +100,22 @@ static int choose_b16(const Rung* r, const ConvKey& k) {
     return NB_CAST;
 }
 
+// What mi355seg_last_conv_path reports for a family (MI355SEG_PATH_B16_*), one host-side store per call.  The igemm, gather and
+// transposing-read launchers record themselves (conv_fwd_mfma, conv_gather_*_mfma, conv_wgrad_lowp: only they know the tiles and the K
+// form), so their families map to 0 = "not here".  The cast fall-back records AFTER the staged fp32 entry point returned, over that call's
+// fp32 code: the report says "cast", never the branch taken on the staged copies.
+static void note_b16(int pass, int family) {
+    static const int code[3][NB_CONVT + 1] = {
+        {MI355SEG_PATH_B16_FWD_CAST, 0, 0, MI355SEG_PATH_B16_FWD_STEM1K5, 0, MI355SEG_PATH_B16_FWD_HEADPW, 0, MI355SEG_PATH_B16_FWD_HEAD2, MI355SEG_PATH_B16_FWD_STEM4,
+         MI355SEG_PATH_B16_FWD_STEM, MI355SEG_PATH_B16_FWD_HEAD, 0, 0, 0, 0, 0, MI355SEG_PATH_B16_FWD_TINYPW, 0},
+        {MI355SEG_PATH_B16_DGRAD_CAST, 0, 0, 0, 0, 0, 0, MI355SEG_PATH_B16_DGRAD_HEAD2, 0, 0, MI355SEG_PATH_B16_DGRAD_HEAD, 0, 0, 0, 0, 0, MI355SEG_PATH_B16_DGRAD_TINYPW,
+         MI355SEG_PATH_B16_DGRAD_K2S2_CONVT},
+        {MI355SEG_PATH_B16_WGRAD_CAST, 0, 0, MI355SEG_PATH_B16_WGRAD_STEM1K5, MI355SEG_PATH_B16_WGRAD_PW_LOWP, MI355SEG_PATH_B16_WGRAD_HEADPW, MI355SEG_PATH_B16_WGRAD_K2S2_CONVT,
+         MI355SEG_PATH_B16_WGRAD_HEAD2, MI355SEG_PATH_B16_WGRAD_STEM4, MI355SEG_PATH_B16_WGRAD_STEM, MI355SEG_PATH_B16_WGRAD_HEAD, 0, MI355SEG_PATH_B16_WGRAD_PW_MFMA,
+         MI355SEG_PATH_B16_WGRAD_SMALLCIN, MI355SEG_PATH_B16_WGRAD_SMALLCOUT, MI355SEG_PATH_B16_WGRAD_GWGRAD, MI355SEG_PATH_B16_WGRAD_TINYPW, 0}};
+    if (code[pass][family]) note_conv_path(code[pass][family]);
+}
+
 // the cast fall-back: fp32 copies of x (or dx) and y (or dy) in the workspace, `run` on them with the rest of it, the written one cast back
 template <typename F>
 static int staged(const ConvCall& c, bool x_in, bool y_in, F run) {
@@ -113,6 +129,7 @@ static int staged(const ConvCall& c, bool x_in, bool y_in, F run) {
     if (y_in) cast_rows((const bf16*)c.y, c.ldy, yf, g.Cout, c.vout(), g.Cout, c.st);
     SEG_CHECK_LAUNCH();
     int rc = run(xf, yf, (char*)c.ws + used, c.ws_bytes - used);
+    note_b16(x_in && y_in ? 2 : (x_in ? 0 : 1), NB_CAST);
     if (rc || (x_in && y_in)) return rc;
     if (x_in) cast_rows(yf, g.Cout, (bf16*)c.y, c.ldy, c.vout(), g.Cout, c.st);
     else cast_rows(xf, g.Cin, (bf16*)c.x, c.ldx, c.vin(), g.Cin, c.st);
@@ -203,7 +220,9 @@ int mi355seg_conv3d_fwd_bf16(const mi355seg_bf16* x, int ldx, const float* w, co
     if (rc) return rc;
     SEG_CHECK_ARG((stats_sum == nullptr) == (stats_sq == nullptr), "conv3d_fwd_bf16: stats_sum/stats_sq must come together");
     hipStream_t st = c.st;
-    switch (choose_b16(FWD_B16, conv_key(c))) {
+    const int family = choose_b16(FWD_B16, conv_key(c));
+    if (family != NB_CAST) note_b16(0, family);
+    switch (family) {
     case NB_IGEMM: return conv_fwd_mfma(MATH_B16, x, ldx, w, bias, y, ldy, N, D, H, W, Cin, Cout, k, /*dgrad=*/0, stats_sum, stats_sq, ws, ws_bytes, st);
     case NB_GATHER: return conv_gather_fwd_mfma(MATH_B16, x, ldx, w, bias, y, ldy, N, D, H, W, Cin, Cout, k, stride, pad, stats_sum, stats_sq, ws, ws_bytes, st);
     case NB_HEAD2: return conv_stats_tail<bf16>(head2_fwd_lowp(x, ldx, w, bias, y, ldy, N, D, H, W, Cin, ws, ws_bytes, st), c, stats_sum, stats_sq);
@@ -227,7 +246,9 @@ int mi355seg_conv3d_dgrad_bf16(const mi355seg_bf16* dy, int lddy, const float* w
     int rc = conv_call(&c, "conv3d_dgrad_bf16", dx, lddx, w, dy, lddy, N, D, H, W, Cin, Cout, k, stride, pad, ws, ws_bytes, stream);
     if (rc) return rc;
     hipStream_t st = c.st;
-    switch (choose_b16(DGRAD_B16, conv_key(c))) {
+    const int family = choose_b16(DGRAD_B16, conv_key(c));
+    if (family != NB_CAST) note_b16(1, family);
+    switch (family) {
     case NB_IGEMM: return conv_fwd_mfma(MATH_B16, dy, lddy, w, nullptr, dx, lddx, N, D, H, W, Cout, Cin, k, /*dgrad=*/1, nullptr, nullptr, ws, ws_bytes, st);
     case NB_GATHER: return conv_gather_dgrad_mfma(MATH_B16, dy, lddy, w, dx, lddx, N, D, H, W, Cin, Cout, k, stride, pad, ws, ws_bytes, st);
     case NB_HEAD2: return head2_dgrad_lowp(dy, lddy, w, dx, lddx, N, D, H, W, Cin, ws, ws_bytes, st);
@@ -275,7 +296,9 @@ int mi355seg_conv3d_wgrad_bf16(const mi355seg_bf16* dy, int lddy, const mi355seg
         if (rc) return rc;
     }
     float* part; int nstrips;
-    switch (choose_b16(WGRAD_B16, conv_key(c, accumulate))) {
+    const int family = choose_b16(WGRAD_B16, conv_key(c, accumulate));
+    if (family != NB_CAST) note_b16(2, family);
+    switch (family) {
     case NB_LOWP: return conv_wgrad_lowp(MATH_B16, dy, lddy, x, ldx, dw, N, D, H, W, Cin, Cout, k, stride, accumulate, ws, ws_bytes, st);
     case NB_HEAD2: return head2_wgrad_lowp(dy, lddy, x, ldx, dw, N, D, H, W, Cin, accumulate, ws, ws_bytes, st);
     case NB_STEM1K5: return stem1k5_wgrad_lowp(dy, lddy, x, dw, N, D, H, W, Cout, accumulate, ws, ws_bytes, st);

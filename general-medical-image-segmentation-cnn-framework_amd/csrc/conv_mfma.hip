@@ -457,7 +457,10 @@ int conv_fwd_mfma(int math, const void* x, int ldx, const float* w, const float*
     if (b16s) { p.CK = 16; p.nM = bp.nM; p.nN = bp.nN; p.ntx = bp.ntx; p.nty = bp.nty; p.ntz = bp.ntz; p.NT = bp.NT; }
     const int nchunks = Cin / p.CK;
     const long long nvox = (long long)N * D * H * W;
-    const int ksplit = b16s ? bp.ksplit : ((ldy % 4 == 0) ? pick_ksplit(p.nM * p.nN, nchunks) : 1);
+    // (splitk_reduce_kernel writes y four elements at a time: pitch and address must allow the 16- / 8-byte store; no rung's `aligned` test
+    // looks at the written tensor, so a y that starts 2 or 4 bytes off stays on the whole-K form, whose epilogue stores element by element)
+    const bool y_st4 = ldy % 4 == 0 && ((uintptr_t)y % (4 * esize(math))) == 0;
+    const int ksplit = b16s ? bp.ksplit : (y_st4 ? pick_ksplit(p.nM * p.nN, nchunks) : 1);
     // fp32 tensors under f16x3: the large layers run conv_x3w's 8 x 4 x 16 tiles (fewer, larger M-tiles: decided before anything is sized by nM)
     const bool x3w = math == MATH_X3 && x3s_enabled() && x3_f16() && x3s_plan_ok(p, x, ldx, y, ldy, (long long)D * H * W) && x3w_plan(p, N, D, H, W, Cin, Cout, ksplit);
     Carver cv(ws);
@@ -470,7 +473,9 @@ int conv_fwd_mfma(int math, const void* x, int ldx, const float* w, const float*
     // the BatchNorm-backward sums of the layer in front ride in that kernel's epilogue (whole-K launches only)
     // the one place that records the igemm branches of the fp32 dispatchers (mi355seg_last_conv_path): every caller on fp32 tensors --
     // conv3d_fwd / _fused / _pro, conv3d_dgrad / _bnsums -- comes through here, and only here is it known which tiles run
-    if (math != MATH_B16)
+    if (math == MATH_B16)
+        note_conv_path((dgrad ? MI355SEG_PATH_B16_DGRAD_IGEMM_S : MI355SEG_PATH_B16_FWD_IGEMM_S) + (b16s ? 0 : 2) + (ksplit > 1 ? 1 : 0));
+    else
         note_conv_path(pro ? MI355SEG_PATH_FWD_PRO_X3S
                        : math == MATH_F32 ? (dgrad ? MI355SEG_PATH_DGRAD_MFMA_F32 : MI355SEG_PATH_FWD_MFMA_F32)
                        : x3s ? (dgrad ? MI355SEG_PATH_DGRAD_MFMA_X3S : MI355SEG_PATH_FWD_MFMA_X3S)
@@ -666,7 +671,8 @@ int conv_gather_fwd_mfma(int math, const void* x, int ldx, const float* w, const
     SEG_CHECK_ARG(((uintptr_t)x % 16) == 0, "conv_gather_fwd_mfma: input pointer must be 16-byte aligned");
     const int T = k * k * k, cpt = Cin / p.CK, nchunks = T * cpt;
     // few output tiles and a long K (the deep down-convolutions: 256 -> 512 at 10 x 12 x 10 is 9 tiles x 432 chunks): split K
-    const int ksplit = (ldy % 4 == 0) ? pick_ksplit(p.nM * p.nN, nchunks) : 1;
+    const int ksplit = (ldy % 4 == 0 && ((uintptr_t)y % (4 * esize(math))) == 0) ? pick_ksplit(p.nM * p.nN, nchunks) : 1;      // (as in conv_fwd_mfma)
+    if (math == MATH_B16) note_conv_path(ksplit > 1 ? MI355SEG_PATH_B16_FWD_GATHER_SPLITK : MI355SEG_PATH_B16_FWD_GATHER);
     const long long nvo = (long long)N * Do * Ho * Wo;
     Carver cv(ws);
     const size_t wq_size = wq_bytes(math, (size_t)T * Cin * Cout);
@@ -764,6 +770,7 @@ int conv_gather_dgrad_mfma(int math, const void* dy, int lddy, const float* w, v
     }
     // (decided before any packing is looked up or launched: the per-phase launches below pack eight separately padded pieces, into the workspace only)
     multi = multi && taps_total == T && igemm_phases_lowp_has(math, phs[0].p);
+    if (math == MATH_B16) note_conv_path(multi ? MI355SEG_PATH_B16_DGRAD_GATHER_PHASES : MI355SEG_PATH_B16_DGRAD_GATHER);
     if (multi) {
         const IgemmPlan& p0 = phs[0].p;
         const int cpt = Cout / p0.CK;

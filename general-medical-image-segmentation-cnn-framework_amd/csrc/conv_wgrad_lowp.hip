@@ -875,6 +875,7 @@ int conv_wgrad_lowp(int math, const void* dy, int lddy, const void* x, int ldx, 
     const bool swap = !wide && !pro && g_wgrad_wide != 0 && math == MATH_X3 && x3_f16() && k == 3 && stride == 1 && Cin % 64 == 0 && Cout % 64 != 0 &&
                       lwgrad_plan(math, k, stride, N, Do, Ho, Wo, Cout, Cin, &psw, true) && psw.nstrips >= 8 && lw_offsets_fit(math, Ho, Wo, lddy, H, W, ldx);
     if (math == MATH_X3) note_conv_path(wide ? MI355SEG_PATH_WGRAD_LOWP_WIDE : (swap ? MI355SEG_PATH_WGRAD_LOWP_SWAPPED : MI355SEG_PATH_WGRAD_LOWP_NARROW));
+    else if (math == MATH_B16) note_conv_path(wide ? MI355SEG_PATH_B16_WGRAD_LOWP_WIDE : (swap ? MI355SEG_PATH_B16_WGRAD_LOWP_SWAPPED : MI355SEG_PATH_B16_WGRAD_LOWP_NARROW));
     if (swap) {
         SEG_CHECK_ARG(((uintptr_t)x % 16) == 0 && ((uintptr_t)dy % 16) == 0, "conv_wgrad_lowp: pointers must be 16-byte aligned");
         Carver cv(ws);

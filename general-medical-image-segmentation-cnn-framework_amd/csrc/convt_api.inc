@@ -1,7 +1,9 @@
 // convt_api.inc -- ConvTranspose3d k2 s2 entry points, compiled once per storage type (TT = float with TT_MATH = MATH_F32,
 // TT = bf16 with TT_MATH = MATH_B16).  Weights, bias and weight gradients are always fp32.
-// The fp32 entry points record the branch they take (MI355SEG_PATH_CONVT_*, mi355seg_last_conv_path).
-#define CONVT_NOTE(code) do { if (sizeof(TT) == 4) note_conv_path(code); } while (0)
+// Every entry point records the branch it takes (mi355seg_last_conv_path): MI355SEG_PATH_CONVT_* on fp32 tensors, the same code in the
+// MI355SEG_PATH_B16_CONVT_* block on bf16 ones -- where convt_direct itself records which of its two forms runs (GEMM or streaming).
+#define CONVT_B16 (MI355SEG_PATH_B16_CONVT_FWD_DIRECT - MI355SEG_PATH_CONVT_FWD_DIRECT)
+#define CONVT_NOTE(code) note_conv_path(sizeof(TT) == 4 ? (code) : (code) + CONVT_B16)
 int FN(convt3d_k2s2_fwd)(const TT* x, int ldx, const float* w, const float* bias,
                                   TT* y, int ldy, int N, int D, int H, int W, int Cin, int Cout,
                                   void* ws, size_t ws_bytes, void* stream) {
@@ -114,3 +116,4 @@ int FN(convt3d_k2s2_wgrad)(const TT* dy, int lddy, const TT* x, int ldx,
 }
 
 #undef CONVT_NOTE
+#undef CONVT_B16

@@ -511,6 +511,9 @@ int convt_direct(bool gather, const TT* x, int ldx, const float* w, const float*
     const double vox = (double)a.nvox;
     ProfScope ps(PF_CONVT, 2.0 * vox * 8 * Cin * Cout, sizeof(TT) * vox * (Cin + 8.0 * Cout) + 4.0 * 8 * Cin * Cout, st);
     const int ks = ct_ksplit(gather, (int)sizeof(TT), p, a.nvox);
+    if constexpr (sizeof(TT) == 2)            // (after the entry point's own note: only here is the form known)
+        note_conv_path(p.stream ? (gather ? MI355SEG_PATH_B16_CONVT_DGRAD_STREAM : MI355SEG_PATH_B16_CONVT_FWD_STREAM)
+                                : (gather ? MI355SEG_PATH_B16_CONVT_DGRAD_DIRECT : MI355SEG_PATH_B16_CONVT_FWD_DIRECT));
     float* slabs = nullptr;
     if (ks > 1) {
         slabs = cv.take<float>((size_t)ks * a.nvox * Cin);

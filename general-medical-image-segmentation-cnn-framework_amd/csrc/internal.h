@@ -133,7 +133,7 @@ template <typename T> inline int conv_stats_tail(int rc, const ConvCall& c, doub
 int wgrad_strips_tail(int rc, const float* part, int nstrips, const ConvCall& c, int accumulate);      // (k1 slabs: [strip][Cin][Cout])
 int f32_conv_policy();     // MATH_X3 when the bf16x6 conv math is selected, else MATH_F32
 int x3_shape();            // 16 | 32: MFMA shape of the bf16x6 forward / dgrad kernels (mi355seg_set_x3_shape)
-void note_conv_path(int code);      // MI355SEG_PATH_*: the branch an fp32 convolution dispatcher took (mi355seg_last_conv_path)
+void note_conv_path(int code);      // MI355SEG_PATH_*: the branch a convolution dispatcher took (mi355seg_last_conv_path)
 bool x3_f16();             // the split-precision kernels run the two-piece fp16 split (MI355SEG_MATH_F16X3) where they have that form
 void pack_w_fwd(const float* w, float* wp, int Cout, int Cin, int T, hipStream_t st);
 void pack_w_dgrad(const float* w, float* wd, int Cout, int Cin, int T, int flip, hipStream_t st);

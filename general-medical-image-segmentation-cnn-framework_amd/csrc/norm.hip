@@ -9,6 +9,7 @@
 #include "common.h"
 #include "internal.h"
 #include <initializer_list>
+#include <type_traits>
 
 namespace seg {
 
@@ -130,6 +131,14 @@ struct PreluF {     // column sum of dy * min(z, 0), z = x (+ res): the gradient
     }
 };
 
+// Which functors have the block's row slots combined in fp64 (below).  With few channels one thread walks up to 256 slots, and that chain
+// in fp32 put the second moment of a narrow bf16 convolution output (Cout = 4 | 8: stem, heads) at up to 1.9x the 2^-22 column-sum bar of
+// tests/test_gpu_bf16_paths.py.  Only SumF<bf16> -- channel_sums on bf16 tensors: the statistics behind split K and conv_stats_tail<bf16>,
+// the bias gradients -- takes the fp64 form: the fp32 instantiations keep their summation order bit for bit, because the fp32 model
+// fixtures (tests/test_gpu_models.py: Residual U-Net, CSRNet) hold gradients to twice the reference's own fp32 noise and moved past
+// that with the more accurate sums (measured: 5.6e-7 against 5.0e-7, 1.99e-5 against 1.88e-5).
+template <typename F> struct Combine64 { static constexpr bool value = false; };
+
 template <typename F, bool VEC>
 __global__ __launch_bounds__(kRedThreads) void colreduce2_kernel(F f, long long rows, int C, int lanes, int rpi,
                                                                  float* __restrict__ part) {
@@ -169,15 +178,16 @@ __global__ __launch_bounds__(kRedThreads) void colreduce2_kernel(F f, long long 
         s[4] = sb.x; s[5] = sb.y; s[6] = sb.z; s[7] = sb.w;
         __syncthreads();
         if (t < lanes) {
-            float acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+            using acc_t = typename std::conditional<Combine64<F>::value, double, float>::type;
+            acc_t acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
             for (int q = 0; q < rpi; ++q) {
                 const float* o = sh + (q * lanes + t) * 8;
 #pragma unroll
-                for (int j = 0; j < 8; ++j) acc[j] += o[j];
+                for (int j = 0; j < 8; ++j) acc[j] += (acc_t)o[j];
             }
             float* dst = part + (((long long)g * nblk + blockIdx.x) * C + t * 4) * 2;
 #pragma unroll
-            for (int j = 0; j < 4; ++j) { dst[j * 2] = acc[j]; dst[j * 2 + 1] = acc[4 + j]; }
+            for (int j = 0; j < 4; ++j) { dst[j * 2] = (float)acc[j]; dst[j * 2 + 1] = (float)acc[4 + j]; }
         }
     } else {
         float sa = 0.f, sb = 0.f;
@@ -192,10 +202,11 @@ __global__ __launch_bounds__(kRedThreads) void colreduce2_kernel(F f, long long 
         sh[t * 2] = sa; sh[t * 2 + 1] = sb;
         __syncthreads();
         if (t < lanes) {
-            float a = 0.f, b = 0.f;
-            for (int q = 0; q < rpi; ++q) { a += sh[(q * lanes + t) * 2]; b += sh[(q * lanes + t) * 2 + 1]; }
+            using acc_t = typename std::conditional<Combine64<F>::value, double, float>::type;
+            acc_t a = 0, b = 0;
+            for (int q = 0; q < rpi; ++q) { a += (acc_t)sh[(q * lanes + t) * 2]; b += (acc_t)sh[(q * lanes + t) * 2 + 1]; }
             float* dst = part + (((long long)g * nblk + blockIdx.x) * C + t) * 2;
-            dst[0] = a; dst[1] = b;
+            dst[0] = (float)a; dst[1] = (float)b;
         }
     }
 }
@@ -652,6 +663,8 @@ struct SumF {        // sums of (x - pivot) and (x - pivot)^2; pivot = 0 when on
         a = v; b = make_float4(v.x * v.x, v.y * v.y, v.z * v.z, v.w * v.w);
     }
 };
+
+template <> struct Combine64<SumF<bf16>> { static constexpr bool value = true; };
 
 template <typename T>
 __global__ __launch_bounds__(64) void sums_finalize_kernel(const float* __restrict__ part, int nblk, int C, double* __restrict__ sum,

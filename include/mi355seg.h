@@ -237,8 +237,13 @@ int mi355seg_convt3d_k2s2_wgrad_f32(const float* dy, int lddy, const float* x, i
  * Every fp32 Conv3d / ConvTranspose3d k2 s2 dispatcher (mi355seg_conv3d_{fwd,dgrad,wgrad}[_ax|_pro_ax|_yamax_ax]_f32,
  * mi355seg_conv3d_fwd_fused_f32, mi355seg_conv3d_dgrad_bnsums[_ax]_f32, mi355seg_convt3d_k2s2_{fwd,dgrad,wgrad}[_ax]_f32) records the branch of its if-chain it took in one host-side integer before it
  * launches: a test asks after the call and so knows which kernel it has graded (tests/test_gpu_conv_paths.py).  One code per
- * branch; a branch that chooses between kernels has one per kernel.  Process-wide like the conv math, not thread-local; the bf16
- * entry points and mi355seg_stem_wgrad_bnbwd_f32 (one kernel, no choice) do not record.  0 before the first call. */
+ * branch; a branch that chooses between kernels has one per kernel.  Process-wide like the conv math, not thread-local;
+ * mi355seg_stem_wgrad_bnbwd_f32 (one kernel, no choice) does not record.  0 before the first call.
+ * The bf16-storage entry points (mi355seg_conv3d_{fwd,fwd_fused,fwd_res,dgrad,dgrad_res,wgrad}_bf16,
+ * mi355seg_convt3d_k2s2_{fwd,fwd_ax,dgrad,wgrad}_bf16) record MI355SEG_PATH_B16_* codes (tests/test_gpu_bf16_paths.py): the family
+ * their ladder chose (a demoted call reports the family it was demoted to), inside the igemm / gather / transposing-read families
+ * the tiles and the K form.  After the cast fall-back the code is *_CAST, not the branch the fp32 entry point took on the staged
+ * copies (it is stored after that call returns). */
 enum {
     MI355SEG_PATH_NONE = 0,
     /* mi355seg_conv3d_fwd*_f32 */
@@ -296,7 +301,64 @@ enum {
     MI355SEG_PATH_CONVT_DGRAD_PLAIN = 65,
     MI355SEG_PATH_CONVT_WGRAD_LOWP = 66,
     MI355SEG_PATH_CONVT_WGRAD_MFMA = 67,
-    MI355SEG_PATH_CONVT_WGRAD_PLAIN = 68
+    MI355SEG_PATH_CONVT_WGRAD_PLAIN = 68,
+    /* mi355seg_conv3d_fwd[_fused|_res]_bf16 */
+    MI355SEG_PATH_B16_FWD_IGEMM_S = 100,         /* igemm, 16x16x32 tiles (conv_b16s.hip), whole K */
+    MI355SEG_PATH_B16_FWD_IGEMM_S_SPLITK = 101,  /* ... fp32 slabs + splitk_reduce_kernel */
+    MI355SEG_PATH_B16_FWD_IGEMM_G = 102,         /* igemm, generic 32x32x16 tiles, whole K */
+    MI355SEG_PATH_B16_FWD_IGEMM_G_SPLITK = 103,
+    MI355SEG_PATH_B16_FWD_GATHER = 104,          /* gather igemm, whole K */
+    MI355SEG_PATH_B16_FWD_GATHER_SPLITK = 105,
+    MI355SEG_PATH_B16_FWD_HEAD2 = 106,           /* k5 head, Cout = 2 (conv_head2_lowp.hip) */
+    MI355SEG_PATH_B16_FWD_STEM1K5 = 107,         /* k5 stem, Cin = 1 (conv_stem1k5_lowp.hip) */
+    MI355SEG_PATH_B16_FWD_STEM4 = 108,           /* k3 stem, Cin = 4 on the matrix cores (conv_stem4_lowp.hip) */
+    MI355SEG_PATH_B16_FWD_STEM = 109,            /* k3 stem, direct kernels */
+    MI355SEG_PATH_B16_FWD_HEADPW = 110,          /* k1 head on the matrix cores (conv_headpw_lowp.hip) */
+    MI355SEG_PATH_B16_FWD_HEAD = 111,            /* k1 head, plain kernel */
+    MI355SEG_PATH_B16_FWD_TINYPW = 112,
+    MI355SEG_PATH_B16_FWD_CAST = 113,            /* fp32 copies staged in the workspace, the fp32 entry point on them */
+    /* mi355seg_conv3d_dgrad[_res]_bf16 */
+    MI355SEG_PATH_B16_DGRAD_IGEMM_S = 120,
+    MI355SEG_PATH_B16_DGRAD_IGEMM_S_SPLITK = 121,
+    MI355SEG_PATH_B16_DGRAD_IGEMM_G = 122,
+    MI355SEG_PATH_B16_DGRAD_IGEMM_G_SPLITK = 123,
+    MI355SEG_PATH_B16_DGRAD_GATHER_PHASES = 124, /* gather igemm, every phase in one launch */
+    MI355SEG_PATH_B16_DGRAD_GATHER = 125,        /* gather igemm, one launch per phase */
+    MI355SEG_PATH_B16_DGRAD_HEAD2 = 126,
+    MI355SEG_PATH_B16_DGRAD_HEAD = 127,
+    MI355SEG_PATH_B16_DGRAD_TINYPW = 128,
+    MI355SEG_PATH_B16_DGRAD_K2S2_CONVT = 129,    /* k2 s2 p0 as the forward of ConvTranspose3d k2 s2 (igemm) */
+    MI355SEG_PATH_B16_DGRAD_CAST = 130,
+    /* mi355seg_conv3d_wgrad_bf16 */
+    MI355SEG_PATH_B16_WGRAD_LOWP_NARROW = 140,   /* conv_wgrad_lowp, 32 x 32 channel blocks */
+    MI355SEG_PATH_B16_WGRAD_LOWP_WIDE = 141,     /* conv_wgrad_lowp, 32 x 64 channel blocks */
+    MI355SEG_PATH_B16_WGRAD_LOWP_SWAPPED = 142,  /* (the swapped-role form exists on fp32 tensors only: never recorded) */
+    MI355SEG_PATH_B16_WGRAD_HEAD2 = 143,
+    MI355SEG_PATH_B16_WGRAD_STEM1K5 = 144,
+    MI355SEG_PATH_B16_WGRAD_K2S2_CONVT = 145,    /* k2 s2 p0 as a ConvTranspose3d k2 s2 weight gradient with the roles swapped */
+    MI355SEG_PATH_B16_WGRAD_TINYPW = 146,
+    MI355SEG_PATH_B16_WGRAD_PW_LOWP = 147,       /* k1 on the bf16 matrix cores */
+    MI355SEG_PATH_B16_WGRAD_PW_MFMA = 148,       /* k1, bf16 loads, fp32 MFMA */
+    MI355SEG_PATH_B16_WGRAD_STEM4 = 149,
+    MI355SEG_PATH_B16_WGRAD_STEM = 150,
+    MI355SEG_PATH_B16_WGRAD_HEADPW = 151,
+    MI355SEG_PATH_B16_WGRAD_HEAD = 152,
+    MI355SEG_PATH_B16_WGRAD_SMALLCIN = 153,
+    MI355SEG_PATH_B16_WGRAD_SMALLCOUT = 154,
+    MI355SEG_PATH_B16_WGRAD_GWGRAD = 155,        /* MFMA gather weight gradient */
+    MI355SEG_PATH_B16_WGRAD_CAST = 156,
+    /* mi355seg_convt3d_k2s2_*_bf16: the fp32 codes + 100, and the streaming form of the direct kernels */
+    MI355SEG_PATH_B16_CONVT_FWD_DIRECT = 160,    /* convt_direct, GEMM form */
+    MI355SEG_PATH_B16_CONVT_FWD_MFMA = 161,
+    MI355SEG_PATH_B16_CONVT_FWD_PLAIN = 162,
+    MI355SEG_PATH_B16_CONVT_DGRAD_DIRECT = 163,
+    MI355SEG_PATH_B16_CONVT_DGRAD_MFMA = 164,
+    MI355SEG_PATH_B16_CONVT_DGRAD_PLAIN = 165,
+    MI355SEG_PATH_B16_CONVT_WGRAD_LOWP = 166,
+    MI355SEG_PATH_B16_CONVT_WGRAD_MFMA = 167,
+    MI355SEG_PATH_B16_CONVT_WGRAD_PLAIN = 168,
+    MI355SEG_PATH_B16_CONVT_FWD_STREAM = 169,    /* convt_direct, streaming form (K = 64 | 128 | 256, whole 32-voxel tiles) */
+    MI355SEG_PATH_B16_CONVT_DGRAD_STREAM = 170
 };
 int mi355seg_last_conv_path(void);
 

@@ -754,7 +754,8 @@ def test_every_path_code_is_asserted_or_listed_unreachable():
         ("bf16x6", 32): f16_only | shadowed_in_split | {"FWD_MFMA_X3S", "DGRAD_MFMA_X3S"},
         ("f16x3", 16): shadowed_in_split,
     }
-    names = set(path_names().values()) - {"NONE"}
+    # (the bf16-storage block of the header, MI355SEG_PATH_B16_*, is no fp32 math's to reach: tests/test_gpu_bf16_paths.py accounts for it)
+    names = {n for n in path_names().values() if not n.startswith("B16_")} - {"NONE"}
     for m in MATHS:
         assert not (seen[m] & unreachable[m]), (m, seen[m] & unreachable[m])
         missing = names - seen[m] - unreachable[m]
