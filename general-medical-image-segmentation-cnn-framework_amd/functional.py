@@ -2355,6 +2355,98 @@ def soft_cldice(logits, target, iters=CLDICE_ITERS, smooth=CLDICE_SMOOTH):
     return loss, parts[1:]
 
 
+# ----------------------------------------------------------------------------- boundary loss (config.boundary_weight; csrc/boundary.hip)
+MAX_SDM_AXIS = 2047
+
+
+def checked_spacing(spacing, what):
+    """(sz, sy, sx) as three positive finite floats, or ValueError before anything reaches the device."""
+    try:
+        vals = [spacing] if isinstance(spacing, (bool, str)) else list(spacing)
+        ok = len(vals) == 3 and all(not isinstance(v, (bool, str)) for v in vals)
+        vals = tuple(float(v) for v in vals) if ok else ()
+    except (TypeError, ValueError):
+        vals = ()
+    if len(vals) != 3 or not all(0 < v < float("inf") for v in vals):
+        raise ValueError(f"{what}: spacing must be three positive numbers (sz, sy, sx), got {spacing!r}")
+    return vals
+
+
+def _signed_distance_map(target, spacing, what):
+    _require_cuda(target, f"{what} input")
+    target = target.to(torch.float32).contiguous()
+    if target.dim() != 5:
+        raise Mi355SegError(f"{what}: expected [N,K,D,H,W], got {tuple(target.shape)}")
+    N, K, D, H, W = target.shape
+    L = lib()
+    phi = torch.empty((N, K - (1 if K > 1 else 0), D, H, W), dtype=torch.float32, device=target.device)
+    nbytes = L.query("mi355seg_sdm_ws_bytes", N, K, D, H, W)
+    ws = workspace(nbytes, target.device)
+    sz, sy, sx = spacing
+    L.call("mi355seg_sdm_f32", _p(target), N, K, D, H, W, sz, sy, sx, min(spacing), _p(phi), _p(ws), ws.numel(), _stream())
+    return phi
+
+
+def signed_distance_map(target, spacing=(1, 1, 1)):
+    """The signed Euclidean distance map of every class of a one-hot target [N,K,D,H,W] on the device (one_hot2dist of the official
+    boundary loss): float32 [N, K - c0, D, H, W], c0 = 1 for K > 1 (no background channel), 0 for K = 1.  A voxel belongs to class k
+    when target[n, k] > 0.5.  Outside the class phi = +distance to the nearest voxel of the class, inside phi = -(distance to the
+    nearest voxel outside the class - min(spacing)), and phi = 0 for a whole (n, k) volume whose class is absent or fills the patch;
+    distances under the voxel ``spacing`` (sz, sy, sx), inside the patch only.  Not differentiable.  DESIGN.md 4.21."""
+    return _signed_distance_map(target, checked_spacing(spacing, "signed_distance_map"), "signed_distance_map")
+
+
+class _BoundaryLoss(Function):
+    """(boundary fp32 scalar, fp64[1] = the same in fp64).  The coefficient of the backward stays on the device (coef), as
+    _SoftClDice's do: capturable in a HIP graph."""
+
+    @staticmethod
+    def forward(ctx, logits, target, spacing):
+        _require_cuda(logits, "boundary_loss input")
+        logits, target = logits.contiguous(), target.to(torch.float32).contiguous()
+        if logits.shape != target.shape:
+            raise ValueError(f"Target size ({tuple(target.shape)}) must be the same as input size ({tuple(logits.shape)})")
+        if logits.dim() != 5:
+            raise Mi355SegError(f"boundary_loss: expected [N,K,D,H,W], got {tuple(logits.shape)}")
+        N, K = logits.shape[:2]
+        S = logits[0, 0].numel()
+        dev = logits.device
+        L = lib()
+        phi = _signed_distance_map(target, spacing, "boundary_loss")
+        ws = workspace(L.query("mi355seg_boundary_ws_bytes", phi.numel()), dev)
+        loss = torch.empty((), dtype=torch.float32, device=dev)
+        parts, coef = torch.empty(1, dtype=torch.float64, device=dev), torch.empty(1, dtype=torch.float64, device=dev)
+        L.call("mi355seg_boundary_fwd_f32", _p(logits), _p(phi), N, K, S, _p(loss), _p(parts), _p(coef), _p(ws), ws.numel(), _stream())
+        ctx.save_for_backward(phi, logits, coef)
+        ctx.dims = (N, K, S)
+        ctx.mark_non_differentiable(parts)
+        ctx.set_materialize_grads(False)
+        return loss, parts
+
+    @staticmethod
+    def backward(ctx, g, _gparts):
+        if g is None:
+            return None, None, None
+        phi, logits, coef = ctx.saved_tensors
+        N, K, S = ctx.dims
+        g = g.contiguous().to(torch.float32)
+        d = torch.empty_like(logits)
+        lib().call("mi355seg_boundary_bwd_f32", _p(logits), _p(phi), _p(coef), _p(g), N, K, S, _p(d), _stream())
+        return d, None, None
+
+
+def boundary_loss_full(logits, target, spacing=(1, 1, 1)):
+    """boundary_loss with the term itself in fp64: (boundary fp32 scalar with the autograd edge, fp64[1] = boundary)."""
+    return _BoundaryLoss.apply(logits, target, checked_spacing(spacing, "boundary_loss"))
+
+
+def boundary_loss(logits, target, spacing=(1, 1, 1)):
+    """The boundary loss term (Kervadec et al., MIDL 2019) on logits and one-hot target [N,K,D,H,W]: mean(sigmoid(logits[:, 1:]) *
+    phi) with phi = signed_distance_map(target, spacing) (the single channel when K = 1), the mean over batch, channels and voxels.
+    A float32 scalar carrying the autograd edge to ``logits``; the map is recomputed on the device at every call."""
+    return boundary_loss_full(logits, target, spacing)[0]
+
+
 def two_channel_gt(gt):
     """train.py:190-193 as one kernel: cat([(gt == 0), gt], dim=1) as float for a single-channel label volume."""
     if not gt.is_cuda:

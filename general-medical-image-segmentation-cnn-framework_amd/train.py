@@ -23,7 +23,8 @@ from .registry import build_model
 from .models.three_d.IS import set_band_split
 
 
-LOSS_KEYS = ("loss_weights", "focal_gamma", "tversky_alpha", "tversky_beta", "cldice_weight", "cldice_iters", "cldice_smooth")
+LOSS_KEYS = ("loss_weights", "focal_gamma", "tversky_alpha", "tversky_beta", "cldice_weight", "cldice_iters", "cldice_smooth",
+             "boundary_weight", "boundary_spacing", "boundary_ramp_epochs")
 
 
 def parse_loss(config):
@@ -31,7 +32,9 @@ def parse_loss(config):
     is absent, empty or "bce"; otherwise a utils.loss_function.CompoundLoss built from ``config.loss_weights=wv,wr``,
     ``config.focal_gamma``, ``config.tversky_alpha`` and ``config.tversky_beta`` (each only with a mode that has that term), and the
     soft-clDice term's ``config.cldice_weight`` (>= 0; 0 = no term), ``config.cldice_iters`` (1..32) and ``config.cldice_smooth``
-    (> 0), which go with any compound mode."""
+    (> 0), which go with any compound mode, as do the boundary term's ``config.boundary_weight`` (>= 0; 0 = no term),
+    ``config.boundary_spacing=sz,sy,sx`` (positive; default ``config.resample_spacing`` when that is set, else 1,1,1) and
+    ``config.boundary_ramp_epochs`` (an integer >= 0, see ``boundary_ramp``; kept on the criterion as ``boundary_ramp_epochs``)."""
     from .utils.loss_function import CompoundLoss
     get = lambda k: config.get(k) if hasattr(config, "get") else getattr(config, k, None)
     mode = get("loss")
@@ -44,7 +47,7 @@ def parse_loss(config):
            "tversky_alpha": mode == "tversky", "tversky_beta": mode == "tversky"}
     compound = "a compound mode (" + ", ".join(F.LOSS_MODES) + ")"
     needs = {"loss_weights": compound, "focal_gamma": "focal or dice_focal", "tversky_alpha": "tversky", "tversky_beta": "tversky"}
-    for k in ("cldice_weight", "cldice_iters", "cldice_smooth"):
+    for k in ("cldice_weight", "cldice_iters", "cldice_smooth", "boundary_weight", "boundary_spacing", "boundary_ramp_epochs"):
         has[k], needs[k] = mode is not None, compound
     for k, v in given.items():
         if not has[k]:
@@ -93,11 +96,45 @@ def parse_loss(config):
         if isinstance(v, bool) or not isinstance(v, int) or not 1 <= v <= F.MAX_SKEL_ITERS:
             raise ValueError(f"config.cldice_iters must be an integer in 1..{F.MAX_SKEL_ITERS}, got {given['cldice_iters']!r}")
         kw["cldice_iters"] = v
+    if "boundary_weight" in given:
+        kw["boundary_weight"] = number("boundary_weight", "a number >= 0", lambda v: 0 <= v < float("inf"))
+    spacing = given.get("boundary_spacing")
+    if spacing is None and kw.get("boundary_weight", 0) > 0 and not _absent(get("resample_spacing")):
+        from .resample import _parse_three
+        spacing = _parse_three("resample_spacing", get("resample_spacing"))     # the grid the patches are drawn from
+    if spacing is not None:
+        parts = spacing.strip("()[] ").split(",") if isinstance(spacing, str) else (list(spacing) if hasattr(spacing, "__len__") else [spacing])
+        bad = ValueError(f"config.boundary_spacing must be three positive numbers sz,sy,sx, got {spacing!r}")
+        try:
+            vals = [float(p) for p in parts if not isinstance(p, bool)]
+        except (TypeError, ValueError):
+            raise bad from None
+        if len(parts) != 3 or len(vals) != 3 or not all(0 < v < float("inf") for v in vals):
+            raise bad
+        kw["boundary_spacing"] = tuple(vals)
+    ramp = 0
+    if "boundary_ramp_epochs" in given:
+        v = given["boundary_ramp_epochs"]
+        try:
+            v = int(v) if isinstance(v, str) else v
+        except ValueError:
+            v = None
+        if isinstance(v, bool) or not isinstance(v, int) or not v >= 0:
+            raise ValueError(f"config.boundary_ramp_epochs must be an integer >= 0, got {given['boundary_ramp_epochs']!r}")
+        ramp = v
     if mode == "tversky":
         a, b = kw.get("tversky_alpha", F.TVERSKY_ALPHA), kw.get("tversky_beta", F.TVERSKY_BETA)
         if not a + b > 0:
             raise ValueError(f"config.tversky_alpha and config.tversky_beta must not both be 0, got {a!r} and {b!r}")
-    return CompoundLoss(mode, **kw)
+    criterion = CompoundLoss(mode, **kw)
+    criterion.boundary_ramp_epochs = ramp
+    return criterion
+
+
+def boundary_ramp(weight, epoch, ramp_epochs):
+    """The factor of the boundary term during (1-based) ``epoch``: weight * min(1, epoch / ramp_epochs), the schedule of the paper
+    (the term enters gradually); ramp_epochs = 0: always the weight."""
+    return weight if ramp_epochs <= 0 else weight * min(1.0, epoch / ramp_epochs)
 
 
 class AverageMeter:
@@ -165,6 +202,8 @@ def train(config, model, logger):
     loss_meter, dice_meter = AverageMeter(), AverageMeter()
     for epoch in range(elapsed_epochs + 1, elapsed_epochs + epochs + 1):
         t_epoch = time.time()
+        if criterion is not None and criterion.boundary_weight > 0:     # config.boundary_ramp_epochs; `epoch` survives a resume
+            criterion.set_boundary_scale(boundary_ramp(criterion.boundary_weight, epoch, criterion.boundary_ramp_epochs))
         for i, batch in enumerate(loader):
             t0 = time.time()
             x, gt = batch["source"]["data"], batch["gt"]["data"]
@@ -186,10 +225,8 @@ def train(config, model, logger):
             if scalars:
                 row = {"iteration": iteration, "Training/Loss": loss_meter.val, "Training/dice": dice_meter.val}
                 if criterion is not None:                       # a compound loss: its terms, unweighted
-                    terms = out["loss_terms"].tolist()
-                    row["Training/loss_voxel"], row["Training/loss_region"] = terms[:2]
-                    if len(terms) > 2:                          # config.cldice_weight > 0
-                        row["Training/loss_cldice"] = terms[2]
+                    for name, v in zip(criterion.term_names, out["loss_terms"].tolist()):
+                        row[f"Training/loss_{name}"] = v        # voxel, region, then cldice / boundary when their weights are > 0
                 scalars.write(json.dumps(row) + "\n")
                 scalars.flush()
             logger.info(f"\nEpoch: {epoch} Batch: {i}, train time: {time.time() - t0:.3f}s\nLoss: {loss_meter.val}\nDice: {dice_meter.val}\n")

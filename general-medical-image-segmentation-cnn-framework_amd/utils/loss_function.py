@@ -114,10 +114,16 @@ class CompoundLoss(nn.Module):
     mask, counts, terms), which engine.train_step uses in place of criterion + two argmaxes + dice_counts.
     ``cldice_weight`` > 0 adds the soft-clDice term (functional.soft_cldice with ``cldice_iters`` and ``cldice_smooth``; DESIGN.md
     4.20): loss = tail loss + cldice_weight * cldice and ``terms`` gains a third entry, the unweighted cldice.  With the weight 0
-    the object is what it is without the three arguments: the same launches and the same bits."""
+    the object is what it is without the three arguments: the same launches and the same bits.
+    ``boundary_weight`` > 0 adds the boundary term (functional.boundary_loss with the voxel spacing ``boundary_spacing``; DESIGN.md
+    4.21): loss += boundary_scale * boundary, where ``boundary_scale`` is a float32[1] device buffer that starts at the weight and
+    that ``set_boundary_scale`` refills in place (a captured HIP graph sees the change: the ramp of config.boundary_ramp_epochs);
+    ``terms`` gains the unweighted boundary value, after the clDice entry when both are on.  ``term_names`` names the entries of
+    ``terms``.  With the weight 0: the same launches and the same bits as without the two arguments."""
 
     def __init__(self, mode, weights=(1, 1), focal_gamma=2.0, tversky_alpha=0.3, tversky_beta=0.7,
-                 cldice_weight=0.0, cldice_iters=F.CLDICE_ITERS, cldice_smooth=F.CLDICE_SMOOTH):
+                 cldice_weight=0.0, cldice_iters=F.CLDICE_ITERS, cldice_smooth=F.CLDICE_SMOOTH,
+                 boundary_weight=0.0, boundary_spacing=(1, 1, 1)):
         super().__init__()
         self.mode = mode
         self.spec = F.LossSpec.from_mode(mode, weights, focal_gamma, tversky_alpha, tversky_beta)
@@ -128,14 +134,43 @@ class CompoundLoss(nn.Module):
             raise ValueError(f"cldice_smooth must be a number > 0, got {cldice_smooth!r}")
         self.cldice_weight, self.cldice_smooth = float(cldice_weight), float(cldice_smooth)
         self.cldice_iters = F.checked_skel_iters(cldice_iters, "cldice_iters")
+        if not number(boundary_weight) or not 0 <= boundary_weight < float("inf"):
+            raise ValueError(f"boundary_weight must be a number >= 0, got {boundary_weight!r}")
+        self.boundary_weight = float(boundary_weight)
+        self.boundary_spacing = F.checked_spacing(boundary_spacing, "boundary_spacing")
+        if self.boundary_weight > 0:                # (a plain attribute would not follow .to(); a buffer must not enter a state_dict)
+            self.register_buffer("boundary_scale", torch.full((1,), self.boundary_weight, dtype=torch.float32), persistent=False)
+
+    @property
+    def term_names(self):
+        """The names of the entries of ``terms``, in order."""
+        return ("voxel", "region") + (("cldice",) if self.cldice_weight > 0 else ()) + (("boundary",) if self.boundary_weight > 0 else ())
+
+    def set_boundary_scale(self, value):
+        """Fill ``boundary_scale`` in place: the factor of the boundary term from the next step on, captured graphs included."""
+        if not self.boundary_weight > 0:
+            raise ValueError("set_boundary_scale: this loss has no boundary term (boundary_weight = 0)")
+        if isinstance(value, bool) or not isinstance(value, (int, float)) or not 0 <= value < float("inf"):
+            raise ValueError(f"set_boundary_scale: expected a number >= 0, got {value!r}")
+        self.boundary_scale.fill_(float(value))
 
     def tail(self, pred, target):
         out = F.loss_tail(pred, target, self.spec)
-        if not self.cldice_weight > 0:
+        if not self.cldice_weight > 0 and not self.boundary_weight > 0:
             return out
         loss, mask, counts, terms = out
-        cl, parts = F.soft_cldice_full(pred, target, self.cldice_iters, self.cldice_smooth)
-        return loss + self.cldice_weight * cl, mask, counts, torch.cat([terms, parts[:1]])
+        extra = [terms]
+        if self.cldice_weight > 0:
+            cl, parts = F.soft_cldice_full(pred, target, self.cldice_iters, self.cldice_smooth)
+            loss = loss + self.cldice_weight * cl
+            extra.append(parts[:1])
+        if self.boundary_weight > 0:
+            if self.boundary_scale.device != pred.device:
+                self.boundary_scale = self.boundary_scale.to(pred.device)        # (once: a criterion is built on the host)
+            bd, parts = F.boundary_loss_full(pred, target, self.boundary_spacing)
+            loss = loss + (self.boundary_scale * bd).reshape(())
+            extra.append(parts)
+        return loss, mask, counts, torch.cat(extra)
 
     def forward(self, pred, target):
         return self.tail(pred, target)[0]
@@ -144,4 +179,6 @@ class CompoundLoss(nn.Module):
         s = f"mode={self.mode!r}, spec={tuple(self.spec)!r}"
         if self.cldice_weight > 0:
             s += f", cldice=(weight={self.cldice_weight!r}, iters={self.cldice_iters!r}, smooth={self.cldice_smooth!r})"
+        if self.boundary_weight > 0:
+            s += f", boundary=(weight={self.boundary_weight!r}, spacing={self.boundary_spacing!r})"
         return s

@@ -704,6 +704,44 @@ int mi355seg_cldice_bwd_head_f32(const float* T, const double* coef, long long n
 int mi355seg_cldice_bwd_tail_f32(const float* g_p, const float* skel_t, const float* P, const double* coef, const float* gscale,
                                  long long N, int K, long long S, float* dlogits, void* stream);
 
+/* Boundary loss term (csrc/boundary.hip; no reference line in this project's model: the official boundary-loss of
+ * Kervadec et al., MIDL 2019 -- utils.py's one_hot2dist and losses.py's SurfaceLoss).  Channels c0 .. K - 1 take part, c0 = 1 for
+ * K > 1 (the background channel is left out), 0 for K = 1, as in mi355seg_cldice_probs_f32; 1 <= K <= 16.
+ *
+ * mi355seg_sdm_f32: the signed Euclidean distance map of every class of the float one-hot target [N, K, D, H, W] (W fastest;
+ *   voxel v belongs to class k when target[n, k, v] > 0.5) under the voxel spacing (sz, sy, sx): phi fp32 [N, K - c0, D, H, W] with
+ *     phi = +dist(v, nearest voxel of the class)                 outside the class,
+ *     phi = -(dist(v, nearest voxel not of the class) - offset)  inside the class,
+ *     phi = 0 for the whole (n, k) volume where the opposite set is empty (class absent from the patch, or class fills it).
+ *   Distances are taken inside the patch only.  DEVIATION from one_hot2dist, whose inside branch is (posdist - 1): that is right at
+ *   unit spacing only (at spacing 0.7 it gives +0.3 on the inner boundary, the wrong sign).  Callers pass offset = min(sz, sy, sx),
+ *   the smallest distance an inside voxel can have: the official map at unit spacing, and never positive inside at any spacing.
+ *   Three separable fp32 passes (W from wave ballots, H and D as min-plus steps through LDS), no fp64, no atomics: two runs are
+ *   bitwise equal and a batched run has the bits of single-volume runs.  At unit spacing every squared distance is an integer below
+ *   2^24, so the map is the correctly rounded square root of the exact squared distance.  Each axis at most 2047.
+ *   ws: mi355seg_sdm_ws_bytes(N, K, D, H, W) (0 for bad arguments): 12 bytes per voxel of phi.
+ * mi355seg_sdm_steps_f32: the same call cut short after its first `steps` of three launches (W, H, D): phi is written only with
+ *   steps = 3.  For tools/bench_boundary.py, which times each launch as the difference of two prefixes.
+ * mi355seg_boundary_fwd_f32: sum sigmoid(logits[:, c0:]) * phi over n = N (K - c0) S elements as fp64 partials in fixed order, one
+ *   pass, then one block: loss fp32[1] = sum / n, parts fp64[1] = the same in fp64, coef fp64[1] = 1 / n, all on the device
+ *   (nothing passes through the host: capturable in a HIP graph).  logits [N, K, S], phi [N, K - c0, S].
+ *   ws: mi355seg_boundary_ws_bytes(n) (0 for n < 1).
+ * mi355seg_boundary_bwd_f32: dlogits[:, c0:] = gscale[0] coef[0] phi p (1 - p), p = sigmoid(logits), in one pass (16-byte accesses
+ *   when S % 4 == 0 and the pointers are aligned); channel 0 (K > 1) gets zeros.  dlogits is [N, K, S].
+ * Refused before any launch, with mi355seg_last_error: null pointers, non-positive extents or spacing, a negative offset, K outside
+ * 1..16, an axis above 2047, more than 2^31 - 1 voxels per (n, k) volume or tiles per launch (one block per 64 x 32 tile: beyond
+ * any memory), steps outside 1..3, a workspace that is too small. */
+size_t mi355seg_sdm_ws_bytes(long long N, int K, int D, int H, int W);
+int mi355seg_sdm_f32(const float* target, long long N, int K, int D, int H, int W, float sz, float sy, float sx, float offset,
+                     float* phi, void* ws, size_t ws_bytes, void* stream);
+int mi355seg_sdm_steps_f32(const float* target, long long N, int K, int D, int H, int W, float sz, float sy, float sx, float offset,
+                           float* phi, void* ws, size_t ws_bytes, int steps, void* stream);
+size_t mi355seg_boundary_ws_bytes(long long n);
+int mi355seg_boundary_fwd_f32(const float* logits, const float* phi, long long N, int K, long long S,
+                              float* loss, double* parts, double* coef, void* ws, size_t ws_bytes, void* stream);
+int mi355seg_boundary_bwd_f32(const float* logits, const float* phi, const double* coef, const float* gscale,
+                              long long N, int K, long long S, float* dlogits, void* stream);
+
 /* Sum-type reductions for the library losses (loss_function.py:61-185):
  * out[0]=sum(a*b) out[1]=sum(a) out[2]=sum(b) out[3]=sum(a*a) out[4]=sum(b*b), a = sigmoid(x) if
  * apply_sigmoid else x.  Deterministic wavefront-shuffle + two-stage reduce. */
