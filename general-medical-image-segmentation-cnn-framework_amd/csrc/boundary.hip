@@ -19,6 +19,7 @@
 // offset; an infinite distance (the opposite set is empty) becomes 0, so the rule above needs no reduction and no host round trip.
 // At unit spacing every squared distance is an integer below 2^24 (3 * 2047^2 < 2^24): fp32 is exact there.
 #include "common.h"
+#include "edt.h"
 #include "loss_math.h"
 #include "reduce.h"
 
@@ -63,20 +64,7 @@ __global__ __launch_bounds__(kSdmThreads) void sdm_pass_w_kernel(const float* __
         const unsigned long long* bits = p ? bn : bm;
         unsigned short* __restrict__ dst = (p ? off_n : off_m) + l * W;
         for (int k = 0; k < nw; ++k) {
-            const int x = k * kWave + lane;
-            const unsigned long long own = bits[k];
-            const unsigned long long le = own & (~0ull >> (kWave - 1 - lane));     // bits 0..lane
-            const unsigned long long ge = own & (~0ull << lane);                  // bits lane..63
-            int left = -1, right = -1;
-            if (le) left = lane - (63 - __clzll((long long)le));
-            else
-                for (int q = k - 1; q >= 0; --q)
-                    if (bits[q]) { left = x - (q * kWave + 63 - __clzll((long long)bits[q])); break; }
-            if (ge) right = (__ffsll((long long)ge) - 1) - lane;
-            else
-                for (int q = k + 1; q < nw; ++q)
-                    if (bits[q]) { right = q * kWave + (__ffsll((long long)bits[q]) - 1) - x; break; }
-            const int best = left < 0 ? right : (right < 0 ? left : min(left, right));
+            const int x = k * kWave + lane, best = nearest_set_bit(bits, nw, k, lane);
             if (live && x < W) dst[x] = best < 0 ? kSdmNone : (unsigned short)best;
         }
     }
@@ -108,10 +96,6 @@ template <typename InT, bool kLast>
 __global__ __launch_bounds__(kSdmThreads) void sdm_pass_axis_kernel(const InT* __restrict__ in_m, const InT* __restrict__ in_n,
         float* __restrict__ out_m, float* __restrict__ out_n, const float* __restrict__ target, int Kp, int K, int c0,
         int n, long long stride, int inner, long long outer_stride, float s, float s_in, float offset) {
-    // s*i and s*j are each rounded on their own, never contracted into the subtraction, so that i == j gives exactly 0
-#pragma clang fp contract(off)
-    __shared__ float tm[kSdmTJ][kSdmTW];
-    __shared__ float tn[kSdmTJ][kSdmTW];
     const int tx = threadIdx.x % kSdmTW, ty = threadIdx.x / kSdmTW;
     const int ncb = (inner + kSdmTW - 1) / kSdmTW, nrb = (n + kSdmRows - 1) / kSdmRows;
     const long long b = blockIdx.x;
@@ -121,48 +105,26 @@ __global__ __launch_bounds__(kSdmThreads) void sdm_pass_axis_kernel(const InT* _
     const long long o = q / nrb, base = o * outer_stride;
     const int col = cb * kSdmTW + tx, i0 = rb * kSdmRows + ty * kSdmRI;
     const bool live = col < inner;
-    float am[kSdmRI], an[kSdmRI], si[kSdmRI];
+    float acc[kLast ? 1 : 2][kSdmRI];       // kLast: the polarity mem[r] selects; else [0] member, [1] non-member
     bool mem[kSdmRI];
 #pragma unroll
     for (int r = 0; r < kSdmRI; ++r) {
-        am[r] = INFINITY; an[r] = INFINITY; si[r] = s * (float)(i0 + r);
         mem[r] = false;
         if (kLast && live && i0 + r < n)
             mem[r] = target[((o / Kp) * K + c0 + o % Kp) * outer_stride + (long long)(i0 + r) * stride + col] > 0.5f;
     }
-    for (int j0 = 0; j0 < n; j0 += kSdmTJ) {
-        const int nj = min(kSdmTJ, n - j0);
-        __syncthreads();
-        for (int j = ty; j < nj; j += kSdmTY) {
-            const long long g = base + (long long)(j0 + j) * stride + col;
-            tm[j][tx] = live ? sdm_load(in_m + g, s_in) : INFINITY;
-            tn[j][tx] = live ? sdm_load(in_n + g, s_in) : INFINITY;
-        }
-        __syncthreads();
-        for (int j = 0; j < nj; ++j) {
-            const float fm = tm[j][tx], fn = tn[j][tx], sj = s * (float)(j0 + j);
-#pragma unroll
-            for (int r = 0; r < kSdmRI; ++r) {
-                const float d = si[r] - sj;
-                if (kLast) {
-                    am[r] = fminf(am[r], fmaf(d, d, mem[r] ? fn : fm));
-                } else {
-                    am[r] = fminf(am[r], fmaf(d, d, fm));
-                    an[r] = fminf(an[r], fmaf(d, d, fn));
-                }
-            }
-        }
-    }
+    const auto load = [=](int p, int j) { return live ? sdm_load((p ? in_n : in_m) + base + (long long)j * stride + col, s_in) : INFINITY; };
+    minplus_axis<float, 2, kLast, kSdmTW, kSdmTY, kSdmTJ, kSdmRI>(acc, mem, load, n, s, i0, tx, ty);
     if (live) {
 #pragma unroll
         for (int r = 0; r < kSdmRI; ++r) {
             if (i0 + r >= n) continue;
             const long long g = base + (long long)(i0 + r) * stride + col;
-            if (kLast) {
-                out_m[g] = am[r] == INFINITY ? 0.f : (mem[r] ? -sdm_sqrt_minus(am[r], offset) : sqrtf(am[r]));
+            if constexpr (kLast) {
+                out_m[g] = acc[0][r] == INFINITY ? 0.f : (mem[r] ? -sdm_sqrt_minus(acc[0][r], offset) : sqrtf(acc[0][r]));
             } else {
-                out_m[g] = am[r];
-                out_n[g] = an[r];
+                out_m[g] = acc[0][r];
+                out_n[g] = acc[1][r];
             }
         }
     }

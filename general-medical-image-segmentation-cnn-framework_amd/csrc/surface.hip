@@ -6,6 +6,7 @@
 // voxels and every (i, j) pair costs one fp64 subtract, one fma and one min: at 256^3 the two strided passes are bound by the fp64
 // rate, not by HBM (1.2 ms each), and the whole metric stays an order of magnitude below the forward it grades.
 #include "common.h"
+#include "edt.h"
 #include "internal.h"
 
 namespace seg {
@@ -82,8 +83,8 @@ __global__ __launch_bounds__(kSurfThreads) void mask_edges_kernel(const int64_t*
 }
 
 // EDT pass 1, along W (contiguous): |x - nearest site in the line| as int32, -1 where the line holds no site.  One wave per line:
-// the line's site bits go to LDS as 64-bit ballots, each lane then finds the nearest set bit on either side with clz / ctz and a
-// walk over whole words.  Box-relative output [2][bd][bh][bw]; the input is the full-volume edge map.
+// the line's site bits go to LDS as 64-bit ballots, each lane then finds the nearest set bit on either side (edt.h).
+// Box-relative output [2][bd][bh][bw]; the input is the full-volume edge map.
 __global__ __launch_bounds__(kSurfThreads) void edt_pass_w_kernel(const uint8_t* __restrict__ sites, long long mask_stride, int H, int W,
         int z0, int y0, int x0, int bd, int bh, int bw, int* __restrict__ out) {
     extern __shared__ unsigned long long edt_bits[];
@@ -107,20 +108,7 @@ __global__ __launch_bounds__(kSurfThreads) void edt_pass_w_kernel(const uint8_t*
         int* __restrict__ dst = out + m * box + r * bw;
         for (int k = 0; k < nw; ++k) {
             const int x = k * kWave + lane;
-            const unsigned long long own = bits[k];
-            const unsigned long long le = own & (~0ull >> (kWave - 1 - lane));     // bits 0..lane
-            const unsigned long long ge = own & (~0ull << lane);                  // bits lane..63
-            int left = -1, right = -1;
-            if (le) left = lane - (63 - __clzll((long long)le));
-            else
-                for (int q = k - 1; q >= 0; --q)
-                    if (bits[q]) { left = x - (q * kWave + 63 - __clzll((long long)bits[q])); break; }
-            if (ge) right = (__ffsll((long long)ge) - 1) - lane;
-            else
-                for (int q = k + 1; q < nw; ++q)
-                    if (bits[q]) { right = q * kWave + (__ffsll((long long)bits[q]) - 1) - x; break; }
-            const int best = left < 0 ? right : (right < 0 ? left : min(left, right));
-            if (live && x < bw) dst[x] = best;
+            if (live && x < bw) dst[x] = nearest_set_bit(bits, nw, k, lane);
         }
         __syncthreads();
     }
@@ -145,36 +133,19 @@ __device__ __forceinline__ double edt_load(const double* p, double) { return *p;
 template <typename InT, int RI>
 __global__ __launch_bounds__(kSurfThreads) void edt_pass_axis_kernel(const InT* __restrict__ in, double* __restrict__ out, int n, long long stride,
         int inner, long long outer_stride, double s, double s_in) {
-    // s*i and s*j are each rounded on their own, never contracted into the subtraction, so that i == j gives exactly 0
-#pragma clang fp contract(off)
-    __shared__ double tile[kEdtTJ][kEdtTW];
     const int tx = threadIdx.x % kEdtTW, ty = threadIdx.x / kEdtTW;
     const int col = blockIdx.x * kEdtTW + tx;
     const int i0 = blockIdx.y * (RI * kEdtTY) + ty * RI;
     const long long base = (long long)blockIdx.z * outer_stride;
     const bool live = col < inner;
-    double acc[RI], si[RI];
-#pragma unroll
-    for (int r = 0; r < RI; ++r) { acc[r] = HUGE_VAL; si[r] = s * (double)(i0 + r); }
-    for (int j0 = 0; j0 < n; j0 += kEdtTJ) {
-        const int nj = min(kEdtTJ, n - j0);
-        __syncthreads();
-        for (int j = ty; j < nj; j += kEdtTY)
-            tile[j][tx] = live ? edt_load(in + base + (long long)(j0 + j) * stride + col, s_in) : HUGE_VAL;
-        __syncthreads();
-        for (int j = 0; j < nj; ++j) {
-            const double fj = tile[j][tx], sj = s * (double)(j0 + j);
-#pragma unroll
-            for (int r = 0; r < RI; ++r) {
-                const double d = si[r] - sj;
-                acc[r] = fmin(acc[r], fma(d, d, fj));
-            }
-        }
-    }
+    double acc[1][RI];
+    const bool none[RI] = {};           // one plane: no row selects
+    const auto load = [=](int, int j) { return live ? edt_load(in + base + (long long)j * stride + col, s_in) : HUGE_VAL; };
+    minplus_axis<double, 1, false, kEdtTW, kEdtTY, kEdtTJ, RI>(acc, none, load, n, s, i0, tx, ty);
     if (live) {
 #pragma unroll
         for (int r = 0; r < RI; ++r)
-            if (i0 + r < n) out[base + (long long)(i0 + r) * stride + col] = acc[r];
+            if (i0 + r < n) out[base + (long long)(i0 + r) * stride + col] = acc[0][r];
     }
 }
 

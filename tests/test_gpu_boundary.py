@@ -13,6 +13,7 @@ Bounds:
   * the loss: 1e-6 * max(1, |ref|) (LOSS_TOL of tests/test_gpu_loss_tail.py); dlogits: 1e-9 + 2e-5 * max|ref| (LIB_GRAD).
 Every graded figure is printed beside its bound (``pytest -rA``)."""
 import ctypes
+import hashlib
 import json
 import math
 import os
@@ -25,6 +26,7 @@ import torch
 
 from test_boundary_host import boundary_masks, cpu32_sdm, ref_boundary, ref_sdm
 from test_cldice_host import ref_cldice
+from test_gpu_hd95 import check_pins
 
 pytestmark = pytest.mark.gpu
 
@@ -39,6 +41,7 @@ UP = 1.7
 SHAPES = [(1, 1, 1, 1, 1), (1, 2, 1, 1, 5), (2, 2, 3, 5, 7), (3, 3, 4, 9, 11), (1, 1, 2, 3, 130), (1, 1, 33, 33, 65), (1, 2, 32, 64, 64),
           (1, 1, 2, 3, 600), (1, 1, 2, 300, 3), (1, 1, 300, 2, 3)]
 ANISO = [(2.5, 0.7, 0.7), (1, 1, 3)]
+PIN_SPACINGS = [(1, 1, 1)] + ANISO + [(0.7, 0.7, 0.7)]
 
 
 @pytest.fixture(scope="module")
@@ -118,6 +121,29 @@ def test_map_at_anisotropic_spacing(seg, shape, spacing):
         ek, ec = float(np.abs(got.astype(np.float64) - ref).max()), float(np.abs(c32.astype(np.float64) - ref).max())
         print(f"[boundary] map {_sid(shape)} spacing {spacing} {name}: kernel {ek:.3e}  CPU-fp32 {ec:.3e}  bound {4 * ec:.3e}  (max|ref| {np.abs(ref).max():.4g})")
         assert np.isfinite(got).all() and ek <= 4 * ec, name
+
+
+def sdm_pin_digests(F):
+    """"<shape> <spacing>" -> {"input", "output"}: SHA-256 over the masks of the shape in sorted name order, of the targets' bytes and
+    the spacing, and of the bytes of functional.signed_distance_map"""
+    out = {}
+    for shape in SHAPES:
+        masks = _masks(shape)
+        for spacing in PIN_SPACINGS:
+            hin, hout = hashlib.sha256(np.asarray(spacing, np.float64).tobytes()), hashlib.sha256()
+            for name in sorted(masks):
+                hin.update(masks[name].numpy().tobytes())
+                hout.update(F.signed_distance_map(masks[name].cuda(), spacing).cpu().numpy().tobytes())
+            out[f"{_sid(shape)} {spacing}"] = {"input": hin.hexdigest(), "output": hout.hexdigest()}
+    return out
+
+
+def test_map_bits_equal_the_recorded_digests(seg):
+    """tests/golden/edt_pins.json: the bytes of the map on every shape and mask above at four spacings, recorded before boundary.hip
+    and surface.hip came to share csrc/edt.h -- the anisotropic maps too, which the tests above hold to a 4 x bound only"""
+    with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "edt_pins.json")) as fh:
+        pins = json.load(fh)
+    check_pins(sdm_pin_digests(seg.functional), pins["signed_distance_map"], "signed_distance_map")
 
 
 def test_the_sign_is_never_wrong_at_a_spacing_below_one(seg):

@@ -2,7 +2,9 @@
 distances, HD95 and the confusion counters, against tests/golden/hd95.npz (the reference's ``metric(gt, pred, spacing)`` run from
 its own file, see tests/golden/make_hd95.py) and against the brute-force fp64 comparator of tests/test_hd95_fixture.py."""
 import csv
+import hashlib
 import importlib.util
+import json
 import os
 
 import numpy as np
@@ -76,39 +78,81 @@ def test_mask_edges_equal_the_six_neighbour_definition(seg):
     assert torch.equal(e3[0].cpu().bool(), edges6(hd95_cases()[0][1]))
 
 
-def test_edt3d_is_exact_at_every_voxel(seg):
-    F = seg.functional
-    for name, gt, pred, sp, _, _ in hd95_cases():
-        sites = torch.stack([edges6(gt), edges6(pred)]).to(torch.uint8)
-        _check_edt(F, sites, sp)
+_EDT_CASES = []
+
+
+def edt_cases():
+    """[(name, sites uint8 [2, D, H, W], spacing, box or None)]: the inputs of the exactness test and of the recorded digests
+    (tests/golden/make_edt_pins.py) -- made once, shared, never modified"""
+    if _EDT_CASES:
+        return _EDT_CASES
+    out = [(name, torch.stack([edges6(gt), edges6(pred)]).to(torch.uint8), sp, None) for name, gt, pred, sp, _, _ in hd95_cases()]
     # odd extents, with sites drawn at random
     g = torch.Generator().manual_seed(3)
-    odd = (torch.rand((2, 13, 37, 71), generator=g) > 0.995).to(torch.uint8)
-    _check_edt(F, odd, (1.3, 0.7, 2.1))
+    out.append(("odd", (torch.rand((2, 13, 37, 71), generator=g) > 0.995).to(torch.uint8), (1.3, 0.7, 2.1), None))
     # a one-voxel-thick volume along each axis
     for shape in [(1, 19, 45), (17, 1, 33), (9, 21, 1)]:
-        thin = (torch.rand((2,) + shape, generator=g) > 0.97).to(torch.uint8)
-        _check_edt(F, thin, (0.8, 1.0, 1.7))
+        out.append(("thin" + "x".join(str(v) for v in shape), (torch.rand((2,) + shape, generator=g) > 0.97).to(torch.uint8), (0.8, 1.0, 1.7), None))
     # lines longer than one LDS tile of the axis passes (64 rows), than one block of output rows (256), and than one 64-bit word
     # of the pass along W
     long = torch.zeros((2, 300, 5, 150), dtype=torch.uint8)
     long[0, 7, 2, 3] = long[0, 290, 4, 140] = long[0, 150, 0, 70] = 1
     long[1, 299, 0, 149] = 1
-    _check_edt(F, long, (0.5, 3.0, 1.1))
+    out.append(("long", long, (0.5, 3.0, 1.1), None))
     tall = torch.zeros((2, 3, 270, 66), dtype=torch.uint8)
     tall[0, 1, 269, 0] = tall[0, 0, 0, 65] = tall[1, 2, 130, 64] = 1
-    _check_edt(F, tall, (1.0, 0.9, 1.0))
-    # a box inside the volume: the distances the whole volume gives there.  Not bit for bit: the kernel forms s*i - s*j from
-    # box-relative indices, and each product is rounded at its own magnitude; with indices below 64 that is at most 64 * 2^-52 =
-    # 1.4e-14 of a term, so 1e-13 on the distance
+    out.append(("tall", tall, (1.0, 0.9, 1.0), None))
+    # a box inside the volume
     sites = torch.zeros((2, 20, 30, 40), dtype=torch.uint8)
     sites[0, 5:9, 7:20, 11:30] = 1
     sites[1, 6, 8, 12] = sites[1, 10, 21, 33] = 1
-    box = (4, 6, 10, 8, 17, 25)
-    part = _check_edt(F, sites, (1.1, 0.6, 0.9), box)
-    whole = F.edt3d(sites.cuda(), (1.1, 0.6, 0.9)).sqrt()
-    sub = whole[:, 4:12, 6:23, 10:35]
-    assert bool(((part - sub).abs() <= 1e-13 * sub).all())
+    out.append(("boxed", sites, (1.1, 0.6, 0.9), (4, 6, 10, 8, 17, 25)))
+    _EDT_CASES.extend(out)
+    return _EDT_CASES
+
+
+def test_edt3d_is_exact_at_every_voxel(seg):
+    F = seg.functional
+    for name, sites, sp, box in edt_cases():
+        part = _check_edt(F, sites, sp, box)
+        if box is None:
+            continue
+        # the distances the whole volume gives inside the box.  Not bit for bit: the kernel forms s*i - s*j from box-relative
+        # indices, and each product is rounded at its own magnitude; with indices below 64 that is at most 64 * 2^-52 = 1.4e-14 of
+        # a term, so 1e-13 on the distance
+        z0, y0, x0, bd, bh, bw = box
+        sub = F.edt3d(sites.cuda(), sp).sqrt()[:, z0:z0 + bd, y0:y0 + bh, x0:x0 + bw]
+        assert bool(((part - sub).abs() <= 1e-13 * sub).all())
+
+
+def edt_pin_digests(F):
+    """name -> {"input", "output"}: SHA-256 of every case's sites, spacing and box, and of the bytes of functional.edt3d's fp64
+    squared distances (a boxed case: the box run, then the whole-volume run)"""
+    out = {}
+    for name, sites, sp, box in edt_cases():
+        hin = hashlib.sha256(sites.numpy().tobytes() + np.asarray(sp, np.float64).tobytes() + np.asarray(box or (), np.int64).tobytes())
+        hout = hashlib.sha256()
+        for b in ([box, None] if box else [None]):
+            hout.update(F.edt3d(sites.cuda(), sp, b).cpu().numpy().tobytes())
+        out[name] = {"input": hin.hexdigest(), "output": hout.hexdigest()}
+    return out
+
+
+def check_pins(got, want, what):
+    """recomputed digests against the recorded ones, every case by name"""
+    assert sorted(got) == sorted(want), f"{what}: the cases changed: {sorted(set(got) ^ set(want))}"
+    for name in sorted(got):
+        assert got[name]["input"] == want[name]["input"], f"{what} {name}: inputs changed (the recorded digest is of other bytes)"
+    bad = [name for name in sorted(got) if got[name]["output"] != want[name]["output"]]
+    assert not bad, f"{what}: the output bits differ from the recorded ones in {bad}"
+
+
+def test_edt3d_bits_equal_the_recorded_digests(seg):
+    """tests/golden/edt_pins.json: the bytes of edt3d's output on every case of edt_cases(), recorded before surface.hip and
+    boundary.hip came to share csrc/edt.h -- all four edt_pass_axis_kernel instantiations, several LDS chunks and ballot words"""
+    with open(os.path.join(GOLDEN, "edt_pins.json")) as fh:
+        pins = json.load(fh)
+    check_pins(edt_pin_digests(seg.functional), pins["edt3d"], "edt3d")
 
 
 def _large_pair():
