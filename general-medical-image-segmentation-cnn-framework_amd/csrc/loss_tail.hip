@@ -133,14 +133,32 @@ __global__ __launch_bounds__(kTailThreads) void loss_tail_fwd_kernel(const float
 // A thread stands for (row group g, column j) of the partial table [nblk][R], R = 1 + 5 K: it adds the rows g, g + G, ... of its
 // column (G = 1024 / R groups; neighbouring threads read neighbouring doubles), and column j's G group sums are then added in
 // ascending g by one thread -- all columns at once, independent loads, one barrier; the counters likewise as 4 columns x 256 groups.
+// CLS (the label form): the class counters' partial table kpart [nblk][3 K] is reduced beside the two others, the same way (3 K
+// columns x 1024 / (3 K) groups, then one thread per column in ascending group), into class_counts int64[3 K].
 constexpr int kTailFinThreads = 1024;
-__global__ __launch_bounds__(kTailFinThreads) void loss_tail_finalize_kernel(const double* __restrict__ part, const long long* __restrict__ cpart,
-        int nblk, int K, int vmode, int rmode, double alpha, double beta, double wv, double wr, double M, double Vox,
-        float* __restrict__ loss, double* __restrict__ terms, double* __restrict__ sums, int64_t* __restrict__ counts,
-        double* __restrict__ coef) {
+template <bool CLS>
+__device__ __forceinline__ void tail_finalize(const double* __restrict__ part, const long long* __restrict__ cpart,
+        const long long* __restrict__ kpart, int nblk, int K, int vmode, int rmode, double alpha, double beta, double wv, double wr,
+        double M, double Vox, float* __restrict__ loss, double* __restrict__ terms, double* __restrict__ sums,
+        int64_t* __restrict__ counts, double* __restrict__ coef, int64_t* __restrict__ class_counts) {
     __shared__ double red[kTailFinThreads];
     __shared__ long long redc[kTailFinThreads];
     __shared__ double tot[1 + 5 * kTailMaxClasses];
+    if constexpr (CLS) {
+        __shared__ long long redk[kTailFinThreads];
+        const int C = 3 * K, GK = kTailFinThreads / C, jk = threadIdx.x % C, gk = threadIdx.x / C;
+        long long ck = 0;
+        if (gk < GK)
+            for (int i = gk; i < nblk; i += GK) ck += kpart[(long long)i * C + jk];
+        redk[threadIdx.x] = ck;
+        __syncthreads();
+        if (threadIdx.x >= 192 && threadIdx.x < 192 + C) {          // (a wavefront of its own, as the four counters below)
+            const int col = threadIdx.x - 192;
+            long long s = redk[col];
+            for (int q = 1; q < GK; ++q) s += redk[q * C + col];
+            class_counts[col] = s;
+        }
+    }
     const int R = 1 + 5 * K, G = kTailFinThreads / R;
     const int tid = threadIdx.x, j = tid % R, g = tid / R;
     double a = 0.0;
@@ -193,6 +211,13 @@ __global__ __launch_bounds__(kTailFinThreads) void loss_tail_finalize_kernel(con
     terms[0] = voxel;
     terms[1] = region;
     loss[0] = (float)(wv * voxel + wr * region);
+}
+
+__global__ __launch_bounds__(kTailFinThreads) void loss_tail_finalize_kernel(const double* __restrict__ part, const long long* __restrict__ cpart,
+        int nblk, int K, int vmode, int rmode, double alpha, double beta, double wv, double wr, double M, double Vox,
+        float* __restrict__ loss, double* __restrict__ terms, double* __restrict__ sums, int64_t* __restrict__ counts,
+        double* __restrict__ coef) {
+    tail_finalize<false>(part, cpart, nullptr, nblk, K, vmode, rmode, alpha, beta, wv, wr, M, Vox, loss, terms, sums, counts, coef, nullptr);
 }
 
 // a + b with both operands already rounded to fp32: the addition is not contracted with the product that formed an operand
@@ -321,6 +346,345 @@ static void tail_launch_bwd(int KT, int nblk, hipStream_t st, const float* x, co
 
 static bool tail_aligned16(const void* p) { return ((uintptr_t)p % 16) == 0; }
 
+// ----------------------------------------------------------------------------- the label form (config.multiclass)
+// The same tail with a uint8 label map [N,S] in place of the float one-hot target [N,K,S].  CONTRACT: for labels in [0, K) every
+// output has the bits the kernels above give on onehot(labels); a label >= K is the all-zero column (argmax 0, member of no class).
+// How it is kept: the same thread-to-voxel map, the same per-thread accumulation order, the same partial table and the same
+// finalise; the target value b = (label == k) goes through tail_opaque, so that the compiler meets an unknown float where the
+// one-hot kernels meet a load and forms the per-element expressions (and their fused multiply-adds) the same way.  What the label
+// form drops: sum t and sum t^2 are the integer gt_k, exact in fp64 in any order, so two of the five fp64 accumulators per class
+// become one 32-bit counter, and the room goes to the class counters tp_k, pred_k (a thread sees fewer than 2^31 voxels; they are
+// widened to int64 in the block reduction).  Class membership is a comparison, never an index.
+
+__device__ __forceinline__ float tail_opaque(float b) {
+    asm("" : "+v"(b));
+    return b;
+}
+
+// the labels of V consecutive voxels: one 4-byte load for V = 4
+template <int V>
+__device__ __forceinline__ void tail_load_lab(const uint8_t* __restrict__ p, int (&v)[V]) {
+    if constexpr (V == 4) {
+        const uint32_t a = *reinterpret_cast<const uint32_t*>(p);
+        v[0] = a & 255u; v[1] = (a >> 8) & 255u; v[2] = (a >> 16) & 255u; v[3] = a >> 24;
+    } else {
+        v[0] = p[0];
+    }
+}
+
+// part, cpart: as loss_tail_fwd_kernel; kpart: per block 3 K counters (per class tp, pred, gt).  CNT: tp and pred are counted here;
+// without it this kernel fills only the gt column and tail_lab_counts_kernel, on the same grid, the two others (the 8- and
+// 16-slot kernels run two wavefronts per SIMD and pay for every instruction: see kTailLabFusedCountMaxKT).
+template <int KT, int V, bool CNT>
+__global__ __launch_bounds__(kTailThreads) void loss_tail_fwd_lab_kernel(const float* __restrict__ x, const uint8_t* __restrict__ lab,
+        long long N, int Krt, long long S, int vmode, float gamma, int64_t* __restrict__ mask,
+        double* __restrict__ part, long long* __restrict__ cpart, long long* __restrict__ kpart) {
+    const int K = KT <= 4 ? KT : Krt;
+    double vacc = 0.0;
+    double sacc[KT][3];                          // sum p t, sum p, sum p^2
+    unsigned kacc[KT][3];                        // tp, pred, gt (tp and pred stay 0 without CNT)
+#pragma unroll
+    for (int k = 0; k < KT; ++k)
+#pragma unroll
+        for (int j = 0; j < 3; ++j) { sacc[k][j] = 0.0; kacc[k][j] = 0u; }
+    long long cacc[4] = {0, 0, 0, 0};
+    const long long groups = N * S / V;
+    for (long long g = (long long)blockIdx.x * blockDim.x + threadIdx.x; g < groups; g += (long long)gridDim.x * blockDim.x) {
+        const long long v0 = g * V, n = v0 / S, s = v0 - n * S;
+        const float* px = x + n * K * S + s;
+        float xv[KT][V];
+        int lb[V];
+#pragma unroll
+        for (int k = 0; k < KT; ++k)
+            if (k < K) { tail_load<V>(px, xv[k]); px += S; }
+        tail_load_lab<V>(lab + v0, lb);
+        long long mk[V];
+#pragma unroll
+        for (int j = 0; j < V; ++j) {
+            const int lj = lb[j], it = lj < K ? lj : 0;
+            float bx = xv[0][j];
+            int ix = 0;
+            float l = 0.f;
+#pragma unroll
+            for (int k = 0; k < KT; ++k)
+                if (k < K) {
+                    const float a = xv[k][j], b = tail_opaque(lj == k ? 1.f : 0.f);
+                    if (k > 0 && nan_first_gt(a, bx)) { bx = a; ix = k; }
+                    const float p = sigmoid(a);
+                    sacc[k][0] += (double)(p * b); sacc[k][1] += (double)p; sacc[k][2] += (double)(p * p);
+                    kacc[k][2] += (lj == k);
+                    if (vmode == TAIL_V_BCE) {
+                        l += bce_term(a, b);
+                    } else if (vmode == TAIL_V_FOCAL) {
+                        const float q = p + b - 2.f * p * b;
+                        l += tail_pow(q, gamma) * bce_term(a, b);
+                    }
+                }
+            if (vmode == TAIL_V_CE) {
+                float m = -INFINITY, xl = xv[0][j];
+#pragma unroll
+                for (int k = 0; k < KT; ++k)
+                    if (k < K) { m = fmaxf(m, xv[k][j]); if (k == it) xl = xv[k][j]; }
+                float sum = 0.f;
+#pragma unroll
+                for (int k = 0; k < KT; ++k)
+                    if (k < K) sum += expf(xv[k][j] - m);
+                l = logf(sum) - (xl - m);
+            }
+            vacc += (double)l;
+            mk[j] = ix;
+            if constexpr (CNT) {
+#pragma unroll
+                for (int k = 0; k < KT; ++k)
+                    if (k < K) { kacc[k][1] += (ix == k); kacc[k][0] += (ix == k && lj == k); }
+            }
+            cacc[0] += it; cacc[1] += ix;
+            cacc[2] += ((it & ix) != 0); cacc[3] += ((it | ix) != 0);
+        }
+#pragma unroll
+        for (int j = 0; j < V; ++j) mask[v0 + j] = mk[j];
+    }
+    const int R = 1 + 5 * K;
+    double* prow = part + (long long)blockIdx.x * R;
+    long long* krow = kpart + (long long)blockIdx.x * 3 * K;
+    double s = block_reduce_one<OpSum, true>(vacc);
+    if (threadIdx.x == 0) prow[0] = s;
+#pragma unroll
+    for (int k = 0; k < KT; ++k)
+        if (k < K) {
+#pragma unroll
+            for (int j = 0; j < 3; ++j) {
+                s = block_reduce_one<OpSum, true>(sacc[k][j]);
+                if (threadIdx.x == 0) prow[1 + 5 * k + (j == 2 ? 3 : j)] = s;
+            }
+#pragma unroll
+            for (int j = CNT ? 0 : 2; j < 3; ++j) {
+                const long long c = block_reduce_one<OpSum, true>((long long)kacc[k][j]);
+                if (threadIdx.x == 0) {
+                    krow[3 * k + j] = c;
+                    if (j == 2) { prow[1 + 5 * k + 2] = (double)c; prow[1 + 5 * k + 4] = (double)c; }      // sum t = sum t^2 = gt_k
+                }
+            }
+        }
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const long long c = block_reduce_one<OpSum, true>(cacc[j]);
+        if (threadIdx.x == 0) cpart[(long long)blockIdx.x * 4 + j] = c;
+    }
+}
+
+// the tp and pred columns of kpart from the labels and the mask the forward wrote, for the forward kernels without CNT: the same
+// grid (block b fills row b, a block without voxels zeros)
+template <int KT>
+__global__ __launch_bounds__(kTailThreads) void tail_lab_counts_kernel(const uint8_t* __restrict__ lab, const int64_t* __restrict__ mask,
+                                                                       long long n, int K, long long* __restrict__ kpart) {
+    unsigned acc[KT][2];
+#pragma unroll
+    for (int k = 0; k < KT; ++k) { acc[k][0] = 0u; acc[k][1] = 0u; }
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
+        const int lj = lab[i], ix = (int)mask[i];
+#pragma unroll
+        for (int k = 0; k < KT; ++k)
+            if (k < K) { acc[k][1] += (ix == k); acc[k][0] += (ix == k && lj == k); }
+    }
+    long long* krow = kpart + (long long)blockIdx.x * 3 * K;
+#pragma unroll
+    for (int k = 0; k < KT; ++k)
+        if (k < K) {
+#pragma unroll
+            for (int j = 0; j < 2; ++j) {
+                const long long c = block_reduce_one<OpSum, true>((long long)acc[k][j]);
+                if (threadIdx.x == 0) krow[3 * k + j] = c;
+            }
+        }
+}
+
+__global__ __launch_bounds__(kTailFinThreads) void loss_tail_finalize_lab_kernel(const double* __restrict__ part, const long long* __restrict__ cpart,
+        const long long* __restrict__ kpart, int nblk, int K, int vmode, int rmode, double alpha, double beta, double wv, double wr,
+        double M, double Vox, float* __restrict__ loss, double* __restrict__ terms, double* __restrict__ sums,
+        int64_t* __restrict__ counts, double* __restrict__ coef, int64_t* __restrict__ class_counts) {
+    tail_finalize<true>(part, cpart, kpart, nblk, K, vmode, rmode, alpha, beta, wv, wr, M, Vox, loss, terms, sums, counts, coef, class_counts);
+}
+
+// loss_tail_bwd_kernel with b = (label == k) and the ce label = the label itself (0 for a label >= K)
+template <int KT, int V>
+__global__ __launch_bounds__(kTailThreads) void loss_tail_bwd_lab_kernel(const float* __restrict__ x, const uint8_t* __restrict__ lab,
+        const double* __restrict__ coef, const float* __restrict__ gscale, long long N, int Krt, long long S,
+        int vmode, int rmode, float gamma, float* __restrict__ dx) {
+    const int K = KT <= 4 ? KT : Krt;
+    const double gs = (double)gscale[0];
+    const float gw = gscale[0] * (float)coef[0];
+    const float sv = vmode == TAIL_V_CE ? gw * (1.f / (float)(N * S)) : gw / (float)(N * K * S);
+    float cI[KT], cP[KT];
+#pragma unroll
+    for (int k = 0; k < KT; ++k) {
+        cI[k] = 0.f; cP[k] = 0.f;
+        if (k < K) { cI[k] = (float)(gs * coef[1 + 2 * k]); cP[k] = (float)(gs * coef[2 + 2 * k]); }
+    }
+    const long long groups = N * S / V;
+    for (long long g = (long long)blockIdx.x * blockDim.x + threadIdx.x; g < groups; g += (long long)gridDim.x * blockDim.x) {
+        const long long v0 = g * V, n = v0 / S, s = v0 - n * S, base = n * K * S + s;
+        const float* px = x + base;
+        float* pd = dx + base;
+        float xv[KT][V];
+        int lb[V];
+#pragma unroll
+        for (int k = 0; k < KT; ++k)
+            if (k < K) { tail_load<V>(px, xv[k]); px += S; }
+        tail_load_lab<V>(lab + v0, lb);
+        float m[V], inv[V];
+        int it[V];
+        if (vmode == TAIL_V_CE) {
+#pragma unroll
+            for (int j = 0; j < V; ++j) {
+                float mm = -INFINITY;
+#pragma unroll
+                for (int k = 0; k < KT; ++k)
+                    if (k < K) mm = fmaxf(mm, xv[k][j]);
+                float sum = 0.f;
+#pragma unroll
+                for (int k = 0; k < KT; ++k)
+                    if (k < K) sum += expf(xv[k][j] - mm);
+                m[j] = mm; inv[j] = 1.f / sum; it[j] = lb[j] < K ? lb[j] : 0;
+            }
+        }
+#pragma unroll
+        for (int k = 0; k < KT; ++k)
+            if (k < K) {
+                float o[V];
+#pragma unroll
+                for (int j = 0; j < V; ++j) {
+                    const float a = xv[k][j], b = tail_opaque(lb[j] == k ? 1.f : 0.f);
+                    const float p = sigmoid(a), dp = p * (1.f - p);
+                    float d = 0.f;
+                    if (vmode == TAIL_V_BCE) {
+                        d = (p - b) * sv;
+                    } else if (vmode == TAIL_V_FOCAL) {
+                        const float q = p + b - 2.f * p * b;
+                        d = (gamma * tail_pow_m1(q, gamma) * (1.f - 2.f * b) * dp * bce_term(a, b) + tail_pow(q, gamma) * (p - b)) * sv;
+                    } else if (vmode == TAIL_V_CE) {
+                        d = sv * (expf(a - m[j]) * inv[j] - (k == it[j] ? 1.f : 0.f));
+                    }
+                    if (rmode != TAIL_R_NONE) {
+                        const float dr = (cI[k] * b + cP[k]) * dp;
+                        d = vmode == TAIL_V_NONE ? dr : tail_add_rounded(dr, d);
+                    }
+                    o[j] = d;
+                }
+                if constexpr (V == 4) *reinterpret_cast<float4*>(pd) = make_float4(o[0], o[1], o[2], o[3]);
+                else pd[0] = o[0];
+                pd += S;
+            }
+    }
+}
+
+// up to this capacity the forward counts tp and pred itself; above it tail_lab_counts_kernel does, in a launch of its own
+// (measured, DESIGN.md 4.22: inside the 16-slot kernel the two counters cost more than the two fp64 accumulators the label form drops)
+#ifndef TAIL_LAB_FUSED_COUNT_MAX_KT
+#define TAIL_LAB_FUSED_COUNT_MAX_KT 4
+#endif
+constexpr int kTailLabFusedCountMaxKT = TAIL_LAB_FUSED_COUNT_MAX_KT;
+
+template <int V>
+static void tail_launch_fwd_lab(int KT, int nblk, hipStream_t st, const float* x, const uint8_t* lab, long long N, int K, long long S,
+                                int vmode, float gamma, int64_t* mask, double* part, long long* cpart, long long* kpart) {
+#define TAIL_FWD(kt) hipLaunchKernelGGL((loss_tail_fwd_lab_kernel<kt, V, (kt <= kTailLabFusedCountMaxKT)>), dim3(nblk), dim3(kTailThreads), 0, st, x, lab, N, K, S, vmode, gamma, mask, part, cpart, kpart)
+    switch (KT) {
+        case 1: TAIL_FWD(1); break;
+        case 2: TAIL_FWD(2); break;
+        case 3: TAIL_FWD(3); break;
+        case 4: TAIL_FWD(4); break;
+        default:
+            if constexpr (V == 1) {                       // (as the one-hot form: one voxel per thread above four classes)
+                if (KT == 8) TAIL_FWD(8); else TAIL_FWD(16);
+            }
+            break;
+    }
+#undef TAIL_FWD
+}
+template <int V>
+static void tail_launch_bwd_lab(int KT, int nblk, hipStream_t st, const float* x, const uint8_t* lab, const double* coef, const float* gscale,
+                                long long N, int K, long long S, int vmode, int rmode, float gamma, float* dx) {
+#define TAIL_BWD(kt) hipLaunchKernelGGL((loss_tail_bwd_lab_kernel<kt, V>), dim3(nblk), dim3(kTailThreads), 0, st, x, lab, coef, gscale, N, K, S, vmode, rmode, gamma, dx)
+    switch (KT) {
+        case 1: TAIL_BWD(1); break;
+        case 2: TAIL_BWD(2); break;
+        case 3: TAIL_BWD(3); break;
+        case 4: TAIL_BWD(4); break;
+        default:
+            if constexpr (V == 1) {
+                if (KT == 8) TAIL_BWD(8); else TAIL_BWD(16);
+            }
+            break;
+    }
+#undef TAIL_BWD
+}
+
+// float label map -> uint8 labels; a value that is no integer in [0, K) is stored as 255 and counted.  The counter is touched only
+// by a block that met such a value (one 64-bit integer add per block: the sum does not depend on the order).
+template <int V>
+__global__ __launch_bounds__(kTailThreads) void labels_u8_kernel(const float* __restrict__ gt, long long n, int K, uint8_t* __restrict__ out,
+                                                                 unsigned long long* __restrict__ bad) {
+    long long nb = 0;
+    const float fk = (float)K;
+    for (long long g = (long long)blockIdx.x * blockDim.x + threadIdx.x; g < n / V; g += (long long)gridDim.x * blockDim.x) {
+        float v[V];
+        tail_load<V>(gt + g * V, v);
+        unsigned w = 0;
+#pragma unroll
+        for (int j = 0; j < V; ++j) {
+            const bool ok = v[j] >= 0.f && v[j] < fk && v[j] == truncf(v[j]);       // (a NaN fails the first comparison)
+            nb += !ok;
+            w |= (ok ? (unsigned)(int)v[j] : 255u) << (8 * j);
+        }
+        if constexpr (V == 4) *reinterpret_cast<uint32_t*>(out + g * 4) = w;
+        else out[g] = (uint8_t)w;
+    }
+    const long long c = block_reduce_one<OpSum>(nb);
+    if (threadIdx.x == 0 && c != 0) atomicAdd(bad, (unsigned long long)c);
+}
+
+// out[n][k][s] = (labels[n][s] == k), float
+template <int V>
+__global__ __launch_bounds__(kTailThreads) void onehot_u8_kernel(const uint8_t* __restrict__ lab, long long N, int K, long long S,
+                                                                 float* __restrict__ out) {
+    const long long groups = N * S / V;
+    for (long long g = (long long)blockIdx.x * blockDim.x + threadIdx.x; g < groups; g += (long long)gridDim.x * blockDim.x) {
+        const long long v0 = g * V, n = v0 / S, s = v0 - n * S;
+        int lb[V];
+        tail_load_lab<V>(lab + v0, lb);
+        float* po = out + n * K * S + s;
+        for (int k = 0; k < K; ++k, po += S) {
+            if constexpr (V == 4) *reinterpret_cast<float4*>(po) = make_float4(lb[0] == k ? 1.f : 0.f, lb[1] == k ? 1.f : 0.f, lb[2] == k ? 1.f : 0.f, lb[3] == k ? 1.f : 0.f);
+            else po[0] = lb[0] == k ? 1.f : 0.f;
+        }
+    }
+}
+
+// per class tp, pred, gt of two int64 label volumes; part [3 K][nblk] (one row per counter: the rows of sums_finalize_kernel)
+template <int KT>
+__global__ __launch_bounds__(kTailThreads) void class_counts_kernel(const int64_t* __restrict__ gt, const int64_t* __restrict__ pred,
+                                                                    long long n, int K, long long* __restrict__ part) {
+    unsigned acc[KT][3];
+#pragma unroll
+    for (int k = 0; k < KT; ++k) { acc[k][0] = 0u; acc[k][1] = 0u; acc[k][2] = 0u; }
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
+        const long long g = gt[i], p = pred[i];
+#pragma unroll
+        for (int k = 0; k < KT; ++k)
+            if (k < K) { acc[k][0] += (g == k && p == k); acc[k][1] += (p == k); acc[k][2] += (g == k); }
+    }
+#pragma unroll
+    for (int k = 0; k < KT; ++k)
+        if (k < K) {
+#pragma unroll
+            for (int j = 0; j < 3; ++j) {
+                const long long c = block_reduce_one<OpSum, true>((long long)acc[k][j]);
+                if (threadIdx.x == 0) part[(long long)(3 * k + j) * gridDim.x + blockIdx.x] = c;
+            }
+        }
+}
+
 }  // namespace seg
 
 using namespace seg;
@@ -386,6 +750,124 @@ int mi355seg_loss_tail_bwd_f32(const float* logits, const float* target, const d
     const int nblk = tail_grid(vec ? N * S / 4 : N * S);
     if (vec) tail_launch_bwd<4>(KT, nblk, st, logits, target, coef, gscale, N, K, S, voxel_term, region_term, gamma, dlogits);
     else tail_launch_bwd<1>(KT, nblk, st, logits, target, coef, gscale, N, K, S, voxel_term, region_term, gamma, dlogits);
+    SEG_CHECK_LAUNCH();
+    return MI355SEG_OK;
+}
+
+int mi355seg_labels_u8_f32(const float* gt, long long n, int K, uint8_t* labels_u8, int64_t* bad, void* stream) {
+    SEG_CHECK_ARG(K >= 1 && K <= kTailMaxClasses, "labels_u8: K must be in 1..%d, got %d", kTailMaxClasses, K);
+    SEG_CHECK_ARG(n > 0, "labels_u8: bad extent n=%lld", n);
+    SEG_CHECK_ARG(gt && labels_u8 && bad, "labels_u8: null pointer");
+    SEG_CHECK_ARG(((uintptr_t)bad % 8) == 0, "labels_u8: the counter must be 8-byte aligned");
+    hipStream_t st = (hipStream_t)stream;
+    ProfScope ps(PF_LOSS, 0.0, 5.0 * n, st);
+    const bool vec = n % 4 == 0 && tail_aligned16(gt) && ((uintptr_t)labels_u8 % 4) == 0;
+    if (vec) hipLaunchKernelGGL(labels_u8_kernel<4>, dim3(tail_grid(n / 4)), dim3(kTailThreads), 0, st, gt, n, K, labels_u8, (unsigned long long*)bad);
+    else hipLaunchKernelGGL(labels_u8_kernel<1>, dim3(tail_grid(n)), dim3(kTailThreads), 0, st, gt, n, K, labels_u8, (unsigned long long*)bad);
+    SEG_CHECK_LAUNCH();
+    return MI355SEG_OK;
+}
+
+int mi355seg_onehot_u8_f32(const uint8_t* labels_u8, long long N, int K, long long S, float* out, void* stream) {
+    SEG_CHECK_ARG(K >= 1 && K <= kTailMaxClasses, "onehot_u8: K must be in 1..%d, got %d", kTailMaxClasses, K);
+    SEG_CHECK_ARG(N > 0 && S > 0, "onehot_u8: bad extents N=%lld S=%lld", N, S);
+    SEG_CHECK_ARG(labels_u8 && out, "onehot_u8: null pointer");
+    hipStream_t st = (hipStream_t)stream;
+    ProfScope ps(PF_LOSS, 0.0, (4.0 * K + 1.0) * N * S, st);
+    const bool vec = S % 4 == 0 && tail_aligned16(out) && ((uintptr_t)labels_u8 % 4) == 0;
+    if (vec) hipLaunchKernelGGL(onehot_u8_kernel<4>, dim3(tail_grid(N * S / 4)), dim3(kTailThreads), 0, st, labels_u8, N, K, S, out);
+    else hipLaunchKernelGGL(onehot_u8_kernel<1>, dim3(tail_grid(N * S)), dim3(kTailThreads), 0, st, labels_u8, N, K, S, out);
+    SEG_CHECK_LAUNCH();
+    return MI355SEG_OK;
+}
+
+size_t mi355seg_loss_tail_lab_ws_bytes(long long N, int K, long long S) {
+    if (N < 1 || S < 1 || K < 1 || K > kTailMaxClasses) return 0;
+    return (size_t)tail_grid(N * S) * ((size_t)(1 + 5 * K) * sizeof(double) + (size_t)(4 + 3 * K) * sizeof(long long));
+}
+
+// the label form takes the path (16-byte or scalar) the one-hot form takes at the same S, or the bits would differ: where S % 4 == 0
+// and K <= 4 a misaligned pointer is refused, not served by the other path
+#define TAIL_LAB_CHECK_ALIGN(what, cond) \
+    SEG_CHECK_ARG(!(tail_capacity(K) <= 4 && S % 4 == 0) || (cond), what ": with S %% 4 == 0 and K <= 4 the float pointers must be 16-byte and labels 4-byte aligned")
+
+int mi355seg_loss_tail_fwd_lab_f32(const float* logits, const uint8_t* labels, long long N, int K, long long S,
+                                   int voxel_term, int region_term, float gamma, float alpha, float beta, float w_voxel, float w_region,
+                                   float* loss, double* terms, double* sums, int64_t* mask, int64_t* counts, double* coef,
+                                   int64_t* class_counts, void* ws, size_t ws_bytes, void* stream) {
+    TAIL_CHECK_SPEC("loss_tail_fwd_lab");
+    SEG_CHECK_ARG(alpha >= 0.f && beta >= 0.f, "loss_tail_fwd_lab: alpha and beta must be >= 0, got %g, %g", (double)alpha, (double)beta);
+    SEG_CHECK_ARG(region_term != TAIL_R_TVERSKY || alpha + beta > 0.f, "loss_tail_fwd_lab: tversky needs alpha + beta > 0");
+    SEG_CHECK_ARG(w_voxel >= 0.f && w_region >= 0.f, "loss_tail_fwd_lab: the weights must be >= 0, got %g, %g", (double)w_voxel, (double)w_region);
+    SEG_CHECK_ARG(logits && labels && loss && terms && sums && mask && counts && coef && class_counts && ws, "loss_tail_fwd_lab: null pointer");
+    SEG_CHECK_ARG(((uintptr_t)ws % 8) == 0, "loss_tail_fwd_lab: the workspace must be 8-byte aligned");
+    SEG_CHECK_WS(mi355seg_loss_tail_lab_ws_bytes(N, K, S), ws_bytes);
+    TAIL_LAB_CHECK_ALIGN("loss_tail_fwd_lab", tail_aligned16(logits) && ((uintptr_t)labels % 4) == 0);
+    hipStream_t st = (hipStream_t)stream;
+    ProfScope ps(PF_LOSS, 0.0, (4.0 * K + 9.0) * N * S, st);
+    if (voxel_term == TAIL_V_FOCAL && gamma == 0.f) voxel_term = TAIL_V_BCE;
+    const int KT = tail_capacity(K);
+    const bool vec = KT <= 4 && S % 4 == 0;
+    const int nblk = tail_grid(vec ? N * S / 4 : N * S);
+    double* part = (double*)ws;
+    long long* cpart = (long long*)(part + (size_t)nblk * (1 + 5 * K));
+    long long* kpart = cpart + (size_t)nblk * 4;
+    if (vec) tail_launch_fwd_lab<4>(KT, nblk, st, logits, labels, N, K, S, voxel_term, gamma, mask, part, cpart, kpart);
+    else tail_launch_fwd_lab<1>(KT, nblk, st, logits, labels, N, K, S, voxel_term, gamma, mask, part, cpart, kpart);
+    SEG_CHECK_LAUNCH();
+    if (KT > kTailLabFusedCountMaxKT) {
+        if (KT <= 4) hipLaunchKernelGGL(tail_lab_counts_kernel<4>, dim3(nblk), dim3(kTailThreads), 0, st, labels, (const int64_t*)mask, N * S, K, kpart);
+        else if (KT == 8) hipLaunchKernelGGL(tail_lab_counts_kernel<8>, dim3(nblk), dim3(kTailThreads), 0, st, labels, (const int64_t*)mask, N * S, K, kpart);
+        else hipLaunchKernelGGL(tail_lab_counts_kernel<16>, dim3(nblk), dim3(kTailThreads), 0, st, labels, (const int64_t*)mask, N * S, K, kpart);
+        SEG_CHECK_LAUNCH();
+    }
+    hipLaunchKernelGGL(loss_tail_finalize_lab_kernel, dim3(1), dim3(kTailFinThreads), 0, st, (const double*)part, (const long long*)cpart,
+                       (const long long*)kpart, nblk, K, voxel_term, region_term, (double)alpha, (double)beta,
+                       voxel_term == TAIL_V_NONE ? 0.0 : (double)w_voxel, region_term == TAIL_R_NONE ? 0.0 : (double)w_region,
+                       (double)N * K * S, (double)N * S, loss, terms, sums, counts, coef, class_counts);
+    SEG_CHECK_LAUNCH();
+    return MI355SEG_OK;
+}
+
+int mi355seg_loss_tail_bwd_lab_f32(const float* logits, const uint8_t* labels, const double* coef, const float* gscale,
+                                   long long N, int K, long long S, int voxel_term, int region_term, float gamma,
+                                   float* dlogits, void* stream) {
+    TAIL_CHECK_SPEC("loss_tail_bwd_lab");
+    SEG_CHECK_ARG(logits && labels && coef && gscale && dlogits, "loss_tail_bwd_lab: null pointer");
+    TAIL_LAB_CHECK_ALIGN("loss_tail_bwd_lab", tail_aligned16(logits) && tail_aligned16(dlogits) && ((uintptr_t)labels % 4) == 0);
+    hipStream_t st = (hipStream_t)stream;
+    ProfScope ps(PF_LOSS, 0.0, (8.0 * K + 1.0) * N * S, st);
+    if (voxel_term == TAIL_V_FOCAL && gamma == 0.f) voxel_term = TAIL_V_BCE;
+    const int KT = tail_capacity(K);
+    const bool vec = KT <= 4 && S % 4 == 0;
+    const int nblk = tail_grid(vec ? N * S / 4 : N * S);
+    if (vec) tail_launch_bwd_lab<4>(KT, nblk, st, logits, labels, coef, gscale, N, K, S, voxel_term, region_term, gamma, dlogits);
+    else tail_launch_bwd_lab<1>(KT, nblk, st, logits, labels, coef, gscale, N, K, S, voxel_term, region_term, gamma, dlogits);
+    SEG_CHECK_LAUNCH();
+    return MI355SEG_OK;
+}
+
+size_t mi355seg_class_counts_ws_bytes(long long n, int K) {
+    if (n < 1 || K < 1 || K > kTailMaxClasses) return 0;
+    return (size_t)tail_grid(n) * (size_t)(3 * K) * sizeof(long long);
+}
+
+int mi355seg_class_counts_i64(const int64_t* gt_labels, const int64_t* pred_labels, long long n, int K, int64_t* out,
+                              void* ws, size_t ws_bytes, void* stream) {
+    SEG_CHECK_ARG(K >= 1 && K <= kTailMaxClasses, "class_counts: K must be in 1..%d, got %d", kTailMaxClasses, K);
+    SEG_CHECK_ARG(n > 0, "class_counts: bad extent n=%lld", n);
+    SEG_CHECK_ARG(gt_labels && pred_labels && out && ws, "class_counts: null pointer");
+    SEG_CHECK_ARG(((uintptr_t)ws % 8) == 0, "class_counts: the workspace must be 8-byte aligned");
+    SEG_CHECK_WS(mi355seg_class_counts_ws_bytes(n, K), ws_bytes);
+    hipStream_t st = (hipStream_t)stream;
+    ProfScope ps(PF_LOSS, 0.0, 16.0 * n, st);
+    const int nblk = tail_grid(n);
+    long long* part = (long long*)ws;
+    if (K <= 4) hipLaunchKernelGGL(class_counts_kernel<4>, dim3(nblk), dim3(kTailThreads), 0, st, gt_labels, pred_labels, n, K, part);
+    else if (K <= 8) hipLaunchKernelGGL(class_counts_kernel<8>, dim3(nblk), dim3(kTailThreads), 0, st, gt_labels, pred_labels, n, K, part);
+    else hipLaunchKernelGGL(class_counts_kernel<16>, dim3(nblk), dim3(kTailThreads), 0, st, gt_labels, pred_labels, n, K, part);
+    SEG_CHECK_LAUNCH();
+    launch_sums_finalize<1>((const long long*)part, nblk, (long long*)out, st, (unsigned)(3 * K));
     SEG_CHECK_LAUNCH();
     return MI355SEG_OK;
 }

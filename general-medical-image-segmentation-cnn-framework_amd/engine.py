@@ -7,7 +7,7 @@ reference's two full int64 volumes, train.py:221).  Optimizer stays torch.optim 
 import torch
 
 from . import functional as F
-from .utils.metric import metric_from_counts
+from .utils.metric import class_metrics_from_counts, metric_from_counts
 
 
 def two_channel_gt(gt):
@@ -54,17 +54,42 @@ def _forward(model, leaves, *args):
     return torch.func.functional_call(model, leaves, args)
 
 
-def train_step(model, optimizer, x, gt, criterion=None, sync_metric=True, grad_hook=None, dtype=None, step_optimizer=True, _leaves=None):
+def _sync_metrics(out, multiclass):
+    """The step's python floats from its device counters (one tiny D2H copy)."""
+    if multiclass:
+        m = class_metrics_from_counts(out["class_counts"])
+        out["class_dice"] = m["dice"]
+        out["dice"] = m["mean_dice"]
+        out["jaccard"] = m["mean_jaccard"]
+    else:
+        out["jaccard"], out["dice"] = metric_from_counts(out["counts"].cpu().tolist())
+
+
+def train_step(model, optimizer, x, gt, criterion=None, sync_metric=True, grad_hook=None, dtype=None, step_optimizer=True, _leaves=None,
+               multiclass=None, label_bad=None):
     """One iteration.  ``gt`` is the single-channel label volume [N,1,D,H,W].  ``dtype`` = torch.bfloat16 runs the
     forward under mi355seg.autocast (bf16 activations; the loss and everything after it stay fp32).
     ``grad_hook`` (if given) runs between backward and optimizer.step -- the data-parallel
     gradient all-reduce plugs in there.  A ``criterion`` with a ``tail`` method (CompoundLoss) runs its fused tail and adds
     'loss_terms' to the result.  Returns a dict with pred, mask, loss and, when
     ``sync_metric``, python floats jaccard/dice (one tiny D2H copy); otherwise the raw
-    int64[4] counters stay on the device under 'counts'."""
+    int64[4] counters stay on the device under 'counts'.
+    ``multiclass`` = K (2..16; config.multiclass) takes the label path: ``gt`` holds the labels 0..K-1, one launch turns it into
+    uint8 labels in place of the two-channel target, and ``criterion.tail_labels`` (CompoundLoss) runs the fused tail on them.  The
+    result gains 'class_counts' (int64 [K,3] on the device: per class tp, pred, gt) and 'label_bad', the int64[1] device counter
+    to which the number of voxels that are no integer in [0, K) was added (``label_bad`` if given: the step state's counter; the
+    step never reads it); 'dice' / 'jaccard' are then the means over the foreground classes that occur
+    (utils.metric.class_metrics_from_counts) and 'class_dice' the per-class list."""
     optimizer.zero_grad(set_to_none=True)
-    loss_terms = None
-    gt2 = two_channel_gt(gt)
+    loss_terms = class_counts = None
+    if multiclass is None:
+        gt2 = two_channel_gt(gt)
+    else:
+        if isinstance(multiclass, bool) or not isinstance(multiclass, int) or not 2 <= multiclass <= F.MAX_LOSS_CLASSES:
+            raise ValueError(f"train_step: multiclass must be the number of classes, an integer in 2..{F.MAX_LOSS_CLASSES}, got {multiclass!r}")
+        if not hasattr(criterion, "tail_labels"):
+            raise ValueError("train_step: multiclass needs a criterion with a tail_labels method (utils.loss_function.CompoundLoss; config.loss)")
+        labels, label_bad = F.labels_u8(gt, multiclass, label_bad)
     x = x.to(torch.float32)
     # every training-mode BatchNorm counter advanced by one multi-tensor launch AFTER the forward (the modules tally their calls
     # meanwhile): the forward's first access to a module buffer is then its first norm layer, which is where a buffer broadcast
@@ -89,7 +114,11 @@ def train_step(model, optimizer, x, gt, criterion=None, sync_metric=True, grad_h
         F.flush_deferred_waits()                                     # (a model without norm layers)
         if bns:
             torch._foreach_add_([m.num_batches_tracked for m in bns], 1)
-        if criterion is None:
+        if multiclass is not None:
+            if pred.shape[1] != multiclass:
+                raise ValueError(f"train_step: multiclass={multiclass} but the model has {pred.shape[1]} output channels")
+            loss, mask, counts, loss_terms, class_counts = criterion.tail_labels(pred, labels)
+        elif criterion is None:
             # nn.BCEWithLogitsLoss + pred.argmax + gt.argmax + the Dice counters in one pass over the logits
             loss, mask, counts = F.bce_argmax_dice(pred, gt2)
         elif hasattr(criterion, "tail"):
@@ -112,8 +141,10 @@ def train_step(model, optimizer, x, gt, criterion=None, sync_metric=True, grad_h
     out = {"pred": pred, "mask": mask, "loss": loss.detach(), "counts": counts}
     if loss_terms is not None:
         out["loss_terms"] = loss_terms           # fp64[2] on the device: voxel term, region term (unweighted)
+    if class_counts is not None:
+        out["class_counts"], out["label_bad"] = class_counts, label_bad
     if sync_metric:
-        out["jaccard"], out["dice"] = metric_from_counts(counts.cpu().tolist())
+        _sync_metrics(out, multiclass)
     return out
 
 
@@ -147,7 +178,7 @@ class GraphedTrainStep:
     copies; whatever ran before the capture, on whatever stream, no longer matters (tests/test_gpu_unet.py::
     test_graphed_step_captures_after_an_eager_step_with_a_live_output)."""
 
-    def __init__(self, model, optimizer, x, gt, criterion=None, warmup=3, dtype=None, grad_hook=None):
+    def __init__(self, model, optimizer, x, gt, criterion=None, warmup=3, dtype=None, grad_hook=None, multiclass=None):
         from ._lib import lib
         if not all(g.get("capturable", False) for g in optimizer.param_groups):
             raise ValueError("GraphedTrainStep: build the optimizer with capturable=True (e.g. torch.optim.Adam(..., capturable=True))")
@@ -155,6 +186,10 @@ class GraphedTrainStep:
         self.model, self.optimizer, self.criterion, self.grad_hook = model, optimizer, criterion, grad_hook
         self.x = x.detach().to(torch.float32).clone()
         self.gt = gt.detach().clone()
+        self.multiclass = multiclass
+        # the label-range counter of the label path: step state, added to by every step (warm-up and replays), read by the caller
+        self.label_bad = torch.zeros(1, dtype=torch.int64, device=self.x.device) if multiclass is not None else None
+        mc = {"multiclass": multiclass, "label_bad": self.label_bad} if multiclass is not None else {}
         if grad_hook is not None and hasattr(grad_hook, "suspend_hooks"):
             grad_hook.suspend_hooks(True)            # from here on every bucket is launched at the reducer's call
         side = torch.cuda.Stream()
@@ -162,10 +197,12 @@ class GraphedTrainStep:
         with torch.cuda.stream(side):
             self.first = None
             for _ in range(warmup):
-                o = train_step(model, optimizer, self.x, self.gt, criterion, sync_metric=False, dtype=dtype, grad_hook=grad_hook)
+                o = train_step(model, optimizer, self.x, self.gt, criterion, sync_metric=False, dtype=dtype, grad_hook=grad_hook, **mc)
                 self.first = {"loss": o["loss"].detach().clone(), "counts": o["counts"].clone()}
                 if "loss_terms" in o:
                     self.first["loss_terms"] = o["loss_terms"].clone()
+                if "class_counts" in o:
+                    self.first["class_counts"] = o["class_counts"].clone()
                 del o
         torch.cuda.current_stream().wait_stream(side)
         torch.cuda.synchronize()
@@ -175,10 +212,10 @@ class GraphedTrainStep:
         leaves = {name: p.detach().requires_grad_(p.requires_grad) for name, p in model.named_parameters()}
         if grad_hook is None:
             with torch.cuda.graph(self.graph):
-                self.out = train_step(model, optimizer, self.x, self.gt, criterion, sync_metric=False, dtype=dtype, _leaves=leaves)
+                self.out = train_step(model, optimizer, self.x, self.gt, criterion, sync_metric=False, dtype=dtype, _leaves=leaves, **mc)
         else:
             with torch.cuda.graph(self.graph):
-                self.out = train_step(model, optimizer, self.x, self.gt, criterion, sync_metric=False, dtype=dtype, step_optimizer=False, _leaves=leaves)
+                self.out = train_step(model, optimizer, self.x, self.gt, criterion, sync_metric=False, dtype=dtype, step_optimizer=False, _leaves=leaves, **mc)
             # a parameter the backward does not reach has no static gradient tensor: the reducer would allocate one at its first call
             # (and the optimizer graph must already see it), so give it zeros now -- no collective here: the captured backward has
             # not executed, the static gradients hold nothing yet
@@ -205,7 +242,7 @@ class GraphedTrainStep:
             self.opt_graph.replay()
         out = dict(self.out)
         if sync_metric:
-            out["jaccard"], out["dice"] = metric_from_counts(out["counts"].cpu().tolist())
+            _sync_metrics(out, self.multiclass)
         return out
 
 

@@ -2217,6 +2217,130 @@ def loss_tail(logits, target, spec):
     return loss_tail_full(logits, target, spec)[:4]
 
 
+# ----------------------------------------------------------------------------- label-map targets (config.multiclass)
+LABEL_OUT_OF_RANGE = 255            # what labels_u8 stores for a value that is no integer in [0, K)
+
+
+def _require_device(t, what):
+    if not t.is_cuda:
+        raise Mi355SegError(f"{what}: expected a tensor on an MI355X (cuda/HIP) device, got {t.device}; there is no CPU fallback in this package")
+
+
+def _checked_classes(K, what):
+    if isinstance(K, bool) or not isinstance(K, int) or not 1 <= K <= MAX_LOSS_CLASSES:
+        raise ValueError(f"{what}: K must be an integer in 1..{MAX_LOSS_CLASSES}, got {K!r}")
+    return K
+
+
+def labels_u8(gt, K, bad=None):
+    """The float label map ``gt`` [N,1,...] as uint8 labels [N,...] in one launch.  A value that is not an integer in [0, K) is
+    stored as 255 and counted: the count is ADDED to ``bad`` (int64[1] on the device; a fresh zeroed one when None).  Returns
+    (labels, bad); nothing is read back."""
+    _require_device(gt, "labels_u8 input")
+    _checked_classes(K, "labels_u8")
+    gt = aligned_contiguous(gt.to(torch.float32))
+    if gt.dim() < 3 or gt.shape[1] != 1:
+        raise Mi355SegError(f"labels_u8: expected [N,1,...], got {tuple(gt.shape)}")
+    if bad is None:
+        bad = torch.zeros(1, dtype=torch.int64, device=gt.device)
+    elif bad.dtype != torch.int64 or bad.numel() != 1 or bad.device != gt.device:
+        raise Mi355SegError("labels_u8: bad must be an int64[1] tensor on the input's device")
+    out = torch.empty((gt.shape[0],) + tuple(gt.shape[2:]), dtype=torch.uint8, device=gt.device)
+    lib().call("mi355seg_labels_u8_f32", _p(gt), gt.numel(), K, _p(out), _p(bad), _stream())
+    return out, bad
+
+
+def _checked_label_map(labels, what):
+    _require_device(labels, f"{what} labels")
+    if labels.dtype != torch.uint8 or labels.dim() < 2:
+        raise Mi355SegError(f"{what}: labels must be uint8 [N,...], got {labels.dtype} {tuple(labels.shape)}")
+    return aligned_contiguous(labels)
+
+
+def one_hot_labels(labels, K):
+    """float32 one-hot [N,K,...] of uint8 labels [N,...]; a label >= K gives an all-zero column."""
+    labels = _checked_label_map(labels, "one_hot_labels")
+    _checked_classes(K, "one_hot_labels")
+    N = labels.shape[0]
+    out = torch.empty((N, K) + tuple(labels.shape[1:]), dtype=torch.float32, device=labels.device)
+    lib().call("mi355seg_onehot_u8_f32", _p(labels), N, K, labels[0].numel(), _p(out), _stream())
+    return out
+
+
+class _LossTailLabels(Function):
+    """_LossTail with uint8 labels [N,...] in place of the one-hot target, plus class_counts int64 [K,3] (tp, pred, gt)."""
+
+    @staticmethod
+    def forward(ctx, logits, labels, spec):
+        _require_cuda(logits, "loss_tail_labels input")
+        logits, labels = aligned_contiguous(logits), _checked_label_map(labels, "loss_tail_labels")
+        if logits.dim() < 3:
+            raise Mi355SegError(f"loss_tail_labels: expected [N,K,...], got {tuple(logits.shape)}")
+        if (logits.shape[0],) + tuple(logits.shape[2:]) != tuple(labels.shape):
+            raise ValueError(f"Label size ({tuple(labels.shape)}) must be the input size ({tuple(logits.shape)}) without its channels")
+        N, K = logits.shape[0], logits.shape[1]
+        S = logits[0, 0].numel()
+        dev = logits.device
+        L = lib()
+        ws = workspace(L.query("mi355seg_loss_tail_lab_ws_bytes", N, K, S), dev)
+        loss = torch.empty((), dtype=torch.float32, device=dev)
+        mask = torch.empty((N, 1) + tuple(logits.shape[2:]), dtype=torch.int64, device=dev)
+        counts = torch.empty(4, dtype=torch.int64, device=dev)
+        terms = torch.empty(2, dtype=torch.float64, device=dev)
+        sums = torch.empty((K, 5), dtype=torch.float64, device=dev)
+        class_counts = torch.empty((K, 3), dtype=torch.int64, device=dev)
+        coef = torch.empty(1 + 2 * MAX_LOSS_CLASSES, dtype=torch.float64, device=dev)
+        args = (LOSS_VOXEL_TERMS[spec.voxel], LOSS_REGION_TERMS[spec.region], spec.gamma)
+        L.call("mi355seg_loss_tail_fwd_lab_f32", _p(logits), _p(labels), N, K, S, *args, spec.alpha, spec.beta, spec.w_voxel, spec.w_region,
+               _p(loss), _p(terms), _p(sums), _p(mask), _p(counts), _p(coef), _p(class_counts), _p(ws), ws.numel(), _stream())
+        ctx.save_for_backward(logits, labels, coef)
+        ctx.args = args
+        ctx.mark_non_differentiable(mask, counts, terms, sums, class_counts)
+        ctx.set_materialize_grads(False)
+        return loss, mask, counts, terms, sums, class_counts
+
+    @staticmethod
+    def backward(ctx, g, _gmask, _gcounts, _gterms, _gsums, _gclass):
+        if g is None:
+            return None, None, None
+        logits, labels, coef = ctx.saved_tensors
+        g = g.contiguous().to(torch.float32)
+        N, K = logits.shape[0], logits.shape[1]
+        d = torch.empty_like(logits)
+        lib().call("mi355seg_loss_tail_bwd_lab_f32", _p(logits), _p(labels), _p(coef), _p(g), N, K, logits[0, 0].numel(), *ctx.args, _p(d), _stream())
+        return d, None, None
+
+
+def loss_tail_labels_full(logits, labels, spec):
+    """loss_tail_labels plus the per-class sums: (loss, mask, counts, terms, sums fp64 [K,5], class_counts int64 [K,3])."""
+    if not isinstance(spec, LossSpec):
+        raise TypeError(f"loss_tail_labels: spec must be a functional.LossSpec, got {type(spec).__name__}")
+    return _LossTailLabels.apply(logits, labels, spec.checked())
+
+
+def loss_tail_labels(logits, labels, spec):
+    """loss_tail on a label map: logits [N,K,...] float32, labels uint8 [N,...] (labels_u8).  Returns (loss, mask, counts, terms,
+    class_counts): the first four with the bits loss_tail gives on one_hot_labels(labels, K), and class_counts int64 [K,3] = per
+    class (tp, pred, gt) for utils.metric.class_metrics_from_counts.  A label >= K belongs to no class."""
+    out = loss_tail_labels_full(logits, labels, spec)
+    return out[:4] + (out[5],)
+
+
+def class_counts(gt, pred, K):
+    """int64 [K,3] = per class (tp, pred, gt) of two int64 label volumes of equal size, on the device."""
+    _require_device(gt, "class_counts gt")
+    _require_device(pred, "class_counts pred")
+    _checked_classes(K, "class_counts")
+    gt, pred = gt.to(torch.int64).contiguous(), pred.to(torch.int64).contiguous()
+    if gt.numel() != pred.numel() or gt.numel() < 1:
+        raise ValueError(f"class_counts: gt {tuple(gt.shape)} and pred {tuple(pred.shape)} must hold the same number of voxels (>= 1)")
+    L = lib()
+    ws = workspace(L.query("mi355seg_class_counts_ws_bytes", gt.numel(), K), gt.device)
+    out = torch.empty((K, 3), dtype=torch.int64, device=gt.device)
+    L.call("mi355seg_class_counts_i64", _p(gt), _p(pred), gt.numel(), K, _p(out), _p(ws), ws.numel(), _stream())
+    return out
+
+
 # ----------------------------------------------------------------------------- soft-clDice (config.cldice_weight; csrc/cldice.hip)
 CLDICE_ITERS, CLDICE_SMOOTH = 3, 1.0
 MAX_SKEL_ITERS = 32

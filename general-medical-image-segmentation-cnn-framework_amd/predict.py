@@ -53,7 +53,7 @@ from .intensity import parse_intensity
 from .resample import parse_resample, parse_spacing_source
 from .registry import build_model
 from .models.three_d.IS import set_band_split
-from .utils.metric import metric_from_counts, metric_with_spacing
+from .utils.metric import class_metrics_from_counts, metric_from_counts, metric_with_spacing
 
 
 def grid_locations(size, patch, overlap):
@@ -414,6 +414,45 @@ def write_metrics_csv(path, rows):
             wr.writerow({"file": "mean", **{k: float(np.mean([r[k] for r in rows])) for k in METRIC_COLUMNS}})
 
 
+def write_class_metrics_csv(path, rows):
+    """config.multiclass: rows of {file, class, jaccard, dice}, one per file and foreground class, in the order given; rows that also
+    hold precision / recall / hs95 (a run with config.spacing) get the reference's five columns in its order.  Last, one ``mean``
+    row per class, ascending: the means of that class's rows."""
+    full = bool(rows) and all(k in rows[0] for k in METRIC_COLUMNS)
+    cols = list(METRIC_COLUMNS) if full else ["jaccard", "dice"]
+    with open(path, "w", newline="") as fh:
+        wr = csv.DictWriter(fh, fieldnames=["file", "class"] + cols)
+        wr.writeheader()
+        wr.writerows(rows)
+        for k in sorted({r["class"] for r in rows}):
+            wr.writerow({"file": "mean", "class": k, **{c: float(np.mean([r[c] for r in rows if r["class"] == k])) for c in cols}})
+
+
+def class_metric_rows(name, gt_lab, mask, K, spacing=None):
+    """The rows of one file for write_class_metrics_csv: the counts of all classes from ONE functional.class_counts launch; with a
+    spacing, hs95 per class from metric_with_spacing on the class masks gt == k and mask == k."""
+    m = class_metrics_from_counts(F.class_counts(gt_lab, mask, K))
+    rows = []
+    for k in range(1, K):
+        row = {"file": name, "class": k, "jaccard": m["jaccard"][k], "dice": m["dice"][k]}
+        if spacing:
+            row["precision"], row["recall"] = m["precision"][k], m["recall"][k]
+            row["hs95"] = metric_with_spacing((gt_lab == k).to(torch.int64), (mask == k).to(torch.int64), spacing)[4]
+        rows.append(row)
+    return rows
+
+
+def parse_predict_multiclass(config):
+    """``config.multiclass`` at predict time -> K = config.out_classes or None (train.parse_multiclass without the loss check).
+    Refused with the component clean-up keys: per-class components are not built."""
+    from .train import parse_multiclass
+    K = parse_multiclass(config, False, data_key="pred_data_path")
+    if K is not None and parse_postprocess(config) is not None:
+        raise ValueError("config.multiclass does not go with config.keep_largest / config.min_component_voxels: the component "
+                         "clean-up works on one foreground class")
+    return K
+
+
 def predict(config, model, log=print):
     device = torch.device("cuda", 0)
     if config.ckpt and str(config.ckpt) != "None":
@@ -428,6 +467,7 @@ def predict(config, model, log=print):
     mode = parse_overlap_mode(config)
     save_prob = parse_save_probabilities(config, mode)
     flips = parse_tta(config)
+    multiclass = parse_predict_multiclass(config)        # config.multiclass: K, or None (everything below as it was)
     if flips:
         log(f"tta: mirror, {len(flips)} flips per patch (codes {','.join(str(f) for f in flips)})")
     os.makedirs(config.hydra_path, exist_ok=True)
@@ -479,6 +519,11 @@ def predict(config, model, log=print):
             log(f"{name}: " + " ".join(f"{k} {stats[k]}" for k in COMPONENT_COLUMNS))
         gt_lab = gt.to(device).to(torch.int64).reshape(mask.shape)
         np.save(os.path.join(config.hydra_path, f"{name}_pred.npy"), mask.cpu().numpy().astype(np.uint8))
+        if multiclass is not None:
+            new = class_metric_rows(name, gt_lab, mask, multiclass, spacing)
+            rows.extend(new)
+            log(f"{name}: " + " ".join(f"dice_{r['class']} {r['dice']:.4f}" for r in new))
+            continue
         if spacing:
             row = dict(zip(METRIC_COLUMNS, metric_with_spacing(gt_lab, mask, spacing)))
             rows.append({"file": name, **row})
@@ -488,7 +533,7 @@ def predict(config, model, log=print):
         jac, dice = metric_from_counts(counts.cpu().tolist())
         rows.append({"file": name, "jaccard": jac, "dice": dice})
         log(f"{name}: dice {dice:.4f} jaccard {jac:.4f}")
-    write_metrics_csv(os.path.join(config.hydra_path, "metrics.csv"), rows)
+    (write_class_metrics_csv if multiclass is not None else write_metrics_csv)(os.path.join(config.hydra_path, "metrics.csv"), rows)
     if post:
         write_components_csv(os.path.join(config.hydra_path, "components.csv"), comp_rows)
     return rows

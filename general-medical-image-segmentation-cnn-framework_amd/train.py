@@ -17,8 +17,7 @@ from . import distributed as D
 from .config import absent as _absent, compose, parse_patch_size
 from .data import make_loader
 from . import functional as F
-from .utils.metric import metric_from_counts
-from .engine import GraphedTrainStep, make_adam, mixed_precision_dtype, train_step, weights_init_normal
+from .engine import GraphedTrainStep, _sync_metrics, make_adam, mixed_precision_dtype, train_step, weights_init_normal
 from .registry import build_model
 from .models.three_d.IS import set_band_split
 
@@ -131,6 +130,30 @@ def parse_loss(config):
     return criterion
 
 
+def parse_multiclass(config, criterion, data_key="data_path"):
+    """``config.multiclass`` -> K = ``config.out_classes`` when the key is true, None when it is absent or false (then nothing of the
+    run changes).  The labels of the data set are the classes 0..K-1 (0 = background); the step takes the label path of
+    engine.train_step.  Needs 2 <= out_classes <= 16, a compound ``config.loss`` (``criterion`` = what parse_loss
+    returned; the fused label tail is the compound losses') and volumes: refused with ``<data_key>=synthetic``, whose labels are
+    binary.  ``criterion`` = False skips the loss check (predict.py, where no loss runs)."""
+    get = lambda k: config.get(k) if hasattr(config, "get") else getattr(config, k, None)
+    v = get("multiclass")
+    if _absent(v):
+        return None
+    if not isinstance(v, bool) and str(v).lower() not in ("true", "false", "1", "0", "yes", "no"):
+        raise ValueError(f"config.multiclass must be true or false, got {v!r}")
+    if str(v).lower() in ("false", "0", "no"):
+        return None
+    K = get("out_classes")
+    if isinstance(K, bool) or not isinstance(K, int) or not 2 <= K <= F.MAX_LOSS_CLASSES:
+        raise ValueError(f"config.multiclass needs config.out_classes in 2..{F.MAX_LOSS_CLASSES} (the labels 0..out_classes-1), got {K!r}")
+    if criterion is None:
+        raise ValueError("config.multiclass needs a compound config.loss (" + ", ".join(F.LOSS_MODES) + "): the BCE default has no label form")
+    if str(get(data_key)) == "synthetic":
+        raise ValueError(f"config.multiclass needs labelled volumes: {data_key}=synthetic draws binary labels")
+    return K
+
+
 def boundary_ramp(weight, epoch, ramp_epochs):
     """The factor of the boundary term during (1-based) ``epoch``: weight * min(1, epoch / ramp_epochs), the schedule of the paper
     (the term enters gradually); ramp_epochs = 0: always the weight."""
@@ -193,6 +216,12 @@ def train(config, model, logger):
     criterion = parse_loss(config)                                              # config.loss: None = the live BCE path (train.py:115)
     if criterion is not None:
         logger.info(f"loss: {criterion}")
+    multiclass = parse_multiclass(config, criterion)                            # config.multiclass: K = out_classes, or None
+    mc = {}
+    if multiclass is not None:
+        # the label-range counter: every step adds to it on the device, read once per epoch
+        mc = {"multiclass": multiclass, "label_bad": torch.zeros(1, dtype=torch.int64, device=device)}
+        logger.info(f"multi-class: labels 0..{multiclass - 1}, per-class Dice in scalars.jsonl")
     act_dtype = mixed_precision_dtype(config)                                   # Accelerator(mixed_precision=...) of train.py:167
     if act_dtype != torch.float32:
         logger.info(f"mixed precision: activations in {act_dtype} (fp32 parameters, gradients, statistics, loss)")
@@ -212,13 +241,16 @@ def train(config, model, logger):
             if hip_graph and graphed is None:
                 # the first iteration runs inside the constructor (eager, on a side stream: workspaces sized, kernel attributes set),
                 # then the iteration is captured for the following ones; a replay waits for the buffer broadcast launched above
-                graphed = GraphedTrainStep(model, optimizer, x, gt, criterion=criterion, warmup=1, dtype=act_dtype, grad_hook=reducer)
+                graphed = GraphedTrainStep(model, optimizer, x, gt, criterion=criterion, warmup=1, dtype=act_dtype, grad_hook=reducer,
+                                           multiclass=multiclass)
+                if multiclass is not None:
+                    mc["label_bad"] = graphed.label_bad
                 out = dict(graphed.first)
-                out["jaccard"], out["dice"] = metric_from_counts(out["counts"].cpu().tolist())
+                _sync_metrics(out, multiclass)
             elif hip_graph:
                 out = graphed(x, gt)
             else:
-                out = train_step(model, optimizer, x, gt, criterion=criterion, grad_hook=reducer, dtype=act_dtype)    # train.py:187-221
+                out = train_step(model, optimizer, x, gt, criterion=criterion, grad_hook=reducer, dtype=act_dtype, **mc)    # train.py:187-221
             iteration += 1
             loss_meter.update(out["loss"].item(), x.size(0))
             dice_meter.update(out["dice"], x.size(0))
@@ -227,9 +259,17 @@ def train(config, model, logger):
                 if criterion is not None:                       # a compound loss: its terms, unweighted
                     for name, v in zip(criterion.term_names, out["loss_terms"].tolist()):
                         row[f"Training/loss_{name}"] = v        # voxel, region, then cldice / boundary when their weights are > 0
+                if multiclass is not None:
+                    for k in range(1, multiclass):
+                        row[f"Training/dice_class_{k}"] = out["class_dice"][k]
                 scalars.write(json.dumps(row) + "\n")
                 scalars.flush()
             logger.info(f"\nEpoch: {epoch} Batch: {i}, train time: {time.time() - t0:.3f}s\nLoss: {loss_meter.val}\nDice: {dice_meter.val}\n")
+        if multiclass is not None:
+            bad = int(mc["label_bad"].item())                           # one D2H copy per epoch
+            if bad:
+                raise ValueError(f"config.multiclass: {bad} label voxels of epoch {epoch} are not integers in 0..{multiclass - 1} "
+                                 f"(config.out_classes={multiclass})")
         if scheduler is not None:
             scheduler.step()
             logger.info(f"Learning rate:  {scheduler.get_last_lr()[0]}")

@@ -158,7 +158,18 @@ class CompoundLoss(nn.Module):
         out = F.loss_tail(pred, target, self.spec)
         if not self.cldice_weight > 0 and not self.boundary_weight > 0:
             return out
-        loss, mask, counts, terms = out
+        return self._extra_terms(pred, target, *out)
+
+    def tail_labels(self, pred, labels_u8):
+        """``tail`` on a uint8 label map [N,...] (functional.labels_u8; config.multiclass): (loss, mask, counts, terms,
+        class_counts) with class_counts int64 [K,3] = per class (tp, pred, gt).  The one-hot target is built (once, by
+        functional.one_hot_labels) only for the clDice and boundary terms; without them no one-hot tensor exists in the step."""
+        loss, mask, counts, terms, class_counts = F.loss_tail_labels(pred, labels_u8, self.spec)
+        if self.cldice_weight > 0 or self.boundary_weight > 0:
+            loss, mask, counts, terms = self._extra_terms(pred, F.one_hot_labels(labels_u8, pred.shape[1]), loss, mask, counts, terms)
+        return loss, mask, counts, terms, class_counts
+
+    def _extra_terms(self, pred, target, loss, mask, counts, terms):
         extra = [terms]
         if self.cldice_weight > 0:
             cl, parts = F.soft_cldice_full(pred, target, self.cldice_iters, self.cldice_smooth)

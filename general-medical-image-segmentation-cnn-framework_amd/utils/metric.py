@@ -24,6 +24,28 @@ def metric_from_counts(counts):
     return inter / (union + smooth), 2 * inter / (gsum + psum + smooth)
 
 
+def class_metrics_from_counts(class_counts):
+    """class_counts = K rows (tp_k, pred_k, gt_k) (functional.loss_tail_labels / functional.class_counts; a tensor, or nested
+    lists) -> {"dice", "jaccard", "precision", "recall": lists of K floats, "mean_dice": float}, each with the reference's
+    smoothing per class (utils/metric.py:57-66).  ``mean_dice`` is the run's scalar Dice: the mean of dice_k over the foreground
+    classes 1..K-1 that occur (gt_k + pred_k > 0), 0.0 when none does; at K = 2 it is metric_from_counts' Dice, number for number."""
+    rows = class_counts.cpu().tolist() if hasattr(class_counts, "cpu") else list(class_counts)
+    rows = [[int(v) for v in row] for row in rows]
+    if not rows or any(len(row) != 3 for row in rows):
+        raise ValueError(f"class_counts must be K rows of (tp, pred, gt), got {rows!r}")
+    smooth = 0.001
+    out = {"dice": [], "jaccard": [], "precision": [], "recall": []}
+    for tp, psum, gsum in rows:
+        out["dice"].append(2 * tp / (gsum + psum + smooth))
+        out["jaccard"].append(tp / (gsum + psum - tp + smooth))
+        out["precision"].append(tp / (psum + smooth))
+        out["recall"].append(tp / (gsum + smooth))
+    present = [k for k in range(1, len(rows)) if rows[k][1] + rows[k][2] > 0]
+    for name in ("dice", "jaccard"):                 # (mean_jaccard: the same mean, what a step reports beside its Dice)
+        out["mean_" + name] = sum(out[name][k] for k in present) / len(present) if present else 0.0
+    return out
+
+
 def rates_from_counts(counts):
     """counts = the eight integers of functional.confusion_counts -> (precision, recall), utils/metric.py:57-59."""
     gsum, psum, tp = int(counts[0]), int(counts[1]), int(counts[4])

@@ -656,6 +656,48 @@ int mi355seg_loss_tail_bwd_f32(const float* logits, const float* target, const d
                                long long N, int K, long long S, int voxel_term, int region_term, float gamma,
                                float* dlogits, void* stream);
 
+/* Label-map targets (config.multiclass; csrc/loss_tail.hip).
+ * labels_u8[i] = (uint8) gt[i] for the float label map gt[n] ([N,1,S] as the patch queue delivers it), K classes, 1 <= K <= 16.  A
+ * value that is not an integer in [0, K) (a NaN included) is stored as 255 and counted: the number of such voxels is ADDED to the
+ * device counter bad (int64[1], 8-byte aligned; the caller zeroes it once and reads it when it likes).  One streaming launch; the
+ * counter is written only by a block that met such a value (one integer add per block, order-free).
+ * Refused before any launch: null pointers, K outside 1..16, n < 1, a misaligned counter. */
+int mi355seg_labels_u8_f32(const float* gt, long long n, int K, uint8_t* labels_u8, int64_t* bad, void* stream);
+/* out[n][k][s] = (labels_u8[n][s] == k) as float, [N,K,S]; a label >= K (255) gives an all-zero column.  For the terms that take a
+ * one-hot target (cldice, boundary) and for tests.  Refused before any launch: null pointers, K outside 1..16, N or S < 1. */
+int mi355seg_onehot_u8_f32(const uint8_t* labels_u8, long long N, int K, long long S, float* out, void* stream);
+
+/* mi355seg_loss_tail_fwd_f32 / _bwd_f32 with the uint8 label map labels [N,S] in place of the float one-hot target [N,K,S]: the
+ * same terms, weights and outputs, and one more output, class_counts int64[3 K] = per class k (tp_k, pred_k, gt_k): voxels with
+ * argmax logits == k and label == k, with argmax logits == k, with label == k.  Class membership is the comparison label == k,
+ * never an index: a label >= K belongs to no class, and gt.argmax of the four Dice counters (and the ce label) is then 0, what
+ * the one-hot form gives for an all-zero column.
+ * CONTRACT: for labels in [0, K) every output that the one-hot entry points also produce (loss, terms, sums, mask, counts, coef,
+ * dlogits) has the bits they produce on mi355seg_onehot_u8_f32(labels).  Deterministic (fixed-order partials, no atomics),
+ * nothing passes through the host, capturable in a HIP graph; 16-byte logit loads and 4-byte label loads when S % 4 == 0, K <= 4.
+ * The forward is the pass and the one-block finalise; above four classes one more launch counts tp_k and pred_k from the labels
+ * and the mask the pass wrote.
+ * Refused before any launch: what mi355seg_loss_tail_fwd_f32 refuses (null pointers, K outside 1..16, an unknown term, both terms
+ * absent, ce with K = 1, gamma outside {0} u [1,8], negative alpha / beta / weights), a workspace below
+ * mi355seg_loss_tail_lab_ws_bytes (0 for bad extents), and, where S % 4 == 0 and K <= 4, logits / dlogits not 16-byte or labels
+ * not 4-byte aligned (the one-hot form would take its scalar path there; this form refuses, so that its path follows from S). */
+size_t mi355seg_loss_tail_lab_ws_bytes(long long N, int K, long long S);
+int mi355seg_loss_tail_fwd_lab_f32(const float* logits, const uint8_t* labels, long long N, int K, long long S,
+                                   int voxel_term, int region_term, float gamma, float alpha, float beta, float w_voxel, float w_region,
+                                   float* loss, double* terms, double* sums, int64_t* mask, int64_t* counts, double* coef,
+                                   int64_t* class_counts, void* ws, size_t ws_bytes, void* stream);
+int mi355seg_loss_tail_bwd_lab_f32(const float* logits, const uint8_t* labels, const double* coef, const float* gscale,
+                                   long long N, int K, long long S, int voxel_term, int region_term, float gamma,
+                                   float* dlogits, void* stream);
+
+/* The same int64[3 K] (per class tp_k, pred_k, gt_k) from two int64 label volumes of n voxels, where no loss runs (predict.py):
+ * one pass plus the shared partials finalise.  A value outside [0, K) in either volume belongs to no class.
+ * Refused before any launch: null pointers, K outside 1..16, n < 1, a workspace below mi355seg_class_counts_ws_bytes or not
+ * 8-byte aligned. */
+size_t mi355seg_class_counts_ws_bytes(long long n, int K);
+int mi355seg_class_counts_i64(const int64_t* gt_labels, const int64_t* pred_labels, long long n, int K, int64_t* out,
+                              void* ws, size_t ws_bytes, void* stream);
+
 /* Soft-clDice loss term (csrc/cldice.hip; no reference line in this project's model: the official clDice of Shit
  * et al., CVPR 2021 -- soft_skeleton.py's soft_erode / soft_dilate / soft_open / soft_skel and cldice.py's soft_cldice).
  * Volumes are [NC, D, H, W] fp32, W fastest, at most 2^31 - 1 voxels per call; iters in 1..32.
