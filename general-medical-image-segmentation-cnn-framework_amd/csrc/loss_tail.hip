@@ -4,6 +4,10 @@
 // 2,048 blocks, grid-stride loop, per-thread fp64 accumulators, wavefront sum -> one LDS hop -> per-block partials, fixed-order
 // fp64 / int64 finalise (here one block of 1,024 threads over all columns of the partial table at once), no atomics.
 //
+// The target comes in two forms, a float one-hot volume [N,K,S] or a uint8 label map [N,S] (config.multiclass).
+// Both run ONE text: every kernel and every entry-point body below is written once and instantiated with OneHotTarget and with
+// LabelTarget, which hold what differs (the forward's accumulator set, the one thing more, sits behind `if constexpr` in it).
+//
 // Reference: nn.BCEWithLogitsLoss train.py:115,209; cross_entropy_3D loss_function.py:8-16; DiceLoss loss_function.py:121-130;
 // pred.argmax(dim=1, keepdim=True) train.py:204; metric() utils/metric.py:20-75.  Focal (Lin et al.) and Tversky (Salehi et al.)
 // are the project's own definitions.
@@ -22,6 +26,7 @@ enum { TAIL_V_NONE = 0, TAIL_V_BCE = 1, TAIL_V_FOCAL = 2, TAIL_V_CE = 3 };
 enum { TAIL_R_NONE = 0, TAIL_R_DICE = 1, TAIL_R_TVERSKY = 2 };
 
 static int tail_grid(long long items) { return stream_grid(items, kTailThreads, kTailMaxBlocks); }
+static bool tail_aligned(const void* p, unsigned bytes) { return ((uintptr_t)p % bytes) == 0; }
 
 // q^g for g = 1, 2 (exact products) or any g >= 1
 __device__ __forceinline__ float tail_pow(float q, float g) { return g == 1.f ? q : (g == 2.f ? q * q : powf(q, g)); }
@@ -39,47 +44,156 @@ __device__ __forceinline__ void tail_load(const float* __restrict__ p, float (&v
     }
 }
 
+// the labels of V consecutive voxels: one 4-byte load for V = 4
+template <int V>
+__device__ __forceinline__ void tail_load_lab(const uint8_t* __restrict__ p, int (&v)[V]) {
+    if constexpr (V == 4) {
+        const uint32_t a = *reinterpret_cast<const uint32_t*>(p);
+        v[0] = a & 255u; v[1] = (a >> 8) & 255u; v[2] = (a >> 16) & 255u; v[3] = a >> 24;
+    } else {
+        v[0] = p[0];
+    }
+}
+
+__device__ __forceinline__ float tail_opaque(float b) {
+    asm("" : "+v"(b));
+    return b;
+}
+
+// ----------------------------------------------------------------------------- the target policies
+// A policy says what the kernels and the entry points below do not.  For the device: Elem (what the target pointer points to) and
+// Voxels<KT, V>, what a thread holds of the target of its V voxels -- how it is loaded, value(k, j) (the target value b of class k),
+// and the class of the four Dice counters and of the ce label, the NaN-first argmax of the column, as a running Best: first(j, K),
+// then best = next(best, k, j) for k = 1 .. K-1.  For the host: the alignment rule and the bytes a launch moves.
+//
+// CONTRACT (4.22): for labels in [0, K) LabelTarget gives every output the bits OneHotTarget gives on onehot(labels); a label >= K
+// is the all-zero column (argmax 0, member of no class).  The thread-to-voxel map, the per-thread accumulation order, the partial
+// table and the finalise are shared by construction: there is one text.  What the label policy adds to that: value() passes
+// b = (label == k) through tail_opaque, so that the compiler meets an unknown float where the one-hot form meets a load and forms
+// the per-element expressions (and their fused multiply-adds) the same way.  Class membership is a comparison, never an index.
+
+struct OneHotTarget {
+    using Elem = float;                          // [N,K,S]
+    static constexpr bool kLabels = false;
+    // a misaligned pointer is served by the scalar path
+    static constexpr bool kRefuseMisaligned = false;
+    static bool aligned(const float* t) { return tail_aligned(t, 16); }
+    static double fwd_bytes(int K) { return 8.0 * K + 8.0; }
+    static double bwd_bytes(int K) { return 12.0 * K; }
+
+    template <int KT, int V>
+    struct Voxels {
+        float tv[KT][V];
+        struct Best { float v; int k; };
+        const float* pt;                         // the next class of the thread's voxels
+        // base: the offset of (n, class 0, s) in [N,K,S]
+        __device__ __forceinline__ Voxels(const float* __restrict__ t, long long base, long long) : pt(t + base) {}
+        // class k (called in the class loop, beside the load of the logits)
+        __device__ __forceinline__ void load_class(int k, long long S) { tail_load<V>(pt, tv[k]); pt += S; }
+        __device__ __forceinline__ void load_voxels() {}
+        __device__ __forceinline__ float value(int k, int j) const { return tv[k][j]; }
+        __device__ __forceinline__ Best first(int j, int K) const { return {tv[0][j], 0}; }
+        __device__ __forceinline__ Best next(Best m, int k, int j) const {
+            if (nan_first_gt(tv[k][j], m.v)) { m.v = tv[k][j]; m.k = k; }
+            return m;
+        }
+    };
+};
+
+struct LabelTarget {
+    using Elem = uint8_t;                        // [N,S]
+    static constexpr bool kLabels = true;
+    // the label form takes the path (16-byte or scalar) the one-hot form takes at the same S, or the bits would differ: where
+    // S % 4 == 0 and K <= 4 a misaligned pointer is refused, not served by the other path
+    static constexpr bool kRefuseMisaligned = true;
+    static bool aligned(const uint8_t* t) { return tail_aligned(t, 4); }
+    static double fwd_bytes(int K) { return 4.0 * K + 9.0; }
+    static double bwd_bytes(int K) { return 8.0 * K + 1.0; }
+
+    template <int KT, int V>
+    struct Voxels {
+        int lb[V];
+        struct Best { int k; };
+        const uint8_t* pv;                       // the labels of the thread's voxels
+        // v0: the offset of (n, s) in [N,S]
+        __device__ __forceinline__ Voxels(const uint8_t* __restrict__ t, long long, long long v0) : pv(t + v0) {}
+        __device__ __forceinline__ void load_class(int, long long) {}
+        // (called after the class loop)
+        __device__ __forceinline__ void load_voxels() { tail_load_lab<V>(pv, lb); }
+        __device__ __forceinline__ bool is(int k, int j) const { return lb[j] == k; }
+        __device__ __forceinline__ float value(int k, int j) const { return tail_opaque(is(k, j) ? 1.f : 0.f); }
+        __device__ __forceinline__ Best first(int j, int K) const { return {lb[j] < K ? lb[j] : 0}; }
+        __device__ __forceinline__ Best next(Best m, int, int) const { return m; }
+    };
+};
+
+// up to this capacity the label forward counts tp and pred itself; above it tail_lab_counts_kernel does, in a launch of its own
+// (measured, DESIGN.md 4.22: inside the 16-slot kernel the two counters cost more than the two fp64 accumulators the label form drops)
+#ifndef TAIL_LAB_FUSED_COUNT_MAX_KT
+#define TAIL_LAB_FUSED_COUNT_MAX_KT 4
+#endif
+constexpr int kTailLabFusedCountMaxKT = TAIL_LAB_FUSED_COUNT_MAX_KT;
+
 // KT: the compile-time class capacity (K == KT for KT <= 4, K <= KT above); V: voxels per thread and trip (4: 16-byte loads, needs
 // S % 4 == 0 and aligned pointers).  part: per block 1 + 5 * K doubles (voxel-term sum; per class I, P, T, sum a^2, sum t^2);
 // cpart: per block the four counters.
-template <int KT, int V>
-__global__ __launch_bounds__(kTailThreads) void loss_tail_fwd_kernel(const float* __restrict__ x, const float* __restrict__ t,
+// The label form: sum t and sum t^2 are the integer gt_k, exact in fp64 in any order, so two of the five fp64 accumulators per class
+// become one 32-bit counter, and the room goes to the class counters tp_k, pred_k (a thread sees fewer than 2^31 voxels; they are
+// widened to int64 in the block reduction).  kpart: per block 3 K counters (per class tp, pred, gt; null for the one-hot form).
+// CNT: tp and pred are counted here; without it this kernel fills only the gt column and tail_lab_counts_kernel, on the same grid,
+// the two others (the 8- and 16-slot kernels run two wavefronts per SIMD and pay for every instruction).
+template <int KT, int V, class Target, bool CNT>
+__global__ __launch_bounds__(kTailThreads) void loss_tail_fwd_kernel(const float* __restrict__ x, const typename Target::Elem* __restrict__ t,
         long long N, int Krt, long long S, int vmode, float gamma, int64_t* __restrict__ mask,
-        double* __restrict__ part, long long* __restrict__ cpart) {
+        double* __restrict__ part, long long* __restrict__ cpart, long long* __restrict__ kpart) {
+    constexpr bool kLab = Target::kLabels;
+    constexpr int NS = kLab ? 3 : 5;             // one-hot: sum p t, sum p, sum t, sum p^2, sum t^2; labels: sum p t, sum p, sum p^2
+    static_assert(kLab || !CNT, "the class counters belong to the label form");
     const int K = KT <= 4 ? KT : Krt;
     double vacc = 0.0;
-    double sacc[KT][5];
+    double sacc[KT][NS];
+    unsigned kacc[KT][3];                        // labels: tp, pred, gt (tp and pred stay 0 without CNT)
 #pragma unroll
-    for (int k = 0; k < KT; ++k)
+    for (int k = 0; k < KT; ++k) {
 #pragma unroll
-        for (int j = 0; j < 5; ++j) sacc[k][j] = 0.0;
+        for (int j = 0; j < NS; ++j) sacc[k][j] = 0.0;
+#pragma unroll
+        for (int j = 0; j < 3; ++j) kacc[k][j] = 0u;
+    }
     long long cacc[4] = {0, 0, 0, 0};
     const long long groups = N * S / V;
     for (long long g = (long long)blockIdx.x * blockDim.x + threadIdx.x; g < groups; g += (long long)gridDim.x * blockDim.x) {
         const long long v0 = g * V, n = v0 / S, s = v0 - n * S;
         const float* px = x + n * K * S + s;
-        const float* pt = t + n * K * S + s;
-        float xv[KT][V], tv[KT][V];
+        float xv[KT][V];
+        typename Target::template Voxels<KT, V> tgt(t, n * K * S + s, v0);
 #pragma unroll
         for (int k = 0; k < KT; ++k)
-            if (k < K) { tail_load<V>(px, xv[k]); tail_load<V>(pt, tv[k]); px += S; pt += S; }
+            if (k < K) { tail_load<V>(px, xv[k]); tgt.load_class(k, S); px += S; }
+        tgt.load_voxels();
         long long mk[V];
 #pragma unroll
         for (int j = 0; j < V; ++j) {
-            float bx = xv[0][j], bt = tv[0][j];
-            int ix = 0, it = 0;
+            auto best = tgt.first(j, K);
+            float bx = xv[0][j];
+            int ix = 0;
             float l = 0.f;
 #pragma unroll
             for (int k = 0; k < KT; ++k)
                 if (k < K) {
-                    const float a = xv[k][j], b = tv[k][j];
+                    const float a = xv[k][j], b = tgt.value(k, j);
                     if (k > 0) {
                         if (nan_first_gt(a, bx)) { bx = a; ix = k; }
-                        if (nan_first_gt(b, bt)) { bt = b; it = k; }
+                        best = tgt.next(best, k, j);
                     }
                     const float p = sigmoid(a);
-                    sacc[k][0] += (double)(p * b); sacc[k][1] += (double)p; sacc[k][2] += (double)b;
-                    sacc[k][3] += (double)(p * p); sacc[k][4] += (double)(b * b);
+                    sacc[k][0] += (double)(p * b); sacc[k][1] += (double)p;
+                    if constexpr (kLab) {
+                        sacc[k][2] += (double)(p * p);
+                        kacc[k][2] += tgt.is(k, j);
+                    } else {
+                        sacc[k][2] += (double)b; sacc[k][3] += (double)(p * p); sacc[k][4] += (double)(b * b);
+                    }
                     if (vmode == TAIL_V_BCE) {
                         l += bce_term(a, b);
                     } else if (vmode == TAIL_V_FOCAL) {
@@ -87,6 +201,7 @@ __global__ __launch_bounds__(kTailThreads) void loss_tail_fwd_kernel(const float
                         l += tail_pow(q, gamma) * bce_term(a, b);
                     }
                 }
+            const int it = best.k;
             if (vmode == TAIL_V_CE) {
                 // logsumexp_k x - x[label], label = argmax_k t; log_softmax's order: rounds at the size of the term (ce3d_fwd_kernel)
                 float m = -INFINITY, xl = xv[0][j];
@@ -101,6 +216,11 @@ __global__ __launch_bounds__(kTailThreads) void loss_tail_fwd_kernel(const float
             }
             vacc += (double)l;
             mk[j] = ix;
+            if constexpr (CNT) {
+#pragma unroll
+                for (int k = 0; k < KT; ++k)
+                    if (k < K) { kacc[k][1] += (ix == k); kacc[k][0] += (ix == k && tgt.is(k, j)); }
+            }
             cacc[0] += it; cacc[1] += ix;
             cacc[2] += ((it & ix) != 0); cacc[3] += ((it | ix) != 0);
         }
@@ -109,15 +229,26 @@ __global__ __launch_bounds__(kTailThreads) void loss_tail_fwd_kernel(const float
     }
     const int R = 1 + 5 * K;
     double* prow = part + (long long)blockIdx.x * R;
+    long long* krow = kLab ? kpart + (long long)blockIdx.x * 3 * K : nullptr;
     double s = block_reduce_one<OpSum, true>(vacc);
     if (threadIdx.x == 0) prow[0] = s;
 #pragma unroll
     for (int k = 0; k < KT; ++k)
         if (k < K) {
 #pragma unroll
-            for (int j = 0; j < 5; ++j) {
+            for (int j = 0; j < NS; ++j) {
                 s = block_reduce_one<OpSum, true>(sacc[k][j]);
-                if (threadIdx.x == 0) prow[1 + 5 * k + j] = s;
+                if (threadIdx.x == 0) prow[1 + 5 * k + (kLab && j == 2 ? 3 : j)] = s;
+            }
+            if constexpr (kLab) {
+#pragma unroll
+                for (int j = CNT ? 0 : 2; j < 3; ++j) {
+                    const long long c = block_reduce_one<OpSum, true>((long long)kacc[k][j]);
+                    if (threadIdx.x == 0) {
+                        krow[3 * k + j] = c;
+                        if (j == 2) { prow[1 + 5 * k + 2] = (double)c; prow[1 + 5 * k + 4] = (double)c; }      // sum t = sum t^2 = gt_k
+                    }
+                }
             }
         }
 #pragma unroll
@@ -125,6 +256,32 @@ __global__ __launch_bounds__(kTailThreads) void loss_tail_fwd_kernel(const float
         const long long c = block_reduce_one<OpSum, true>(cacc[j]);
         if (threadIdx.x == 0) cpart[(long long)blockIdx.x * 4 + j] = c;
     }
+}
+
+// the tp and pred columns of kpart from the labels and the mask the forward wrote, for the label forwards without CNT: the same
+// grid (block b fills row b, a block without voxels zeros)
+template <int KT>
+__global__ __launch_bounds__(kTailThreads) void tail_lab_counts_kernel(const uint8_t* __restrict__ lab, const int64_t* __restrict__ mask,
+                                                                       long long n, int K, long long* __restrict__ kpart) {
+    unsigned acc[KT][2];
+#pragma unroll
+    for (int k = 0; k < KT; ++k) { acc[k][0] = 0u; acc[k][1] = 0u; }
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
+        const int lj = lab[i], ix = (int)mask[i];
+#pragma unroll
+        for (int k = 0; k < KT; ++k)
+            if (k < K) { acc[k][1] += (ix == k); acc[k][0] += (ix == k && lj == k); }
+    }
+    long long* krow = kpart + (long long)blockIdx.x * 3 * K;
+#pragma unroll
+    for (int k = 0; k < KT; ++k)
+        if (k < K) {
+#pragma unroll
+            for (int j = 0; j < 2; ++j) {
+                const long long c = block_reduce_one<OpSum, true>((long long)acc[k][j]);
+                if (threadIdx.x == 0) krow[3 * k + j] = c;
+            }
+        }
 }
 
 // One block of 1,024 threads.  Reduces the partials in a fixed order and writes loss (fp32), terms (fp64[2]: voxel, region,
@@ -137,7 +294,7 @@ __global__ __launch_bounds__(kTailThreads) void loss_tail_fwd_kernel(const float
 // columns x 1024 / (3 K) groups, then one thread per column in ascending group), into class_counts int64[3 K].
 constexpr int kTailFinThreads = 1024;
 template <bool CLS>
-__device__ __forceinline__ void tail_finalize(const double* __restrict__ part, const long long* __restrict__ cpart,
+__global__ __launch_bounds__(kTailFinThreads) void loss_tail_finalize_kernel(const double* __restrict__ part, const long long* __restrict__ cpart,
         const long long* __restrict__ kpart, int nblk, int K, int vmode, int rmode, double alpha, double beta, double wv, double wr,
         double M, double Vox, float* __restrict__ loss, double* __restrict__ terms, double* __restrict__ sums,
         int64_t* __restrict__ counts, double* __restrict__ coef, int64_t* __restrict__ class_counts) {
@@ -213,13 +370,6 @@ __device__ __forceinline__ void tail_finalize(const double* __restrict__ part, c
     loss[0] = (float)(wv * voxel + wr * region);
 }
 
-__global__ __launch_bounds__(kTailFinThreads) void loss_tail_finalize_kernel(const double* __restrict__ part, const long long* __restrict__ cpart,
-        int nblk, int K, int vmode, int rmode, double alpha, double beta, double wv, double wr, double M, double Vox,
-        float* __restrict__ loss, double* __restrict__ terms, double* __restrict__ sums, int64_t* __restrict__ counts,
-        double* __restrict__ coef) {
-    tail_finalize<false>(part, cpart, nullptr, nblk, K, vmode, rmode, alpha, beta, wv, wr, M, Vox, loss, terms, sums, counts, coef, nullptr);
-}
-
 // a + b with both operands already rounded to fp32: the addition is not contracted with the product that formed an operand
 __device__ __forceinline__ float tail_add_rounded(float a, float b) {
 #pragma clang fp contract(off)
@@ -232,8 +382,8 @@ __device__ __forceinline__ float tail_add_rounded(float a, float b) {
 // unit weights dice_bce and dice_ce give the BITS of DiceLoss + BCEWithLogitsLoss and cross_entropy_3D + DiceLoss.  That matters
 // beyond tidiness: a network holds parameters whose exact gradient is zero (a convolution bias ahead of a BatchNorm), what a step
 // returns for them is the rounding residue of the whole backward, and a last-bit change of dlogits redraws it.
-template <int KT, int V>
-__global__ __launch_bounds__(kTailThreads) void loss_tail_bwd_kernel(const float* __restrict__ x, const float* __restrict__ t,
+template <int KT, int V, class Target>
+__global__ __launch_bounds__(kTailThreads) void loss_tail_bwd_kernel(const float* __restrict__ x, const typename Target::Elem* __restrict__ t,
         const double* __restrict__ coef, const float* __restrict__ gscale, long long N, int Krt, long long S,
         int vmode, int rmode, float gamma, float* __restrict__ dx) {
     const int K = KT <= 4 ? KT : Krt;
@@ -251,30 +401,31 @@ __global__ __launch_bounds__(kTailThreads) void loss_tail_bwd_kernel(const float
     for (long long g = (long long)blockIdx.x * blockDim.x + threadIdx.x; g < groups; g += (long long)gridDim.x * blockDim.x) {
         const long long v0 = g * V, n = v0 / S, s = v0 - n * S, base = n * K * S + s;
         const float* px = x + base;
-        const float* pt = t + base;
         float* pd = dx + base;
-        float xv[KT][V], tv[KT][V];
+        float xv[KT][V];
+        typename Target::template Voxels<KT, V> tgt(t, base, v0);
 #pragma unroll
         for (int k = 0; k < KT; ++k)
-            if (k < K) { tail_load<V>(px, xv[k]); tail_load<V>(pt, tv[k]); px += S; pt += S; }
+            if (k < K) { tail_load<V>(px, xv[k]); tgt.load_class(k, S); px += S; }
+        tgt.load_voxels();
         float m[V], inv[V];
         int lab[V];
         if (vmode == TAIL_V_CE) {
 #pragma unroll
             for (int j = 0; j < V; ++j) {
-                float bt = tv[0][j], mm = -INFINITY;
-                int it = 0;
+                auto best = tgt.first(j, K);
+                float mm = -INFINITY;
 #pragma unroll
                 for (int k = 0; k < KT; ++k)
                     if (k < K) {
                         mm = fmaxf(mm, xv[k][j]);
-                        if (k > 0 && nan_first_gt(tv[k][j], bt)) { bt = tv[k][j]; it = k; }
+                        if (k > 0) best = tgt.next(best, k, j);
                     }
                 float sum = 0.f;
 #pragma unroll
                 for (int k = 0; k < KT; ++k)
                     if (k < K) sum += expf(xv[k][j] - mm);
-                m[j] = mm; inv[j] = 1.f / sum; lab[j] = it;
+                m[j] = mm; inv[j] = 1.f / sum; lab[j] = best.k;
             }
         }
 #pragma unroll
@@ -283,7 +434,7 @@ __global__ __launch_bounds__(kTailThreads) void loss_tail_bwd_kernel(const float
                 float o[V];
 #pragma unroll
                 for (int j = 0; j < V; ++j) {
-                    const float a = xv[k][j], b = tv[k][j];
+                    const float a = xv[k][j], b = tgt.value(k, j);
                     const float p = sigmoid(a), dp = p * (1.f - p);
                     float d = 0.f;
                     if (vmode == TAIL_V_BCE) {
@@ -305,319 +456,6 @@ __global__ __launch_bounds__(kTailThreads) void loss_tail_bwd_kernel(const float
                 pd += S;
             }
     }
-}
-
-static int tail_capacity(int K) { return K <= 4 ? K : (K <= 8 ? 8 : 16); }
-
-template <int V>
-static void tail_launch_fwd(int KT, int nblk, hipStream_t st, const float* x, const float* t, long long N, int K, long long S, int vmode,
-                            float gamma, int64_t* mask, double* part, long long* cpart) {
-#define TAIL_FWD(kt) hipLaunchKernelGGL((loss_tail_fwd_kernel<kt, V>), dim3(nblk), dim3(kTailThreads), 0, st, x, t, N, K, S, vmode, gamma, mask, part, cpart)
-    switch (KT) {
-        case 1: TAIL_FWD(1); break;
-        case 2: TAIL_FWD(2); break;
-        case 3: TAIL_FWD(3); break;
-        case 4: TAIL_FWD(4); break;
-        default:
-            if constexpr (V == 1) {                       // more than four classes: one voxel per thread (the 4-voxel form would spill)
-                if (KT == 8) TAIL_FWD(8); else TAIL_FWD(16);
-            }
-            break;
-    }
-#undef TAIL_FWD
-}
-template <int V>
-static void tail_launch_bwd(int KT, int nblk, hipStream_t st, const float* x, const float* t, const double* coef, const float* gscale,
-                            long long N, int K, long long S, int vmode, int rmode, float gamma, float* dx) {
-#define TAIL_BWD(kt) hipLaunchKernelGGL((loss_tail_bwd_kernel<kt, V>), dim3(nblk), dim3(kTailThreads), 0, st, x, t, coef, gscale, N, K, S, vmode, rmode, gamma, dx)
-    switch (KT) {
-        case 1: TAIL_BWD(1); break;
-        case 2: TAIL_BWD(2); break;
-        case 3: TAIL_BWD(3); break;
-        case 4: TAIL_BWD(4); break;
-        default:
-            if constexpr (V == 1) {                       // more than four classes: one voxel per thread (the 4-voxel form would spill)
-                if (KT == 8) TAIL_BWD(8); else TAIL_BWD(16);
-            }
-            break;
-    }
-#undef TAIL_BWD
-}
-
-static bool tail_aligned16(const void* p) { return ((uintptr_t)p % 16) == 0; }
-
-// ----------------------------------------------------------------------------- the label form (config.multiclass)
-// The same tail with a uint8 label map [N,S] in place of the float one-hot target [N,K,S].  CONTRACT: for labels in [0, K) every
-// output has the bits the kernels above give on onehot(labels); a label >= K is the all-zero column (argmax 0, member of no class).
-// How it is kept: the same thread-to-voxel map, the same per-thread accumulation order, the same partial table and the same
-// finalise; the target value b = (label == k) goes through tail_opaque, so that the compiler meets an unknown float where the
-// one-hot kernels meet a load and forms the per-element expressions (and their fused multiply-adds) the same way.  What the label
-// form drops: sum t and sum t^2 are the integer gt_k, exact in fp64 in any order, so two of the five fp64 accumulators per class
-// become one 32-bit counter, and the room goes to the class counters tp_k, pred_k (a thread sees fewer than 2^31 voxels; they are
-// widened to int64 in the block reduction).  Class membership is a comparison, never an index.
-
-__device__ __forceinline__ float tail_opaque(float b) {
-    asm("" : "+v"(b));
-    return b;
-}
-
-// the labels of V consecutive voxels: one 4-byte load for V = 4
-template <int V>
-__device__ __forceinline__ void tail_load_lab(const uint8_t* __restrict__ p, int (&v)[V]) {
-    if constexpr (V == 4) {
-        const uint32_t a = *reinterpret_cast<const uint32_t*>(p);
-        v[0] = a & 255u; v[1] = (a >> 8) & 255u; v[2] = (a >> 16) & 255u; v[3] = a >> 24;
-    } else {
-        v[0] = p[0];
-    }
-}
-
-// part, cpart: as loss_tail_fwd_kernel; kpart: per block 3 K counters (per class tp, pred, gt).  CNT: tp and pred are counted here;
-// without it this kernel fills only the gt column and tail_lab_counts_kernel, on the same grid, the two others (the 8- and
-// 16-slot kernels run two wavefronts per SIMD and pay for every instruction: see kTailLabFusedCountMaxKT).
-template <int KT, int V, bool CNT>
-__global__ __launch_bounds__(kTailThreads) void loss_tail_fwd_lab_kernel(const float* __restrict__ x, const uint8_t* __restrict__ lab,
-        long long N, int Krt, long long S, int vmode, float gamma, int64_t* __restrict__ mask,
-        double* __restrict__ part, long long* __restrict__ cpart, long long* __restrict__ kpart) {
-    const int K = KT <= 4 ? KT : Krt;
-    double vacc = 0.0;
-    double sacc[KT][3];                          // sum p t, sum p, sum p^2
-    unsigned kacc[KT][3];                        // tp, pred, gt (tp and pred stay 0 without CNT)
-#pragma unroll
-    for (int k = 0; k < KT; ++k)
-#pragma unroll
-        for (int j = 0; j < 3; ++j) { sacc[k][j] = 0.0; kacc[k][j] = 0u; }
-    long long cacc[4] = {0, 0, 0, 0};
-    const long long groups = N * S / V;
-    for (long long g = (long long)blockIdx.x * blockDim.x + threadIdx.x; g < groups; g += (long long)gridDim.x * blockDim.x) {
-        const long long v0 = g * V, n = v0 / S, s = v0 - n * S;
-        const float* px = x + n * K * S + s;
-        float xv[KT][V];
-        int lb[V];
-#pragma unroll
-        for (int k = 0; k < KT; ++k)
-            if (k < K) { tail_load<V>(px, xv[k]); px += S; }
-        tail_load_lab<V>(lab + v0, lb);
-        long long mk[V];
-#pragma unroll
-        for (int j = 0; j < V; ++j) {
-            const int lj = lb[j], it = lj < K ? lj : 0;
-            float bx = xv[0][j];
-            int ix = 0;
-            float l = 0.f;
-#pragma unroll
-            for (int k = 0; k < KT; ++k)
-                if (k < K) {
-                    const float a = xv[k][j], b = tail_opaque(lj == k ? 1.f : 0.f);
-                    if (k > 0 && nan_first_gt(a, bx)) { bx = a; ix = k; }
-                    const float p = sigmoid(a);
-                    sacc[k][0] += (double)(p * b); sacc[k][1] += (double)p; sacc[k][2] += (double)(p * p);
-                    kacc[k][2] += (lj == k);
-                    if (vmode == TAIL_V_BCE) {
-                        l += bce_term(a, b);
-                    } else if (vmode == TAIL_V_FOCAL) {
-                        const float q = p + b - 2.f * p * b;
-                        l += tail_pow(q, gamma) * bce_term(a, b);
-                    }
-                }
-            if (vmode == TAIL_V_CE) {
-                float m = -INFINITY, xl = xv[0][j];
-#pragma unroll
-                for (int k = 0; k < KT; ++k)
-                    if (k < K) { m = fmaxf(m, xv[k][j]); if (k == it) xl = xv[k][j]; }
-                float sum = 0.f;
-#pragma unroll
-                for (int k = 0; k < KT; ++k)
-                    if (k < K) sum += expf(xv[k][j] - m);
-                l = logf(sum) - (xl - m);
-            }
-            vacc += (double)l;
-            mk[j] = ix;
-            if constexpr (CNT) {
-#pragma unroll
-                for (int k = 0; k < KT; ++k)
-                    if (k < K) { kacc[k][1] += (ix == k); kacc[k][0] += (ix == k && lj == k); }
-            }
-            cacc[0] += it; cacc[1] += ix;
-            cacc[2] += ((it & ix) != 0); cacc[3] += ((it | ix) != 0);
-        }
-#pragma unroll
-        for (int j = 0; j < V; ++j) mask[v0 + j] = mk[j];
-    }
-    const int R = 1 + 5 * K;
-    double* prow = part + (long long)blockIdx.x * R;
-    long long* krow = kpart + (long long)blockIdx.x * 3 * K;
-    double s = block_reduce_one<OpSum, true>(vacc);
-    if (threadIdx.x == 0) prow[0] = s;
-#pragma unroll
-    for (int k = 0; k < KT; ++k)
-        if (k < K) {
-#pragma unroll
-            for (int j = 0; j < 3; ++j) {
-                s = block_reduce_one<OpSum, true>(sacc[k][j]);
-                if (threadIdx.x == 0) prow[1 + 5 * k + (j == 2 ? 3 : j)] = s;
-            }
-#pragma unroll
-            for (int j = CNT ? 0 : 2; j < 3; ++j) {
-                const long long c = block_reduce_one<OpSum, true>((long long)kacc[k][j]);
-                if (threadIdx.x == 0) {
-                    krow[3 * k + j] = c;
-                    if (j == 2) { prow[1 + 5 * k + 2] = (double)c; prow[1 + 5 * k + 4] = (double)c; }      // sum t = sum t^2 = gt_k
-                }
-            }
-        }
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        const long long c = block_reduce_one<OpSum, true>(cacc[j]);
-        if (threadIdx.x == 0) cpart[(long long)blockIdx.x * 4 + j] = c;
-    }
-}
-
-// the tp and pred columns of kpart from the labels and the mask the forward wrote, for the forward kernels without CNT: the same
-// grid (block b fills row b, a block without voxels zeros)
-template <int KT>
-__global__ __launch_bounds__(kTailThreads) void tail_lab_counts_kernel(const uint8_t* __restrict__ lab, const int64_t* __restrict__ mask,
-                                                                       long long n, int K, long long* __restrict__ kpart) {
-    unsigned acc[KT][2];
-#pragma unroll
-    for (int k = 0; k < KT; ++k) { acc[k][0] = 0u; acc[k][1] = 0u; }
-    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
-        const int lj = lab[i], ix = (int)mask[i];
-#pragma unroll
-        for (int k = 0; k < KT; ++k)
-            if (k < K) { acc[k][1] += (ix == k); acc[k][0] += (ix == k && lj == k); }
-    }
-    long long* krow = kpart + (long long)blockIdx.x * 3 * K;
-#pragma unroll
-    for (int k = 0; k < KT; ++k)
-        if (k < K) {
-#pragma unroll
-            for (int j = 0; j < 2; ++j) {
-                const long long c = block_reduce_one<OpSum, true>((long long)acc[k][j]);
-                if (threadIdx.x == 0) krow[3 * k + j] = c;
-            }
-        }
-}
-
-__global__ __launch_bounds__(kTailFinThreads) void loss_tail_finalize_lab_kernel(const double* __restrict__ part, const long long* __restrict__ cpart,
-        const long long* __restrict__ kpart, int nblk, int K, int vmode, int rmode, double alpha, double beta, double wv, double wr,
-        double M, double Vox, float* __restrict__ loss, double* __restrict__ terms, double* __restrict__ sums,
-        int64_t* __restrict__ counts, double* __restrict__ coef, int64_t* __restrict__ class_counts) {
-    tail_finalize<true>(part, cpart, kpart, nblk, K, vmode, rmode, alpha, beta, wv, wr, M, Vox, loss, terms, sums, counts, coef, class_counts);
-}
-
-// loss_tail_bwd_kernel with b = (label == k) and the ce label = the label itself (0 for a label >= K)
-template <int KT, int V>
-__global__ __launch_bounds__(kTailThreads) void loss_tail_bwd_lab_kernel(const float* __restrict__ x, const uint8_t* __restrict__ lab,
-        const double* __restrict__ coef, const float* __restrict__ gscale, long long N, int Krt, long long S,
-        int vmode, int rmode, float gamma, float* __restrict__ dx) {
-    const int K = KT <= 4 ? KT : Krt;
-    const double gs = (double)gscale[0];
-    const float gw = gscale[0] * (float)coef[0];
-    const float sv = vmode == TAIL_V_CE ? gw * (1.f / (float)(N * S)) : gw / (float)(N * K * S);
-    float cI[KT], cP[KT];
-#pragma unroll
-    for (int k = 0; k < KT; ++k) {
-        cI[k] = 0.f; cP[k] = 0.f;
-        if (k < K) { cI[k] = (float)(gs * coef[1 + 2 * k]); cP[k] = (float)(gs * coef[2 + 2 * k]); }
-    }
-    const long long groups = N * S / V;
-    for (long long g = (long long)blockIdx.x * blockDim.x + threadIdx.x; g < groups; g += (long long)gridDim.x * blockDim.x) {
-        const long long v0 = g * V, n = v0 / S, s = v0 - n * S, base = n * K * S + s;
-        const float* px = x + base;
-        float* pd = dx + base;
-        float xv[KT][V];
-        int lb[V];
-#pragma unroll
-        for (int k = 0; k < KT; ++k)
-            if (k < K) { tail_load<V>(px, xv[k]); px += S; }
-        tail_load_lab<V>(lab + v0, lb);
-        float m[V], inv[V];
-        int it[V];
-        if (vmode == TAIL_V_CE) {
-#pragma unroll
-            for (int j = 0; j < V; ++j) {
-                float mm = -INFINITY;
-#pragma unroll
-                for (int k = 0; k < KT; ++k)
-                    if (k < K) mm = fmaxf(mm, xv[k][j]);
-                float sum = 0.f;
-#pragma unroll
-                for (int k = 0; k < KT; ++k)
-                    if (k < K) sum += expf(xv[k][j] - mm);
-                m[j] = mm; inv[j] = 1.f / sum; it[j] = lb[j] < K ? lb[j] : 0;
-            }
-        }
-#pragma unroll
-        for (int k = 0; k < KT; ++k)
-            if (k < K) {
-                float o[V];
-#pragma unroll
-                for (int j = 0; j < V; ++j) {
-                    const float a = xv[k][j], b = tail_opaque(lb[j] == k ? 1.f : 0.f);
-                    const float p = sigmoid(a), dp = p * (1.f - p);
-                    float d = 0.f;
-                    if (vmode == TAIL_V_BCE) {
-                        d = (p - b) * sv;
-                    } else if (vmode == TAIL_V_FOCAL) {
-                        const float q = p + b - 2.f * p * b;
-                        d = (gamma * tail_pow_m1(q, gamma) * (1.f - 2.f * b) * dp * bce_term(a, b) + tail_pow(q, gamma) * (p - b)) * sv;
-                    } else if (vmode == TAIL_V_CE) {
-                        d = sv * (expf(a - m[j]) * inv[j] - (k == it[j] ? 1.f : 0.f));
-                    }
-                    if (rmode != TAIL_R_NONE) {
-                        const float dr = (cI[k] * b + cP[k]) * dp;
-                        d = vmode == TAIL_V_NONE ? dr : tail_add_rounded(dr, d);
-                    }
-                    o[j] = d;
-                }
-                if constexpr (V == 4) *reinterpret_cast<float4*>(pd) = make_float4(o[0], o[1], o[2], o[3]);
-                else pd[0] = o[0];
-                pd += S;
-            }
-    }
-}
-
-// up to this capacity the forward counts tp and pred itself; above it tail_lab_counts_kernel does, in a launch of its own
-// (measured, DESIGN.md 4.22: inside the 16-slot kernel the two counters cost more than the two fp64 accumulators the label form drops)
-#ifndef TAIL_LAB_FUSED_COUNT_MAX_KT
-#define TAIL_LAB_FUSED_COUNT_MAX_KT 4
-#endif
-constexpr int kTailLabFusedCountMaxKT = TAIL_LAB_FUSED_COUNT_MAX_KT;
-
-template <int V>
-static void tail_launch_fwd_lab(int KT, int nblk, hipStream_t st, const float* x, const uint8_t* lab, long long N, int K, long long S,
-                                int vmode, float gamma, int64_t* mask, double* part, long long* cpart, long long* kpart) {
-#define TAIL_FWD(kt) hipLaunchKernelGGL((loss_tail_fwd_lab_kernel<kt, V, (kt <= kTailLabFusedCountMaxKT)>), dim3(nblk), dim3(kTailThreads), 0, st, x, lab, N, K, S, vmode, gamma, mask, part, cpart, kpart)
-    switch (KT) {
-        case 1: TAIL_FWD(1); break;
-        case 2: TAIL_FWD(2); break;
-        case 3: TAIL_FWD(3); break;
-        case 4: TAIL_FWD(4); break;
-        default:
-            if constexpr (V == 1) {                       // (as the one-hot form: one voxel per thread above four classes)
-                if (KT == 8) TAIL_FWD(8); else TAIL_FWD(16);
-            }
-            break;
-    }
-#undef TAIL_FWD
-}
-template <int V>
-static void tail_launch_bwd_lab(int KT, int nblk, hipStream_t st, const float* x, const uint8_t* lab, const double* coef, const float* gscale,
-                                long long N, int K, long long S, int vmode, int rmode, float gamma, float* dx) {
-#define TAIL_BWD(kt) hipLaunchKernelGGL((loss_tail_bwd_lab_kernel<kt, V>), dim3(nblk), dim3(kTailThreads), 0, st, x, lab, coef, gscale, N, K, S, vmode, rmode, gamma, dx)
-    switch (KT) {
-        case 1: TAIL_BWD(1); break;
-        case 2: TAIL_BWD(2); break;
-        case 3: TAIL_BWD(3); break;
-        case 4: TAIL_BWD(4); break;
-        default:
-            if constexpr (V == 1) {
-                if (KT == 8) TAIL_BWD(8); else TAIL_BWD(16);
-            }
-            break;
-    }
-#undef TAIL_BWD
 }
 
 // float label map -> uint8 labels; a value that is no integer in [0, K) is stored as 255 and counted.  The counter is touched only
@@ -685,83 +523,179 @@ __global__ __launch_bounds__(kTailThreads) void class_counts_kernel(const int64_
         }
 }
 
+// ----------------------------------------------------------------------------- launch
+template <int I>
+using TailInt = std::integral_constant<int, I>;
+
+static int tail_capacity(int K) { return K <= 4 ? K : (K <= 8 ? 8 : 16); }
+
+// the runtime (class capacity, 16-byte path) as the compile-time <KT, V> of the tail kernels: f(TailInt<KT>, TailInt<V>).
+// More than four classes: one voxel per thread (the 4-voxel form would spill), so `vec` is only ever set for KT <= 4.
+template <class F>
+static void tail_dispatch(int KT, bool vec, F f) {
+    auto pick_v = [&](auto kt) { vec ? f(kt, TailInt<4>{}) : f(kt, TailInt<1>{}); };
+    switch (KT) {
+        case 1: pick_v(TailInt<1>{}); break;
+        case 2: pick_v(TailInt<2>{}); break;
+        case 3: pick_v(TailInt<3>{}); break;
+        case 4: pick_v(TailInt<4>{}); break;
+        case 8: f(TailInt<8>{}, TailInt<1>{}); break;
+        default: f(TailInt<16>{}, TailInt<1>{}); break;
+    }
+}
+
+// the counting kernels' slots for K classes: f(TailInt<4 | 8 | 16>)
+template <class F>
+static void tail_dispatch_slots(int K, F f) {
+    if (K <= 4) f(TailInt<4>{});
+    else if (K <= 8) f(TailInt<8>{});
+    else f(TailInt<16>{});
+}
+
+static size_t tail_ws_bytes(long long N, int K, long long S, bool labels) {
+    if (N < 1 || S < 1 || K < 1 || K > kTailMaxClasses) return 0;
+    return (size_t)tail_grid(N * S) * ((size_t)(1 + 5 * K) * sizeof(double) + (size_t)(4 + (labels ? 3 * K : 0)) * sizeof(long long));
+}
+
+// the refusals that forward and backward share; `what` prefixes the message
+static int tail_check_spec(const char* what, long long N, int K, long long S, int voxel_term, int region_term, float gamma) {
+    SEG_CHECK_ARG(K >= 1 && K <= kTailMaxClasses, "%s: K must be in 1..%d, got %d", what, kTailMaxClasses, K);
+    SEG_CHECK_ARG(voxel_term >= TAIL_V_NONE && voxel_term <= TAIL_V_CE, "%s: unknown voxel term %d (0 none, 1 bce, 2 focal, 3 ce)", what, voxel_term);
+    SEG_CHECK_ARG(region_term >= TAIL_R_NONE && region_term <= TAIL_R_TVERSKY, "%s: unknown region term %d (0 none, 1 dice, 2 tversky)", what, region_term);
+    SEG_CHECK_ARG(voxel_term != TAIL_V_NONE || region_term != TAIL_R_NONE, "%s: both terms absent", what);
+    SEG_CHECK_ARG(voxel_term != TAIL_V_CE || K >= 2, "%s: the ce term needs K >= 2, got %d", what, K);
+    SEG_CHECK_ARG(gamma == 0.f || (gamma >= 1.f && gamma <= 8.f), "%s: gamma must be 0 or in [1, 8], got %g", what, (double)gamma);
+    SEG_CHECK_ARG(N > 0 && S > 0, "%s: bad extents N=%lld S=%lld", what, N, S);
+    return MI355SEG_OK;
+}
+
+// The path of a launch: the class capacity, the 16-byte path (K <= 4, S % 4 == 0 and every pointer aligned; floats_aligned: the
+// call's float pointers are) and the grid.  Where the policy says so, a misaligned pointer on that path is refused.
+struct TailPath {
+    int KT, nblk;
+    bool vec;
+};
+
+template <class Target>
+static int tail_path(const char* what, long long N, int K, long long S, bool floats_aligned, const typename Target::Elem* target, TailPath& p) {
+    p.KT = tail_capacity(K);
+    const bool fits = p.KT <= 4 && S % 4 == 0, aligned = floats_aligned && Target::aligned(target);
+    SEG_CHECK_ARG(!(Target::kRefuseMisaligned && fits) || aligned,
+                  "%s: with S %% 4 == 0 and K <= 4 the float pointers must be 16-byte and labels 4-byte aligned", what);
+    p.vec = fits && aligned;
+    p.nblk = tail_grid(p.vec ? N * S / 4 : N * S);
+    return MI355SEG_OK;
+}
+
+// mi355seg_loss_tail_fwd_f32 and mi355seg_loss_tail_fwd_lab_f32 (class_counts: the label form's, null for the one-hot form)
+template <class Target>
+static int tail_forward(const char* what, const float* logits, const typename Target::Elem* target, long long N, int K, long long S,
+                        int voxel_term, int region_term, float gamma, float alpha, float beta, float w_voxel, float w_region,
+                        float* loss, double* terms, double* sums, int64_t* mask, int64_t* counts, double* coef,
+                        int64_t* class_counts, void* ws, size_t ws_bytes, void* stream) {
+    constexpr bool kLabels = Target::kLabels;
+    if (int rc = tail_check_spec(what, N, K, S, voxel_term, region_term, gamma)) return rc;
+    SEG_CHECK_ARG(alpha >= 0.f && beta >= 0.f, "%s: alpha and beta must be >= 0, got %g, %g", what, (double)alpha, (double)beta);
+    SEG_CHECK_ARG(region_term != TAIL_R_TVERSKY || alpha + beta > 0.f, "%s: tversky needs alpha + beta > 0", what);
+    SEG_CHECK_ARG(w_voxel >= 0.f && w_region >= 0.f, "%s: the weights must be >= 0, got %g, %g", what, (double)w_voxel, (double)w_region);
+    SEG_CHECK_ARG(logits && target && loss && terms && sums && mask && counts && coef && (class_counts || !kLabels) && ws, "%s: null pointer", what);
+    SEG_CHECK_ARG(tail_aligned(ws, 8), "%s: the workspace must be 8-byte aligned", what);
+    SEG_CHECK_WS(tail_ws_bytes(N, K, S, kLabels), ws_bytes);
+    TailPath p;
+    if (int rc = tail_path<Target>(what, N, K, S, tail_aligned(logits, 16), target, p)) return rc;      // (the mask goes out in 8-byte stores)
+    hipStream_t st = (hipStream_t)stream;
+    ProfScope ps(PF_LOSS, 0.0, Target::fwd_bytes(K) * N * S, st);
+    if (voxel_term == TAIL_V_FOCAL && gamma == 0.f) voxel_term = TAIL_V_BCE;      // q^0 = 1: the bce code path
+    const int nblk = p.nblk;
+    double* part = (double*)ws;
+    long long* cpart = (long long*)(part + (size_t)nblk * (1 + 5 * K));
+    long long* kpart = kLabels ? cpart + (size_t)nblk * 4 : nullptr;
+    tail_dispatch(p.KT, p.vec, [&](auto kt, auto v) {
+        constexpr int KT = decltype(kt)::value, V = decltype(v)::value;
+        hipLaunchKernelGGL((loss_tail_fwd_kernel<KT, V, Target, (kLabels && KT <= kTailLabFusedCountMaxKT)>), dim3(nblk), dim3(kTailThreads), 0, st,
+                           logits, target, N, K, S, voxel_term, gamma, mask, part, cpart, kpart);
+    });
+    SEG_CHECK_LAUNCH();
+    if constexpr (kLabels) {
+        if (p.KT > kTailLabFusedCountMaxKT) {
+            tail_dispatch_slots(K, [&](auto kt) {
+                hipLaunchKernelGGL(tail_lab_counts_kernel<decltype(kt)::value>, dim3(nblk), dim3(kTailThreads), 0, st, target, (const int64_t*)mask, N * S, K, kpart);
+            });
+            SEG_CHECK_LAUNCH();
+        }
+    }
+    hipLaunchKernelGGL(loss_tail_finalize_kernel<kLabels>, dim3(1), dim3(kTailFinThreads), 0, st, (const double*)part, (const long long*)cpart,
+                       (const long long*)kpart, nblk, K, voxel_term, region_term, (double)alpha, (double)beta,
+                       voxel_term == TAIL_V_NONE ? 0.0 : (double)w_voxel, region_term == TAIL_R_NONE ? 0.0 : (double)w_region,
+                       (double)N * K * S, (double)N * S, loss, terms, sums, counts, coef, class_counts);
+    SEG_CHECK_LAUNCH();
+    return MI355SEG_OK;
+}
+
+// mi355seg_loss_tail_bwd_f32 and mi355seg_loss_tail_bwd_lab_f32
+template <class Target>
+static int tail_backward(const char* what, const float* logits, const typename Target::Elem* target, const double* coef, const float* gscale,
+                         long long N, int K, long long S, int voxel_term, int region_term, float gamma, float* dlogits, void* stream) {
+    if (int rc = tail_check_spec(what, N, K, S, voxel_term, region_term, gamma)) return rc;
+    SEG_CHECK_ARG(logits && target && coef && gscale && dlogits, "%s: null pointer", what);
+    TailPath p;
+    if (int rc = tail_path<Target>(what, N, K, S, tail_aligned(logits, 16) && tail_aligned(dlogits, 16), target, p)) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    ProfScope ps(PF_LOSS, 0.0, Target::bwd_bytes(K) * N * S, st);
+    if (voxel_term == TAIL_V_FOCAL && gamma == 0.f) voxel_term = TAIL_V_BCE;
+    tail_dispatch(p.KT, p.vec, [&](auto kt, auto v) {
+        hipLaunchKernelGGL((loss_tail_bwd_kernel<decltype(kt)::value, decltype(v)::value, Target>), dim3(p.nblk), dim3(kTailThreads), 0, st,
+                           logits, target, coef, gscale, N, K, S, voxel_term, region_term, gamma, dlogits);
+    });
+    SEG_CHECK_LAUNCH();
+    return MI355SEG_OK;
+}
+
 }  // namespace seg
 
 using namespace seg;
 
-// the refusals that forward and backward share; `what` prefixes the message
-#define TAIL_CHECK_SPEC(what)                                                                                                        \
-    do {                                                                                                                             \
-        SEG_CHECK_ARG(K >= 1 && K <= kTailMaxClasses, what ": K must be in 1..%d, got %d", kTailMaxClasses, K);                       \
-        SEG_CHECK_ARG(voxel_term >= TAIL_V_NONE && voxel_term <= TAIL_V_CE, what ": unknown voxel term %d (0 none, 1 bce, 2 focal, 3 ce)", voxel_term); \
-        SEG_CHECK_ARG(region_term >= TAIL_R_NONE && region_term <= TAIL_R_TVERSKY, what ": unknown region term %d (0 none, 1 dice, 2 tversky)", region_term); \
-        SEG_CHECK_ARG(voxel_term != TAIL_V_NONE || region_term != TAIL_R_NONE, what ": both terms absent");                          \
-        SEG_CHECK_ARG(voxel_term != TAIL_V_CE || K >= 2, what ": the ce term needs K >= 2, got %d", K);                               \
-        SEG_CHECK_ARG(gamma == 0.f || (gamma >= 1.f && gamma <= 8.f), what ": gamma must be 0 or in [1, 8], got %g", (double)gamma);  \
-        SEG_CHECK_ARG(N > 0 && S > 0, what ": bad extents N=%lld S=%lld", N, S);                                                     \
-    } while (0)
-
 extern "C" {
 
-size_t mi355seg_loss_tail_ws_bytes(long long N, int K, long long S) {
-    if (N < 1 || S < 1 || K < 1 || K > kTailMaxClasses) return 0;
-    return (size_t)tail_grid(N * S) * ((size_t)(1 + 5 * K) * sizeof(double) + 4 * sizeof(long long));
-}
+size_t mi355seg_loss_tail_ws_bytes(long long N, int K, long long S) { return tail_ws_bytes(N, K, S, false); }
+size_t mi355seg_loss_tail_lab_ws_bytes(long long N, int K, long long S) { return tail_ws_bytes(N, K, S, true); }
 
 int mi355seg_loss_tail_fwd_f32(const float* logits, const float* target, long long N, int K, long long S,
                                int voxel_term, int region_term, float gamma, float alpha, float beta, float w_voxel, float w_region,
                                float* loss, double* terms, double* sums, int64_t* mask, int64_t* counts, double* coef,
                                void* ws, size_t ws_bytes, void* stream) {
-    TAIL_CHECK_SPEC("loss_tail_fwd");
-    SEG_CHECK_ARG(alpha >= 0.f && beta >= 0.f, "loss_tail_fwd: alpha and beta must be >= 0, got %g, %g", (double)alpha, (double)beta);
-    SEG_CHECK_ARG(region_term != TAIL_R_TVERSKY || alpha + beta > 0.f, "loss_tail_fwd: tversky needs alpha + beta > 0");
-    SEG_CHECK_ARG(w_voxel >= 0.f && w_region >= 0.f, "loss_tail_fwd: the weights must be >= 0, got %g, %g", (double)w_voxel, (double)w_region);
-    SEG_CHECK_ARG(logits && target && loss && terms && sums && mask && counts && coef && ws, "loss_tail_fwd: null pointer");
-    SEG_CHECK_ARG(((uintptr_t)ws % 8) == 0, "loss_tail_fwd: the workspace must be 8-byte aligned");
-    SEG_CHECK_WS(mi355seg_loss_tail_ws_bytes(N, K, S), ws_bytes);
-    hipStream_t st = (hipStream_t)stream;
-    ProfScope ps(PF_LOSS, 0.0, (8.0 * K + 8.0) * N * S, st);
-    if (voxel_term == TAIL_V_FOCAL && gamma == 0.f) voxel_term = TAIL_V_BCE;      // q^0 = 1: the bce code path
-    const int KT = tail_capacity(K);
-    const bool vec = KT <= 4 && S % 4 == 0 && tail_aligned16(logits) && tail_aligned16(target);       // (the mask goes out in 8-byte stores)
-    const int nblk = tail_grid(vec ? N * S / 4 : N * S);
-    double* part = (double*)ws;
-    long long* cpart = (long long*)(part + (size_t)nblk * (1 + 5 * K));
-    if (vec) tail_launch_fwd<4>(KT, nblk, st, logits, target, N, K, S, voxel_term, gamma, mask, part, cpart);
-    else tail_launch_fwd<1>(KT, nblk, st, logits, target, N, K, S, voxel_term, gamma, mask, part, cpart);
-    SEG_CHECK_LAUNCH();
-    hipLaunchKernelGGL(loss_tail_finalize_kernel, dim3(1), dim3(kTailFinThreads), 0, st, (const double*)part, (const long long*)cpart, nblk, K,
-                       voxel_term, region_term, (double)alpha, (double)beta, voxel_term == TAIL_V_NONE ? 0.0 : (double)w_voxel,
-                       region_term == TAIL_R_NONE ? 0.0 : (double)w_region, (double)N * K * S, (double)N * S, loss, terms, sums, counts, coef);
-    SEG_CHECK_LAUNCH();
-    return MI355SEG_OK;
+    return tail_forward<OneHotTarget>("loss_tail_fwd", logits, target, N, K, S, voxel_term, region_term, gamma, alpha, beta, w_voxel, w_region,
+                                      loss, terms, sums, mask, counts, coef, nullptr, ws, ws_bytes, stream);
+}
+
+int mi355seg_loss_tail_fwd_lab_f32(const float* logits, const uint8_t* labels, long long N, int K, long long S,
+                                   int voxel_term, int region_term, float gamma, float alpha, float beta, float w_voxel, float w_region,
+                                   float* loss, double* terms, double* sums, int64_t* mask, int64_t* counts, double* coef,
+                                   int64_t* class_counts, void* ws, size_t ws_bytes, void* stream) {
+    return tail_forward<LabelTarget>("loss_tail_fwd_lab", logits, labels, N, K, S, voxel_term, region_term, gamma, alpha, beta, w_voxel, w_region,
+                                     loss, terms, sums, mask, counts, coef, class_counts, ws, ws_bytes, stream);
 }
 
 int mi355seg_loss_tail_bwd_f32(const float* logits, const float* target, const double* coef, const float* gscale,
                                long long N, int K, long long S, int voxel_term, int region_term, float gamma,
                                float* dlogits, void* stream) {
-    TAIL_CHECK_SPEC("loss_tail_bwd");
-    SEG_CHECK_ARG(logits && target && coef && gscale && dlogits, "loss_tail_bwd: null pointer");
-    hipStream_t st = (hipStream_t)stream;
-    ProfScope ps(PF_LOSS, 0.0, 12.0 * K * N * S, st);
-    if (voxel_term == TAIL_V_FOCAL && gamma == 0.f) voxel_term = TAIL_V_BCE;
-    const int KT = tail_capacity(K);
-    const bool vec = KT <= 4 && S % 4 == 0 && tail_aligned16(logits) && tail_aligned16(target) && tail_aligned16(dlogits);
-    const int nblk = tail_grid(vec ? N * S / 4 : N * S);
-    if (vec) tail_launch_bwd<4>(KT, nblk, st, logits, target, coef, gscale, N, K, S, voxel_term, region_term, gamma, dlogits);
-    else tail_launch_bwd<1>(KT, nblk, st, logits, target, coef, gscale, N, K, S, voxel_term, region_term, gamma, dlogits);
-    SEG_CHECK_LAUNCH();
-    return MI355SEG_OK;
+    return tail_backward<OneHotTarget>("loss_tail_bwd", logits, target, coef, gscale, N, K, S, voxel_term, region_term, gamma, dlogits, stream);
+}
+
+int mi355seg_loss_tail_bwd_lab_f32(const float* logits, const uint8_t* labels, const double* coef, const float* gscale,
+                                   long long N, int K, long long S, int voxel_term, int region_term, float gamma,
+                                   float* dlogits, void* stream) {
+    return tail_backward<LabelTarget>("loss_tail_bwd_lab", logits, labels, coef, gscale, N, K, S, voxel_term, region_term, gamma, dlogits, stream);
 }
 
 int mi355seg_labels_u8_f32(const float* gt, long long n, int K, uint8_t* labels_u8, int64_t* bad, void* stream) {
     SEG_CHECK_ARG(K >= 1 && K <= kTailMaxClasses, "labels_u8: K must be in 1..%d, got %d", kTailMaxClasses, K);
     SEG_CHECK_ARG(n > 0, "labels_u8: bad extent n=%lld", n);
     SEG_CHECK_ARG(gt && labels_u8 && bad, "labels_u8: null pointer");
-    SEG_CHECK_ARG(((uintptr_t)bad % 8) == 0, "labels_u8: the counter must be 8-byte aligned");
+    SEG_CHECK_ARG(tail_aligned(bad, 8), "labels_u8: the counter must be 8-byte aligned");
     hipStream_t st = (hipStream_t)stream;
     ProfScope ps(PF_LOSS, 0.0, 5.0 * n, st);
-    const bool vec = n % 4 == 0 && tail_aligned16(gt) && ((uintptr_t)labels_u8 % 4) == 0;
+    const bool vec = n % 4 == 0 && tail_aligned(gt, 16) && tail_aligned(labels_u8, 4);
     if (vec) hipLaunchKernelGGL(labels_u8_kernel<4>, dim3(tail_grid(n / 4)), dim3(kTailThreads), 0, st, gt, n, K, labels_u8, (unsigned long long*)bad);
     else hipLaunchKernelGGL(labels_u8_kernel<1>, dim3(tail_grid(n)), dim3(kTailThreads), 0, st, gt, n, K, labels_u8, (unsigned long long*)bad);
     SEG_CHECK_LAUNCH();
@@ -774,75 +708,9 @@ int mi355seg_onehot_u8_f32(const uint8_t* labels_u8, long long N, int K, long lo
     SEG_CHECK_ARG(labels_u8 && out, "onehot_u8: null pointer");
     hipStream_t st = (hipStream_t)stream;
     ProfScope ps(PF_LOSS, 0.0, (4.0 * K + 1.0) * N * S, st);
-    const bool vec = S % 4 == 0 && tail_aligned16(out) && ((uintptr_t)labels_u8 % 4) == 0;
+    const bool vec = S % 4 == 0 && tail_aligned(out, 16) && tail_aligned(labels_u8, 4);
     if (vec) hipLaunchKernelGGL(onehot_u8_kernel<4>, dim3(tail_grid(N * S / 4)), dim3(kTailThreads), 0, st, labels_u8, N, K, S, out);
     else hipLaunchKernelGGL(onehot_u8_kernel<1>, dim3(tail_grid(N * S)), dim3(kTailThreads), 0, st, labels_u8, N, K, S, out);
-    SEG_CHECK_LAUNCH();
-    return MI355SEG_OK;
-}
-
-size_t mi355seg_loss_tail_lab_ws_bytes(long long N, int K, long long S) {
-    if (N < 1 || S < 1 || K < 1 || K > kTailMaxClasses) return 0;
-    return (size_t)tail_grid(N * S) * ((size_t)(1 + 5 * K) * sizeof(double) + (size_t)(4 + 3 * K) * sizeof(long long));
-}
-
-// the label form takes the path (16-byte or scalar) the one-hot form takes at the same S, or the bits would differ: where S % 4 == 0
-// and K <= 4 a misaligned pointer is refused, not served by the other path
-#define TAIL_LAB_CHECK_ALIGN(what, cond) \
-    SEG_CHECK_ARG(!(tail_capacity(K) <= 4 && S % 4 == 0) || (cond), what ": with S %% 4 == 0 and K <= 4 the float pointers must be 16-byte and labels 4-byte aligned")
-
-int mi355seg_loss_tail_fwd_lab_f32(const float* logits, const uint8_t* labels, long long N, int K, long long S,
-                                   int voxel_term, int region_term, float gamma, float alpha, float beta, float w_voxel, float w_region,
-                                   float* loss, double* terms, double* sums, int64_t* mask, int64_t* counts, double* coef,
-                                   int64_t* class_counts, void* ws, size_t ws_bytes, void* stream) {
-    TAIL_CHECK_SPEC("loss_tail_fwd_lab");
-    SEG_CHECK_ARG(alpha >= 0.f && beta >= 0.f, "loss_tail_fwd_lab: alpha and beta must be >= 0, got %g, %g", (double)alpha, (double)beta);
-    SEG_CHECK_ARG(region_term != TAIL_R_TVERSKY || alpha + beta > 0.f, "loss_tail_fwd_lab: tversky needs alpha + beta > 0");
-    SEG_CHECK_ARG(w_voxel >= 0.f && w_region >= 0.f, "loss_tail_fwd_lab: the weights must be >= 0, got %g, %g", (double)w_voxel, (double)w_region);
-    SEG_CHECK_ARG(logits && labels && loss && terms && sums && mask && counts && coef && class_counts && ws, "loss_tail_fwd_lab: null pointer");
-    SEG_CHECK_ARG(((uintptr_t)ws % 8) == 0, "loss_tail_fwd_lab: the workspace must be 8-byte aligned");
-    SEG_CHECK_WS(mi355seg_loss_tail_lab_ws_bytes(N, K, S), ws_bytes);
-    TAIL_LAB_CHECK_ALIGN("loss_tail_fwd_lab", tail_aligned16(logits) && ((uintptr_t)labels % 4) == 0);
-    hipStream_t st = (hipStream_t)stream;
-    ProfScope ps(PF_LOSS, 0.0, (4.0 * K + 9.0) * N * S, st);
-    if (voxel_term == TAIL_V_FOCAL && gamma == 0.f) voxel_term = TAIL_V_BCE;
-    const int KT = tail_capacity(K);
-    const bool vec = KT <= 4 && S % 4 == 0;
-    const int nblk = tail_grid(vec ? N * S / 4 : N * S);
-    double* part = (double*)ws;
-    long long* cpart = (long long*)(part + (size_t)nblk * (1 + 5 * K));
-    long long* kpart = cpart + (size_t)nblk * 4;
-    if (vec) tail_launch_fwd_lab<4>(KT, nblk, st, logits, labels, N, K, S, voxel_term, gamma, mask, part, cpart, kpart);
-    else tail_launch_fwd_lab<1>(KT, nblk, st, logits, labels, N, K, S, voxel_term, gamma, mask, part, cpart, kpart);
-    SEG_CHECK_LAUNCH();
-    if (KT > kTailLabFusedCountMaxKT) {
-        if (KT <= 4) hipLaunchKernelGGL(tail_lab_counts_kernel<4>, dim3(nblk), dim3(kTailThreads), 0, st, labels, (const int64_t*)mask, N * S, K, kpart);
-        else if (KT == 8) hipLaunchKernelGGL(tail_lab_counts_kernel<8>, dim3(nblk), dim3(kTailThreads), 0, st, labels, (const int64_t*)mask, N * S, K, kpart);
-        else hipLaunchKernelGGL(tail_lab_counts_kernel<16>, dim3(nblk), dim3(kTailThreads), 0, st, labels, (const int64_t*)mask, N * S, K, kpart);
-        SEG_CHECK_LAUNCH();
-    }
-    hipLaunchKernelGGL(loss_tail_finalize_lab_kernel, dim3(1), dim3(kTailFinThreads), 0, st, (const double*)part, (const long long*)cpart,
-                       (const long long*)kpart, nblk, K, voxel_term, region_term, (double)alpha, (double)beta,
-                       voxel_term == TAIL_V_NONE ? 0.0 : (double)w_voxel, region_term == TAIL_R_NONE ? 0.0 : (double)w_region,
-                       (double)N * K * S, (double)N * S, loss, terms, sums, counts, coef, class_counts);
-    SEG_CHECK_LAUNCH();
-    return MI355SEG_OK;
-}
-
-int mi355seg_loss_tail_bwd_lab_f32(const float* logits, const uint8_t* labels, const double* coef, const float* gscale,
-                                   long long N, int K, long long S, int voxel_term, int region_term, float gamma,
-                                   float* dlogits, void* stream) {
-    TAIL_CHECK_SPEC("loss_tail_bwd_lab");
-    SEG_CHECK_ARG(logits && labels && coef && gscale && dlogits, "loss_tail_bwd_lab: null pointer");
-    TAIL_LAB_CHECK_ALIGN("loss_tail_bwd_lab", tail_aligned16(logits) && tail_aligned16(dlogits) && ((uintptr_t)labels % 4) == 0);
-    hipStream_t st = (hipStream_t)stream;
-    ProfScope ps(PF_LOSS, 0.0, (8.0 * K + 1.0) * N * S, st);
-    if (voxel_term == TAIL_V_FOCAL && gamma == 0.f) voxel_term = TAIL_V_BCE;
-    const int KT = tail_capacity(K);
-    const bool vec = KT <= 4 && S % 4 == 0;
-    const int nblk = tail_grid(vec ? N * S / 4 : N * S);
-    if (vec) tail_launch_bwd_lab<4>(KT, nblk, st, logits, labels, coef, gscale, N, K, S, voxel_term, region_term, gamma, dlogits);
-    else tail_launch_bwd_lab<1>(KT, nblk, st, logits, labels, coef, gscale, N, K, S, voxel_term, region_term, gamma, dlogits);
     SEG_CHECK_LAUNCH();
     return MI355SEG_OK;
 }
@@ -857,15 +725,15 @@ int mi355seg_class_counts_i64(const int64_t* gt_labels, const int64_t* pred_labe
     SEG_CHECK_ARG(K >= 1 && K <= kTailMaxClasses, "class_counts: K must be in 1..%d, got %d", kTailMaxClasses, K);
     SEG_CHECK_ARG(n > 0, "class_counts: bad extent n=%lld", n);
     SEG_CHECK_ARG(gt_labels && pred_labels && out && ws, "class_counts: null pointer");
-    SEG_CHECK_ARG(((uintptr_t)ws % 8) == 0, "class_counts: the workspace must be 8-byte aligned");
+    SEG_CHECK_ARG(tail_aligned(ws, 8), "class_counts: the workspace must be 8-byte aligned");
     SEG_CHECK_WS(mi355seg_class_counts_ws_bytes(n, K), ws_bytes);
     hipStream_t st = (hipStream_t)stream;
     ProfScope ps(PF_LOSS, 0.0, 16.0 * n, st);
     const int nblk = tail_grid(n);
     long long* part = (long long*)ws;
-    if (K <= 4) hipLaunchKernelGGL(class_counts_kernel<4>, dim3(nblk), dim3(kTailThreads), 0, st, gt_labels, pred_labels, n, K, part);
-    else if (K <= 8) hipLaunchKernelGGL(class_counts_kernel<8>, dim3(nblk), dim3(kTailThreads), 0, st, gt_labels, pred_labels, n, K, part);
-    else hipLaunchKernelGGL(class_counts_kernel<16>, dim3(nblk), dim3(kTailThreads), 0, st, gt_labels, pred_labels, n, K, part);
+    tail_dispatch_slots(K, [&](auto kt) {
+        hipLaunchKernelGGL(class_counts_kernel<decltype(kt)::value>, dim3(nblk), dim3(kTailThreads), 0, st, gt_labels, pred_labels, n, K, part);
+    });
     SEG_CHECK_LAUNCH();
     launch_sums_finalize<1>((const long long*)part, nblk, (long long*)out, st, (unsigned)(3 * K));
     SEG_CHECK_LAUNCH();

@@ -2160,54 +2160,64 @@ class LossSpec(collections.namedtuple("LossSpec", "voxel region gamma alpha beta
 class _LossTail(Function):
     """The fused tail for a LossSpec: (loss, mask, counts, terms, sums) from one pass over logits and target plus a one-block
     finalise; the backward is one pass.  The coefficients of the backward stay on the device (coef), so the pair is capturable
-    in a HIP graph exactly like _BCEArgmaxDice."""
+    in a HIP graph exactly like _BCEArgmaxDice.  ``labels``: the target is a uint8 label map [N,...] in place of the float one-hot
+    [N,K,...] (the *_lab entry points), and class_counts int64 [K,3] (tp, pred, gt) is a sixth output."""
 
     @staticmethod
-    def forward(ctx, logits, target, spec):
-        _require_cuda(logits, "loss_tail input")
-        logits, target = aligned_contiguous(logits), aligned_contiguous(target.to(torch.float32))
-        if logits.shape != target.shape:
+    def forward(ctx, logits, target, spec, labels):
+        what, form = ("loss_tail_labels", "_lab") if labels else ("loss_tail", "")
+        _require_cuda(logits, f"{what} input")
+        logits = aligned_contiguous(logits)
+        target = _checked_label_map(target, what) if labels else aligned_contiguous(target.to(torch.float32))
+        if not labels and logits.shape != target.shape:
             raise ValueError(f"Target size ({tuple(target.shape)}) must be the same as input size ({tuple(logits.shape)})")
         if logits.dim() < 3:
-            raise Mi355SegError(f"loss_tail: expected [N,K,...], got {tuple(logits.shape)}")
+            raise Mi355SegError(f"{what}: expected [N,K,...], got {tuple(logits.shape)}")
+        if labels and (logits.shape[0],) + tuple(logits.shape[2:]) != tuple(target.shape):
+            raise ValueError(f"Label size ({tuple(target.shape)}) must be the input size ({tuple(logits.shape)}) without its channels")
         N, K = logits.shape[0], logits.shape[1]
         S = logits[0, 0].numel()
         dev = logits.device
         L = lib()
-        ws = workspace(L.query("mi355seg_loss_tail_ws_bytes", N, K, S), dev)
+        ws = workspace(L.query(f"mi355seg_loss_tail{form}_ws_bytes", N, K, S), dev)
         loss = torch.empty((), dtype=torch.float32, device=dev)
         mask = torch.empty((N, 1) + tuple(logits.shape[2:]), dtype=torch.int64, device=dev)
         counts = torch.empty(4, dtype=torch.int64, device=dev)
         terms = torch.empty(2, dtype=torch.float64, device=dev)
         sums = torch.empty((K, 5), dtype=torch.float64, device=dev)
+        extra = (torch.empty((K, 3), dtype=torch.int64, device=dev),) if labels else ()
         coef = torch.empty(1 + 2 * MAX_LOSS_CLASSES, dtype=torch.float64, device=dev)
         args = (LOSS_VOXEL_TERMS[spec.voxel], LOSS_REGION_TERMS[spec.region], spec.gamma)
-        L.call("mi355seg_loss_tail_fwd_f32", _p(logits), _p(target), N, K, S, *args, spec.alpha, spec.beta, spec.w_voxel, spec.w_region,
-               _p(loss), _p(terms), _p(sums), _p(mask), _p(counts), _p(coef), _p(ws), ws.numel(), _stream())
+        L.call(f"mi355seg_loss_tail_fwd{form}_f32", _p(logits), _p(target), N, K, S, *args, spec.alpha, spec.beta, spec.w_voxel, spec.w_region,
+               _p(loss), _p(terms), _p(sums), _p(mask), _p(counts), _p(coef), *(_p(t) for t in extra), _p(ws), ws.numel(), _stream())
         ctx.save_for_backward(logits, target, coef)
-        ctx.args = args
-        ctx.mark_non_differentiable(mask, counts, terms, sums)
+        ctx.args, ctx.form = args, form
+        ctx.mark_non_differentiable(mask, counts, terms, sums, *extra)
         ctx.set_materialize_grads(False)         # (or autograd zero-fills a gradient for each of them, the int64 mask included, per backward)
-        return loss, mask, counts, terms, sums
+        return (loss, mask, counts, terms, sums) + extra
 
     @staticmethod
-    def backward(ctx, g, _gmask, _gcounts, _gterms, _gsums):
+    def backward(ctx, g, *_):
         if g is None:
-            return None, None, None
+            return None, None, None, None
         logits, target, coef = ctx.saved_tensors
         g = g.contiguous().to(torch.float32)
         N, K = logits.shape[0], logits.shape[1]
         d = torch.empty_like(logits)
-        lib().call("mi355seg_loss_tail_bwd_f32", _p(logits), _p(target), _p(coef), _p(g), N, K, logits[0, 0].numel(), *ctx.args, _p(d), _stream())
-        return d, None, None
+        lib().call(f"mi355seg_loss_tail_bwd{ctx.form}_f32", _p(logits), _p(target), _p(coef), _p(g), N, K, logits[0, 0].numel(), *ctx.args, _p(d), _stream())
+        return d, None, None, None
+
+
+def _loss_tail(logits, target, spec, labels):
+    if not isinstance(spec, LossSpec):
+        raise TypeError(f"{'loss_tail_labels' if labels else 'loss_tail'}: spec must be a functional.LossSpec, got {type(spec).__name__}")
+    return _LossTail.apply(logits, target, spec.checked(), labels)
 
 
 def loss_tail_full(logits, target, spec):
     """loss_tail plus the per-class sums: (loss, mask, counts, terms, sums fp64 [K,5]) -- sums[k] = (sum p t, sum p, sum t, sum p^2,
     sum t^2) with p = sigmoid(logits[:, k]), what dice_sums gives for class k."""
-    if not isinstance(spec, LossSpec):
-        raise TypeError(f"loss_tail: spec must be a functional.LossSpec, got {type(spec).__name__}")
-    return _LossTail.apply(logits, target, spec.checked())
+    return _loss_tail(logits, target, spec, False)
 
 
 def loss_tail(logits, target, spec):
@@ -2267,55 +2277,9 @@ def one_hot_labels(labels, K):
     return out
 
 
-class _LossTailLabels(Function):
-    """_LossTail with uint8 labels [N,...] in place of the one-hot target, plus class_counts int64 [K,3] (tp, pred, gt)."""
-
-    @staticmethod
-    def forward(ctx, logits, labels, spec):
-        _require_cuda(logits, "loss_tail_labels input")
-        logits, labels = aligned_contiguous(logits), _checked_label_map(labels, "loss_tail_labels")
-        if logits.dim() < 3:
-            raise Mi355SegError(f"loss_tail_labels: expected [N,K,...], got {tuple(logits.shape)}")
-        if (logits.shape[0],) + tuple(logits.shape[2:]) != tuple(labels.shape):
-            raise ValueError(f"Label size ({tuple(labels.shape)}) must be the input size ({tuple(logits.shape)}) without its channels")
-        N, K = logits.shape[0], logits.shape[1]
-        S = logits[0, 0].numel()
-        dev = logits.device
-        L = lib()
-        ws = workspace(L.query("mi355seg_loss_tail_lab_ws_bytes", N, K, S), dev)
-        loss = torch.empty((), dtype=torch.float32, device=dev)
-        mask = torch.empty((N, 1) + tuple(logits.shape[2:]), dtype=torch.int64, device=dev)
-        counts = torch.empty(4, dtype=torch.int64, device=dev)
-        terms = torch.empty(2, dtype=torch.float64, device=dev)
-        sums = torch.empty((K, 5), dtype=torch.float64, device=dev)
-        class_counts = torch.empty((K, 3), dtype=torch.int64, device=dev)
-        coef = torch.empty(1 + 2 * MAX_LOSS_CLASSES, dtype=torch.float64, device=dev)
-        args = (LOSS_VOXEL_TERMS[spec.voxel], LOSS_REGION_TERMS[spec.region], spec.gamma)
-        L.call("mi355seg_loss_tail_fwd_lab_f32", _p(logits), _p(labels), N, K, S, *args, spec.alpha, spec.beta, spec.w_voxel, spec.w_region,
-               _p(loss), _p(terms), _p(sums), _p(mask), _p(counts), _p(coef), _p(class_counts), _p(ws), ws.numel(), _stream())
-        ctx.save_for_backward(logits, labels, coef)
-        ctx.args = args
-        ctx.mark_non_differentiable(mask, counts, terms, sums, class_counts)
-        ctx.set_materialize_grads(False)
-        return loss, mask, counts, terms, sums, class_counts
-
-    @staticmethod
-    def backward(ctx, g, _gmask, _gcounts, _gterms, _gsums, _gclass):
-        if g is None:
-            return None, None, None
-        logits, labels, coef = ctx.saved_tensors
-        g = g.contiguous().to(torch.float32)
-        N, K = logits.shape[0], logits.shape[1]
-        d = torch.empty_like(logits)
-        lib().call("mi355seg_loss_tail_bwd_lab_f32", _p(logits), _p(labels), _p(coef), _p(g), N, K, logits[0, 0].numel(), *ctx.args, _p(d), _stream())
-        return d, None, None
-
-
 def loss_tail_labels_full(logits, labels, spec):
     """loss_tail_labels plus the per-class sums: (loss, mask, counts, terms, sums fp64 [K,5], class_counts int64 [K,3])."""
-    if not isinstance(spec, LossSpec):
-        raise TypeError(f"loss_tail_labels: spec must be a functional.LossSpec, got {type(spec).__name__}")
-    return _LossTailLabels.apply(logits, labels, spec.checked())
+    return _loss_tail(logits, labels, spec, True)
 
 
 def loss_tail_labels(logits, labels, spec):

@@ -10,6 +10,7 @@ confusion matrix, exactly.  Then the layers above: train_step / GraphedTrainStep
 predict.py."""
 import csv
 import ctypes
+import hashlib
 import json
 import os
 import subprocess
@@ -218,6 +219,86 @@ def test_functional_label_tail_equals_the_one_hot_tail_and_differentiates(seg):
         F.loss_tail_labels(x, lab[:, :-1], spec)
     with pytest.raises(seg.Mi355SegError, match="labels must be uint8"):
         F.loss_tail_labels(x, lab.to(I64), spec)
+
+
+# ----------------------------------------------------------------------------- recorded bits (tests/golden/loss_tail_pins.json)
+def _pin(t):
+    """SHA-256 of a tensor's bytes, every NaN written as the one quiet NaN first: NaN positions are pinned, a NaN's sign is not (the
+    freedom _same_bits documents)"""
+    a = t.detach().cpu().contiguous().numpy().reshape(-1)
+    if a.dtype.kind == "f":
+        nan = np.isnan(a)
+        a = a.view({4: np.uint32, 8: np.uint64}[a.itemsize]).copy()
+        a[nan] = {4: 0x7FC00000, 8: 0x7FF8000000000000}[a.itemsize]
+    return hashlib.sha256(a.tobytes()).hexdigest()
+
+
+def _pin_inputs(*ts):
+    h = hashlib.sha256()
+    for t in ts:
+        h.update(t.detach().cpu().contiguous().numpy().tobytes())
+    return h.hexdigest()
+
+
+def _sid(shape):
+    return "x".join(str(v) for v in shape)
+
+
+def loss_tail_pin_digests(F):
+    """case -> {"input", and one entry per output}: SHA-256 of the input bytes and of each output's bytes, of every kernel family of
+    csrc/loss_tail.hip through the C-ABI (_raw: the workspace full of 0xff): {loss, terms, sums, mask, counts, coef, dlogits} of
+    both forms (class_counts too for the label form) for every mode x K x {16-byte path, scalar path, scalar path with NaN and +-inf
+    columns}, labels of 255, the grid-stride loop's second trip, and the conversion and counting kernels."""
+    import mi355seg as seg
+    out = {}
+
+    def tail(K, shape, mode, seed, tag="", **kw):
+        x, lab = _case(K, shape, seed, **kw)
+        for form, target in (("labels", lab), ("onehot", F.one_hot_labels(lab, K))):
+            o = _raw(seg, x, target, mode, form == "labels")
+            out[f"tail {form} {mode} K{K} {_sid(shape)}{tag}"] = {"input": _pin_inputs(x, target), **{k: _pin(v) for k, v in o.items()}}
+
+    for mode in MODES:
+        for K in CLASSES:
+            if mode in ("ce", "dice_ce") and K == 1:
+                continue                                         # (refused)
+            seed = 100 * K + len(mode)
+            tail(K, VEC_SHAPE, mode, seed)
+            tail(K, ODD_SHAPE, mode, seed)
+            tail(K, ODD_SHAPE, mode, seed, " special", special=True)
+    for K in (2, 4, 8, 16):
+        for shape in (VEC_SHAPE, ODD_SHAPE):
+            tail(K, shape, "dice_ce", 7 * K, " out_of_range", out_of_range=True)
+    for mode in ("dice_ce", "dice_focal"):
+        tail(3, BIG_SHAPE, mode, 9)
+    for shape in ((2, 1, 8, 12, 16), (3, 1, 1, 1, 1031)):         # labels_u8 and one_hot_labels: valid labels, and values that are none
+        gt = torch.randint(0, 4, shape, generator=_gen(sum(shape))).float()
+        flat = gt.view(-1)
+        for i, v in enumerate((0.5, -1.0, 4.0, float("nan"), float("inf"), 3.0001, -0.25, 255.0, 1e9, float("-inf"))):
+            flat[(i * 13 + 40) % flat.numel()] = v
+        lab, bad = F.labels_u8(gt.cuda(), 4)
+        out[f"convert {_sid(shape)}"] = {"input": _pin_inputs(gt), "labels": _pin(lab), "bad": _pin(bad),
+                                         "one_hot_4": _pin(F.one_hot_labels(lab, 4)), "one_hot_16": _pin(F.one_hot_labels(lab, 16))}
+    g = _gen(4)
+    gt, pr = torch.randint(-1, 17, (600001,), generator=g), torch.randint(0, 16, (600001,), generator=g)      # several blocks, a second trip
+    for K in (4, 8, 16):
+        out[f"class_counts K{K} 600001"] = {"input": _pin_inputs(gt, pr), "class_counts": _pin(F.class_counts(gt.cuda(), pr.cuda(), K))}
+    torch.cuda.synchronize()
+    return out
+
+
+def test_loss_tail_bits_are_the_parents(seg):
+    """tests/golden/loss_tail_pins.json (tests/golden/make_loss_tail_pins.py): every output of loss_tail.hip's kernels on the cases of
+    loss_tail_pin_digests, recorded on the MI355X before the one-hot and the label form came to be two instantiations of one text --
+    also the bits against which the modes that the unfused criterions pin only to a tolerance could move in both forms alike."""
+    with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "loss_tail_pins.json")) as fh:
+        want = json.load(fh)["loss_tail"]
+    got = loss_tail_pin_digests(seg.functional)
+    assert sorted(got) == sorted(want), f"the cases changed: {sorted(set(got) ^ set(want))}"
+    for name in sorted(got):
+        assert got[name]["input"] == want[name]["input"], f"{name}: torch drew other inputs (the recorded digests are of other bytes)"
+    bad = [(name, k) for name in sorted(got) for k in sorted(set(got[name]) | set(want[name])) if got[name].get(k) != want[name].get(k)]
+    assert not bad, f"{len(bad)} outputs differ from the recorded bits: {bad[:12]}"
 
 
 # ----------------------------------------------------------------------------- conversion kernels
