@@ -267,6 +267,20 @@ def _(mask, connectivity=26):
             torch.empty(4, dtype=torch.int64, device=mask.device))
 
 
+@torch.library.custom_op("mi355seg::connected_components_by_class", mutates_args=())
+def connected_components_by_class(mask: Tensor, connectivity: int = 26) -> Tuple[Tensor, Tensor, Tensor]:
+    """Class-aware connected components of an int64 label volume (voxels join only within one value 1..255; every class in one
+    labelling call): labels int32 [D, H, W], sizes int32 [D*H*W], info int64[8] (slot 4: voxels outside 0..255, which raise)."""
+    return F.connected_components_by_class(mask, connectivity)
+
+
+@connected_components_by_class.register_fake
+def _(mask, connectivity=26):
+    shape = tuple(mask.shape[-3:])
+    return (torch.empty(shape, dtype=torch.int32, device=mask.device), torch.empty(shape[0] * shape[1] * shape[2], dtype=torch.int32, device=mask.device),
+            torch.empty(8, dtype=torch.int64, device=mask.device))
+
+
 @torch.library.custom_op("mi355seg::confusion_counts", mutates_args=())
 def confusion_counts(gt: Tensor, pred: Tensor) -> Tensor:
     """utils/metric.py:34-55 on the device: int64[8] = the four counters of dice_counts, then tp, fp, fn, tn."""
@@ -548,5 +562,5 @@ torch.library.register_autograd("mi355seg::cat_channels", lambda ctx, g: (g[...,
 
 OPS = ["conv3d", "conv3d_dgrad", "conv3d_wgrad", "conv_transpose3d_k2s2", "conv_transpose3d_k2s2_backward", "max_pool3d_2x",
        "max_pool3d_2x_backward", "upsample_nearest_2x", "upsample_nearest_2x_backward", "bce_argmax_dice", "bce_with_logits_backward",
-       "dice_counts", "confusion_counts", "hd95", "connected_components", "to_channels_last", "to_channels_first", "norm_stats", "norm_apply_act", "norm_act_backward", "conv_bn_act",
+       "dice_counts", "confusion_counts", "hd95", "connected_components", "connected_components_by_class", "to_channels_last", "to_channels_first", "norm_stats", "norm_apply_act", "norm_act_backward", "conv_bn_act",
        "conv_bn_act_backward", "activation", "activation_backward", "cat_channels"]

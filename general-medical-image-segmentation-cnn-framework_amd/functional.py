@@ -2077,6 +2077,179 @@ def filter_components(mask, min_voxels=0, keep_largest=0, connectivity=26, inpla
     return out.reshape(mask.shape), {"components": comps, "kept": kept, "voxels_removed": gone, "largest": largest}
 
 
+MAX_COMPONENT_CLASS = 255
+
+
+def connected_components_by_class(mask, connectivity=26):
+    """Class-aware connected components of an int64 label volume on the GPU: two voxels are joined only when they are neighbours
+    and carry the same value 1..255 (``scipy.ndimage.label(mask == k, ...)`` for every k != 0 that occurs), all classes in ONE
+    labelling call -> (labels int32 [D, H, W], sizes int32 [D*H*W], info int64[8]).  labels and sizes as ``connected_components``
+    (a component belongs to one class: the mask value at its first voxel); info[:4] as there over all classes, info[4] = voxels
+    outside 0..255, which raise here (that one integer is read back)."""
+    connectivity = _connectivity(connectivity, "connected_components_by_class")
+    mask = _label_volume(mask, "connected_components_by_class")
+    D, H, W = mask.shape
+    L = lib()
+    need = L.query("mi355seg_components_classes_ws_bytes", D, H, W)
+    if need == 0:
+        raise Mi355SegError(f"connected_components_by_class: a volume of {D * H * W} voxels is refused (labels are int32: at most 2^31 - 2)")
+    ws = workspace(need, mask.device)
+    labels = torch.empty((D, H, W), dtype=torch.int32, device=mask.device)
+    sizes = torch.empty(D * H * W, dtype=torch.int32, device=mask.device)
+    info = torch.empty(8, dtype=torch.int64, device=mask.device)
+    L.call("mi355seg_components_label_classes_i64", _p(mask), D, H, W, connectivity, _p(labels), _p(sizes), _p(info), _p(ws), ws.numel(), _stream())
+    bad = int(info[4])
+    if bad:
+        raise Mi355SegError(f"connected_components_by_class: {bad} voxels hold values outside 0..{MAX_COMPONENT_CLASS}")
+    return labels, sizes, info
+
+
+def component_table(mask, labels, sizes, info):
+    """The compact table of a labelling (``connected_components`` or ``connected_components_by_class`` of ``mask``) and consecutive
+    labels -> (labels_consecutive int32 [D, H, W], first int32[n], size int32[n], cls int64[n]).  Components are ranked by their
+    first voxel in raster order, which is the order scipy.ndimage.label numbers them in: labels_consecutive is 1..n (0 on
+    background), first / size / cls[k] the first voxel's raster index, the voxel count and the mask value at the first voxel of the
+    component labelled k + 1.  Nothing but n = info[1] goes to the host."""
+    vol = _label_volume(mask, "component_table")
+    for t, name, dt in ((labels, "labels", torch.int32), (sizes, "sizes", torch.int32), (info, "info", torch.int64)):
+        if not torch.is_tensor(t) or not t.is_cuda or t.dtype != dt or t.device != vol.device:
+            raise Mi355SegError(f"component_table: {name} must be a {dt} tensor on the mask's GPU")
+    if labels.numel() != vol.numel() or sizes.numel() != vol.numel() or info.numel() < 4:
+        raise Mi355SegError(f"component_table: the mask holds {vol.numel()} voxels, labels {labels.numel()}, sizes {sizes.numel()}, info {info.numel()} entries")
+    labels, sizes = aligned_contiguous(labels), aligned_contiguous(sizes)
+    L = lib()
+    n = int(info[1])
+    ws = workspace(L.query("mi355seg_components_table_ws_bytes", vol.numel()), vol.device)
+    lc = torch.empty(tuple(vol.shape), dtype=torch.int32, device=vol.device)
+    first = torch.empty(n, dtype=torch.int32, device=vol.device)
+    size = torch.empty(n, dtype=torch.int32, device=vol.device)
+    cls = torch.empty(n, dtype=torch.int64, device=vol.device)
+    L.call("mi355seg_components_table_i64", _p(vol), _p(labels), _p(sizes), vol.numel(), n, _p(lc), _p(first) if n else None,
+           _p(size) if n else None, _p(cls) if n else None, _p(ws), ws.numel(), _stream())
+    return lc, first, size, cls
+
+
+def _per_class(v, name, what, top=None):
+    """an int (every class) or a {class: value} dict of non-negative ints -> the same, checked"""
+    def ok(x, hi):
+        return not isinstance(x, bool) and isinstance(x, int) and 0 <= x and (hi is None or x <= hi)
+    if isinstance(v, dict):
+        for k, x in v.items():
+            if not ok(k, None) or k == 0:
+                raise Mi355SegError(f"{what}: {name} names class {k!r}; classes are positive integers")
+            if not ok(x, top):
+                raise Mi355SegError(f"{what}: {name}[{k}] must be " + (f"an integer in 0..{top}" if top is not None else "a non-negative integer") + f", got {x!r}")
+        return dict(v)
+    if not ok(v, top):
+        raise Mi355SegError(f"{what}: {name} must be " + (f"an integer in 0..{top}" if top is not None else "a non-negative integer") +
+                            f" or a {{class: value}} dict, got {v!r}")
+    return v
+
+
+def _per_component(v, cls):
+    """the per-class argument spread over the components of the table: int64 [n]"""
+    if not isinstance(v, dict):
+        return torch.full_like(cls, v)
+    out = torch.zeros_like(cls)
+    for k, x in v.items():
+        out = torch.where(cls == k, torch.full_like(cls, x), out)
+    return out
+
+
+def select_components_by_class(cls, size, min_voxels=0, keep_largest=0):
+    """Which components of a compact table stay, class by class: (cls[n], size[n]) in rank order (``component_table``) -> bool
+    keep[n].  ``min_voxels`` and ``keep_largest`` are each an int (every class) or a ``{class: value}`` dict (a class that is absent:
+    0); ``keep_largest`` lies in 0..MAX_KEEP_LARGEST.  Within a class: components below ``min_voxels`` go; then, with ``keep_largest``
+    = K > 0, the K largest of the rest stay (equal sizes: the smaller rank), all of them where fewer remain.  Plain tensor code on
+    the table's device, CPU tensors included."""
+    what = "select_components_by_class"
+    min_voxels, keep_largest = _per_class(min_voxels, "min_voxels", what), _per_class(keep_largest, "keep_largest", what, MAX_KEEP_LARGEST)
+    if not torch.is_tensor(cls) or not torch.is_tensor(size) or cls.is_floating_point() or size.is_floating_point():
+        raise Mi355SegError(f"{what}: cls and size must be integer tensors")
+    if cls.numel() != size.numel():
+        raise Mi355SegError(f"{what}: {cls.numel()} classes and {size.numel()} sizes")
+    cls, size = cls.reshape(-1).to(torch.int64), size.reshape(-1).to(torch.int64)
+    n = cls.numel()
+    big = size >= _per_component(min_voxels, cls)
+    top = _per_component(keep_largest, cls)
+    # the components of each class side by side, the ones that pass min_voxels first, larger first, equal sizes by rank: three
+    # stable sorts, the last key first
+    order = torch.sort(size, descending=True, stable=True).indices
+    order = order[torch.sort((~big[order]).to(torch.int8), stable=True).indices]
+    order = order[torch.sort(cls[order], stable=True).indices]
+    pos = torch.arange(n, dtype=torch.int64, device=cls.device)
+    c = cls[order]
+    starts = torch.ones(n, dtype=torch.bool, device=cls.device)
+    starts[1:] = c[1:] != c[:-1]
+    place = pos - torch.cummax(torch.where(starts, pos, torch.zeros_like(pos)), 0).values if n else pos      # place within the class
+    stay = big[order] & ((top[order] == 0) | (place < top[order]))
+    keep = torch.zeros(n, dtype=torch.bool, device=cls.device)
+    keep[order] = stay
+    return keep
+
+
+def class_component_stats(cls, size, keep, classes=()):
+    """{class: {components, kept, voxels_removed, largest}} from the n-entry table and its keep flags, for every class of the
+    table and of ``classes``; one [4, 256] copy to the host (and the table's smallest and largest class, which must lie in 0..255)."""
+    K = MAX_COMPONENT_CLASS + 1
+    cls, size, keep = cls.reshape(-1).to(torch.int64), size.reshape(-1).to(torch.int64), keep.reshape(-1).to(torch.int64)
+    if cls.numel():                                  # (a table of the binary labelling may hold any value at a root)
+        lo, hi = torch.stack([cls.min(), cls.max()]).tolist()
+        if lo < 0 or hi > MAX_COMPONENT_CLASS:
+            raise Mi355SegError(f"class_component_stats: classes lie in 0..{MAX_COMPONENT_CLASS}, the table holds {lo}..{hi}")
+    zero = torch.zeros(K, dtype=torch.int64, device=cls.device)
+    rows = torch.stack([zero.index_add(0, cls, torch.ones_like(cls)), zero.index_add(0, cls, keep),
+                        zero.index_add(0, cls, size * (1 - keep)), zero.scatter_reduce(0, cls, size, "amax")]).tolist()
+    present = sorted({k for k in range(K) if rows[0][k]} | {int(k) for k in classes})
+    return {k: {"components": rows[0][k], "kept": rows[1][k], "voxels_removed": rows[2][k], "largest": rows[3][k]} for k in present}
+
+
+def filter_components_by_class(mask, min_voxels=0, keep_largest=0, connectivity=26, inplace=False):
+    """Connected-component clean-up of a multi-class int64 label volume on the GPU, class by class -> (mask_out, stats).  Components
+    are those of ``connected_components_by_class``; ``min_voxels`` / ``keep_largest`` as ``select_components_by_class`` (an int for
+    every class or a ``{class: value}`` dict).  Kept voxels keep their class value.  stats[k] = {components, kept, voxels_removed,
+    largest} for every class in the arguments or the mask, from the n-entry table.  With both thresholds 0 the mask itself is
+    returned; ``inplace`` writes the result into ``mask`` (contiguous) and returns it."""
+    what = "filter_components_by_class"
+    min_voxels, keep_largest = _per_class(min_voxels, "min_voxels", what), _per_class(keep_largest, "keep_largest", what, MAX_KEEP_LARGEST)
+    for arg in (min_voxels, keep_largest):
+        if isinstance(arg, dict) and any(k > MAX_COMPONENT_CLASS for k in arg):
+            raise Mi355SegError(f"{what}: classes lie in 1..{MAX_COMPONENT_CLASS}, got {sorted(arg)}")
+    vol = _label_volume(mask, what)
+    if inplace and vol.data_ptr() != mask.data_ptr():
+        raise Mi355SegError(f"{what}: inplace needs a contiguous mask")
+    labels, sizes, info = connected_components_by_class(vol, connectivity)
+    lc, first, size, cls = component_table(vol, labels, sizes, info)
+    keep = select_components_by_class(cls, size, min_voxels, keep_largest)
+    named = {k for arg in (min_voxels, keep_largest) if isinstance(arg, dict) for k in arg}
+    stats = class_component_stats(cls, size, keep, named)
+    if not any(any(arg.values()) if isinstance(arg, dict) else arg for arg in (min_voxels, keep_largest)):
+        return mask, stats
+    return filter_by_component_table(mask, lc, keep, inplace=inplace)[0], stats
+
+
+def filter_by_component_table(mask, labels_consecutive, keep, inplace=False):
+    """``out[v] = (lc[v] == 0 or keep[lc[v] - 1]) ? mask[v] : 0`` on the GPU with the consecutive labels of ``component_table`` and one
+    flag per component (bool or uint8 [n]) -> (mask_out, removed int64[1] on the device: the voxels set to 0).  Nothing goes to the
+    host.  ``inplace`` writes into ``mask`` (contiguous) and returns it."""
+    what = "filter_by_component_table"
+    vol = _label_volume(mask, what)
+    lc = labels_consecutive
+    if not torch.is_tensor(lc) or not lc.is_cuda or lc.dtype != torch.int32 or lc.numel() != vol.numel():
+        raise Mi355SegError(f"{what}: labels_consecutive must be an int32 GPU tensor of the mask's {vol.numel()} voxels")
+    if not torch.is_tensor(keep) or not keep.is_cuda or keep.dtype not in (torch.bool, torch.uint8) or keep.dim() != 1:
+        raise Mi355SegError(f"{what}: keep must be a bool or uint8 GPU tensor [n]")
+    if inplace and vol.data_ptr() != mask.data_ptr():
+        raise Mi355SegError(f"{what}: inplace needs a contiguous mask")
+    lc = aligned_contiguous(lc)
+    out = vol if inplace else torch.empty_like(vol)
+    removed = torch.empty(1, dtype=torch.int64, device=vol.device)
+    flags = keep.to(torch.uint8).contiguous()
+    lib().call("mi355seg_components_filter_table_i64", _p(vol), _p(lc), _p(flags) if flags.numel() else None, flags.numel(), vol.numel(),
+               _p(out), _p(removed), _stream())
+    return out.reshape(mask.shape), removed
+
+
 class _BCEArgmaxDice(Function):
     """train.py:204,209,221 in ONE pass over the logits: BCE-with-logits mean loss (differentiable w.r.t. the logits),
     pred.argmax(1, keepdim) and the four integer Dice counters of metric(gt.argmax, mask)."""

@@ -17,6 +17,12 @@ the device (csrc/components.hip) before it is saved and graded: components below
 ``config.connectivity`` = 6 | 18 | 26 (default 26).  components.csv (``file, components, kept, voxels_removed, largest``) is then
 written beside metrics.csv.  Without the two keys nothing of this runs and no file is added.
 
+``config.class_keep_largest`` and / or ``config.class_min_voxels`` (optional, with ``config.multiclass=true``) are the per-class form:
+components are connected voxels of ONE class (functional.filter_components_by_class, every class in one labelling call), and each
+key is one integer for every foreground class or ``k:v,k:v`` (``config.class_keep_largest=1:1,2:1,3:2``: one liver, one spleen, two
+kidneys; a class that is not named is left alone; a single pair is written ``2:1,`` or ``{2: 1}``, as YAML reads ``2:1`` as 121).
+components.csv is then ``file, class, components, kept, voxels_removed, largest``, one row per file and foreground class.
+
 ``config.overlap_mode=crop|average|hann|gaussian`` (optional, default crop) chooses how overlapping patches are aggregated.  ``crop`` is
 the reference's mode: argmax labels, each voxel from one patch.  The other three blend the patches' class PROBABILITIES with a window
 weight on the device (csrc/aggregate.hip) and take the argmax afterwards -- torchio's GridAggregator modes 'average' and 'hann', and an
@@ -330,6 +336,61 @@ def parse_postprocess(config):
     return keep, small, int(c)
 
 
+CLASS_COMPONENT_COLUMNS = ("class",) + COMPONENT_COLUMNS
+
+
+def parse_class_postprocess(config, multiclass):
+    """``config.class_keep_largest`` / ``config.class_min_voxels`` / ``config.connectivity`` -> (keep_largest, min_voxels,
+    connectivity), or None when neither of the first two keys is set: no clean-up.  A value is one integer (every foreground class)
+    or ``k:v,k:v`` (a class that is not named: 0; a single pair with a trailing comma, ``2:1,``, or as ``{2: 1}``: YAML reads ``2:1`` as
+    the base-60 number 121), returned as an int or a {class: value} dict.  ``multiclass`` is parse_predict_multiclass's K: the keys
+    need ``config.multiclass=true`` and classes in 1..K-1."""
+    def per_class(key, top=None):
+        v = getattr(config, key, None)
+        if _absent(v):
+            return 0
+        bad = ValueError(f"config.{key} must be " + (f"an integer in 0..{top}" if top is not None else "a non-negative integer") +
+                         f" or class:value pairs k:v,k:v, got {v!r} (YAML reads a single pair such as 2:1 as a base-60 number: write it "
+                         f"with a trailing comma, 2:1, or as {{2: 1}})")
+        if isinstance(v, dict):                          # {2: 1} on the command line arrives as a mapping
+            v = ",".join(f"{k}:{x}" for k, x in v.items()) + ","
+        if isinstance(v, bool) or not isinstance(v, (int, str)):
+            raise bad
+        if multiclass is None and str(v).strip() != "0":
+            raise ValueError(f"config.{key} needs config.multiclass=true (config.keep_largest / config.min_component_voxels clean one foreground class)")
+        def number(t):
+            if not t.strip().isdigit() or (top is not None and int(t) > top):
+                raise bad
+            return int(t)
+        if isinstance(v, int) or ":" not in v:
+            return number(str(v))
+        out = {}
+        body = v.strip()
+        for pair in (body[:-1] if body.endswith(",") else body).split(","):          # (one trailing comma: the single pair's form)
+            k, sep, x = pair.partition(":")
+            if not sep or not k.strip().isdigit() or int(k) in out:
+                raise bad
+            if not 1 <= int(k) <= multiclass - 1:
+                raise ValueError(f"config.{key} names class {int(k)}; config.out_classes={multiclass} has the foreground classes 1..{multiclass - 1}")
+            out[int(k)] = number(x)
+        return out
+    keep, small = per_class("class_keep_largest", F.MAX_KEEP_LARGEST), per_class("class_min_voxels")
+    if not keep and not small:
+        return None
+    c = getattr(config, "connectivity", None)
+    if _absent(c):
+        c = 26
+    if isinstance(c, bool) or not (isinstance(c, int) or (isinstance(c, str) and c.strip().isdigit())) or int(c) not in F.CONNECTIVITIES:
+        raise ValueError(f"config.connectivity must be 6, 18 or 26, got {c!r}")
+    return keep, small, int(c)
+
+
+def class_component_rows(name, stats, K):
+    """the rows of one file for write_class_components_csv: one per foreground class 1..K-1, zeros for a class that is absent"""
+    none = dict.fromkeys(COMPONENT_COLUMNS, 0)
+    return [{"file": name, "class": k, **stats.get(k, none)} for k in range(1, K)]
+
+
 def parse_overlap_mode(config):
     """``config.overlap_mode`` -> one of functional.OVERLAP_MODES; "crop" (the reference's mode) when the key is absent or empty."""
     m = getattr(config, "overlap_mode", None)
@@ -397,6 +458,14 @@ def parse_tta(config):
 def write_components_csv(path, rows):
     with open(path, "w", newline="") as fh:
         wr = csv.DictWriter(fh, fieldnames=["file"] + list(COMPONENT_COLUMNS))
+        wr.writeheader()
+        wr.writerows(rows)
+
+
+def write_class_components_csv(path, rows):
+    """config.class_keep_largest / config.class_min_voxels: rows of {file, class, components, kept, voxels_removed, largest}"""
+    with open(path, "w", newline="") as fh:
+        wr = csv.DictWriter(fh, fieldnames=["file"] + list(CLASS_COMPONENT_COLUMNS))
         wr.writeheader()
         wr.writerows(rows)
 
@@ -484,6 +553,7 @@ def predict(config, model, log=print):
     rows, comp_rows = [], []
     spacing = parse_spacing(config)
     post = parse_postprocess(config)
+    class_post = parse_class_postprocess(config, multiclass)      # config.class_keep_largest / config.class_min_voxels; None: off
     intensity = parse_intensity(config)                  # config.intensity and its companions; None: the z-score of today
     if intensity is not None:
         log(f"intensity: {intensity}")
@@ -517,6 +587,12 @@ def predict(config, model, log=print):
             mask, stats = F.filter_components(mask, min_voxels=post[1], keep_largest=post[0], connectivity=post[2], inplace=True)
             comp_rows.append({"file": name, **stats})
             log(f"{name}: " + " ".join(f"{k} {stats[k]}" for k in COMPONENT_COLUMNS))
+        if class_post:
+            mask, stats = F.filter_components_by_class(mask, min_voxels=class_post[1], keep_largest=class_post[0], connectivity=class_post[2],
+                                                       inplace=True)
+            new = class_component_rows(name, stats, multiclass)
+            comp_rows.extend(new)
+            log(f"{name}: " + " ".join(f"kept_{r['class']} {r['kept']}/{r['components']}" for r in new))
         gt_lab = gt.to(device).to(torch.int64).reshape(mask.shape)
         np.save(os.path.join(config.hydra_path, f"{name}_pred.npy"), mask.cpu().numpy().astype(np.uint8))
         if multiclass is not None:
@@ -536,6 +612,8 @@ def predict(config, model, log=print):
     (write_class_metrics_csv if multiclass is not None else write_metrics_csv)(os.path.join(config.hydra_path, "metrics.csv"), rows)
     if post:
         write_components_csv(os.path.join(config.hydra_path, "components.csv"), comp_rows)
+    if class_post:
+        write_class_components_csv(os.path.join(config.hydra_path, "components.csv"), comp_rows)
     return rows
 
 

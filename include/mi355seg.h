@@ -616,6 +616,40 @@ int mi355seg_components_filter_i64(const int64_t* mask, const int32_t* labels, c
                                    long long min_voxels, const int32_t* keep_labels, int n_keep,
                                    int64_t* out, int64_t* removed, void* stream);
 
+/* The class-aware labelling: two voxels are joined only when they are neighbours under `connectivity` AND
+ * carry the same value 1..255; the reference is scipy.ndimage.label(mask == k, ...) for every value k != 0 that occurs.  All
+ * classes are labelled by one call.  Arguments, labels and sizes as mi355seg_components_label_i64: a component is a component of
+ * one class, components of different classes have different first voxels, so one labels volume holds them all; the class of a
+ * component is the mask value at its first voxel.  0 and every value outside 0..255 is background.
+ * info: int64[8] = slots 0..3 as mi355seg_components_label_i64 over all classes, slot 4 = voxels whose value lies outside 0..255
+ * (the caller's refusal; they are background in labels and sizes), slots 5..7 = 0.  8-byte aligned.
+ * ws: mi355seg_components_classes_ws_bytes(D, H, W) (0 for bad extents): the binary call's plus one byte per voxel.
+ * _steps_: the call cut short after its first `steps` of five launches, as above, for tools/bench_class_components.py. */
+size_t mi355seg_components_classes_ws_bytes(int D, int H, int W);
+int mi355seg_components_label_classes_i64(const int64_t* mask, int D, int H, int W, int connectivity,
+                                          int32_t* labels, int32_t* sizes, int64_t* info,
+                                          void* ws, size_t ws_bytes, void* stream);
+int mi355seg_components_label_classes_steps_i64(const int64_t* mask, int D, int H, int W, int connectivity,
+                                                int32_t* labels, int32_t* sizes, int64_t* info,
+                                                void* ws, size_t ws_bytes, int steps, void* stream);
+
+/* The compact table of the n components of a labelling (either form), ranked by first voxel in raster order -- the order in which
+ * scipy.ndimage.label numbers them --, and the consecutive labels: first[k] = raster index of the first voxel, size[k] = voxels,
+ * cls[k] = mask value at the first voxel of the component of rank k (int32[n], int32[n], int64[n]);
+ * labels_consecutive: int32 [numel] = rank + 1 of the voxel's component, 0 on background.  n = info[1] of the labelling call, read
+ * back by the caller: it sizes the three tables, and a component whose rank is not below n writes none of them.  n = 0: the tables
+ * may be NULL.  labels, sizes, labels_consecutive and ws 16-byte aligned.  ws: mi355seg_components_table_ws_bytes(numel). */
+size_t mi355seg_components_table_ws_bytes(long long numel);
+int mi355seg_components_table_i64(const int64_t* mask, const int32_t* labels, const int32_t* sizes, long long numel, long long n,
+                                  int32_t* labels_consecutive, int32_t* first, int32_t* size, int64_t* cls,
+                                  void* ws, size_t ws_bytes, void* stream);
+
+/* out[v] = (labels_consecutive[v] == 0 || keep[labels_consecutive[v] - 1]) ? mask[v] : 0 with one flag per component of the
+ * table (uint8[n] on the device, non-zero = keep; n = 0: keep may be NULL; a label above n is not kept).  Mask values are preserved.
+ * out may be mask itself.  removed: int64[1] = the number of voxels set to 0.  labels_consecutive 8-byte aligned. */
+int mi355seg_components_filter_table_i64(const int64_t* mask, const int32_t* labels_consecutive, const uint8_t* keep, long long n,
+                                         long long numel, int64_t* out, int64_t* removed, void* stream);
+
 /* The 2-channel target of the live loop (train.py:190-193): out[n][0] = (gt[n] == 0), out[n][1] = gt[n], float [N,2,S]. */
 int mi355seg_two_channel_gt_f32(const float* gt, float* out, long long N, long long S, void* stream);
 
